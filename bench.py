@@ -9,6 +9,13 @@ One step = PWC-Net flow + mask-generator fwd + 3x recover fwd + generator-loss b
 both clipped-Adam updates on 4 DAVIS-480p-shaped synthetic frame pairs per GPU (BASELINE.json configs[1]/[2]).
 Inputs are resident in HBM (reader preprocessing done before the timed region).  Prints ONE JSON line.
 
+A plain run sets up (plan, weights, kernel configurations, resident inputs), runs W warm-up and K timed steps and prints the
+headline line (value, ms_per_step and the per-step distribution).  `--dump-outputs DIR` also writes what the last timed step computed
+as DIR/<name>.npy (float32).  Inputs are seeded and the kernel configurations of the headline workload are the committed ones
+(SHIPPED_TUNE), so every run of the same arguments computes the same outputs and two builds can be compared output for output.
+
+`--full` adds everything else the line has carried: the CPU-oracle leg and both parity checks, the reference schedule, the
+ensemble workload, the per-launch profiling pass (roofline, hbm_kernels) and, with N > 1, the gradient-exchange timings.
 The GPU leg and the CPU-oracle leg (`cpu_baseline`, rank 0 at N=1) run the SAME seeded weights on the SAME frame pairs;
 their first (untimed) step is compared -- `parity_check` in the JSON line -- and the process exits non-zero when the HIP path
 is more than 1e-3 (north_star tolerance) away from the oracle."""
@@ -29,6 +36,12 @@ ENSEMBLE_GFLOP_PER_FRAME = 1983.5  # 16 x (PWC-Net + generat
 PEAK_FP32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md chip table
 PEAK_HBM_GBS = 8000.0
 PARITY_TOL = 1e-3
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+# The kernel configurations the autotuner picked for this build on the headline workload (fp32, batch 4), on an MI355X.  Timing picks
+# between near-equal candidates differently from run to run, and another split count or kernel family rounds differently -- which
+# Adam turns into step-sized weight differences within a few steps.  Loaded before the autotune pass (which then times only the
+# shapes the file lacks: other batch sizes, fp16 convolutions), they make every run of the same arguments compute the same outputs.
+SHIPPED_TUNE = os.path.join(ROOT, "profiles", "r06_tune.txt")
 
 
 def cpu_baseline(weights, i1, i2, gpu_first, reps: int, threads: int = 0, tol: float = None):
@@ -220,11 +233,36 @@ def ensemble_workload(eng, frames_u8, shifts, reps):
             "tflops_algorithmic": round(ENSEMBLE_GFLOP_PER_FRAME * len(shifts) / 4.0 * reps / dt / 1e3, 2)}
 
 
+def dump_outputs(out_dir, eng, st):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy -- its losses, the flow, mask and predictions of
+    its forward pass, both networks' gradients and the weights its optimizer left.  Must run before any other work on the plan (the
+    buffers are overwritten by the next forward).  Above DUMP_LIMIT_BYTES in all (batches above 8) every array becomes the same fixed,
+    seeded sample of its flattened elements (the losses stay whole)."""
+    import numpy as np
+    arrays = {"losses": eng.buffer("losses").reshape(-1), "flow": eng.buffer("flow"), "mask": eng.buffer("mask"), "pred": eng.buffer("pred"),
+              "grad_generator": st.g_gen, "grad_recover": st.g_rec, "weights_generator": st.w_gen, "weights_recover": st.w_rec}
+    total = sum(4 * t.numel() for t in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float().cpu()
+        if total > DUMP_LIMIT_BYTES and t.numel() > 4096:
+            keep = t.numel() * (DUMP_LIMIT_BYTES - 65536) // total  # (room for the files' headers)
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every extra measurement and check of the line: "
+                    "CPU-oracle leg and parity checks, reference schedule, ensemble workload, profiling pass (roofline, hbm_kernels), "
+                    "gradient-exchange timings (--no-cpu-baseline, --cpu-reps, --cycles, --ensemble-frames, --pmc-json and --save-state act only "
+                    "with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed (losses, flow, mask, "
+                    "predictions, gradients, updated weights) to DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--batch", type=int, default=0, help="frame pairs per GPU (BASELINE.json: 4; 2 with --fp16-convs)")
     ap.add_argument("--fp16-convs", action="store_true", help="BASELINE.json configs[4]: the convolution GEMMs multiply in fp16 with fp32 "
                     "accumulation (udet_config.conv_fp16), batch 2/GPU, SegTrackV2-shaped pairs (its reader resizes to the same 384x640); "
@@ -251,6 +289,8 @@ def main():
                     help="PMC counters of whole steps collected offline with tools/pmc_step.py (separate rocprofv3 --pmc passes); fills "
                          "roofline.traffic with the convolution kernels' HBM bytes per step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.trace_only:
         args.no_cpu_baseline, args.cycles, args.ensemble_frames = True, 0, 0
     if args.batch <= 0:
@@ -330,15 +370,21 @@ def main():
             torch.zeros(16, device="cuda").add_(1.0)
     torch.cuda.synchronize()
     eng = Engine(EngineConfig(batch_size=args.batch, conv_fp16=args.fp16_convs), device=f"cuda:{local_rank}")
-    loaded = 0
+    loaded, shipped = 0, 0
     if args.tune_cache and os.path.exists(args.tune_cache):
         loaded = max(0, int(lib.udet_tune_load(args.tune_cache.encode())))  # < 0: a file of another build -> tune again
+    elif not args.tune_cache and not args.no_autotune:
+        shipped = int(lib.udet_tune_load(SHIPPED_TUNE.encode()))
+        if shipped < 0:  # (a build whose tuning ABI moved on: every shape is timed, and runs may differ in their last bits)
+            print("bench.py: %s is not a tuning file of this build; autotuning every shape" % os.path.relpath(SHIPPED_TUNE, ROOT),
+                  file=sys.stderr, flush=True)
+            shipped = 0
     # (N > 1: rank 0 tunes and the other ranks load its configurations -- TrainState._autotune_shared -- so every GPU runs the same kernels)
     st = TrainState(eng, seed=8964, autotune=not (args.no_autotune or loaded > 0))  # identical weights on every rank; kernels autotuned once
     if args.tune_cache and not loaded and not args.no_autotune and rank == 0:
         lib.udet_tune_save(args.tune_cache.encode())
     w0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # the oracle leg starts from the same weights
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:  # the oracle leg starts from the same weights
         w0 = tuple(W.as_dict(t.cpu().clone(), n) for t, n in ((st.w_pwc, W.NET_PWC), (st.w_gen, W.NET_GEN), (st.w_rec, W.NET_REC)))
     # NPAIRS distinct resident batches per rank, visited round-robin (distinct data per rank: weak scaling); batch 0 is the one
     # the parity check and the CPU-oracle leg use
@@ -413,6 +459,45 @@ def main():
     pairs_per_s = args.batch * world * args.steps / dt
     losses = eng.losses()
     stage("timed region done")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, st)
+    headline = {
+        "metric": "frame-pairs/sec per adversarial step, DAVIS 480p batch4, 1/2/4/8 GPU",
+        "value": round(pairs_per_s, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms, 3),
+        # SURVEY 8d protocol: per-step times from HIP events on the launch stream over the same K timed steps
+        "ms_per_step_median": round(pct(0.5), 3), "ms_per_step_p95": round(pct(0.95), 3), "ms_per_step_min": round(step_ms[0], 3),
+        "ms_per_step_max": round(step_ms[-1], 3), "value_at_median": round(args.batch * world / (pct(0.5) * 1e-3), 3),
+        "resident_batches": NPAIRS,
+        "lanes": {"hardware_queues_in_use": lane_nq, "queue_of_lane": lane_q, "extra_streams": args.extra_streams},
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16 x f16 -> f32 in the convolution MFMAs (fp32 tensors, losses, reductions, optimizer)" if args.fp16_convs else "f32",
+        "data": "synthetic (DAVIS-480p-shaped pairs, reader preprocessing applied before timing; random-init weights)",
+        "config": {"workload": ("BASELINE.json configs[4]: SegTrackV2-shaped pairs -> 384x640 (PWC) -> 192x384, batch %d/GPU, fp16 convs with "
+                                "fp32 loss accumulation, PWC flow + generator + 3x inpainter fwd + both backward + clipped Adam" % args.batch)
+                               if args.fp16_convs else
+                               "BASELINE.json configs[%d]: DAVIS2016 480p -> 384x640 (PWC) -> 192x384, batch %d/GPU, "
+                               "PWC flow + generator + 3x inpainter fwd + both backward + clipped Adam" % (1 if world == 1 else 2, args.batch),
+                   "global_batch": args.batch * world, "parallelism": "dp%d" % world,
+                   "alg_gflop_per_pair": ALG_GFLOP_PER_PAIR},
+        "step_tflops_algorithmic": round(ALG_GFLOP_PER_PAIR * 1e9 * args.batch * world / (ms * 1e-3) / 1e12, 2),
+        "execution": {"autotuned_shapes": getattr(st, "tuned_shapes", 0) or loaded, "tuned_configurations_loaded": loaded,
+                      "shipped_configurations_loaded": shipped,
+                      "tune_rejected": int(lib.udet_tune_rejected()), "pipelined": nxt is not None,
+                      "note": "step = forward(prefetched PWC flow) + PWC flow of the next pair beside both backward passes "
+                              "+ 2 applies; every timed step contains all of that work exactly once"},
+        "process_group": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
+                           "forced_at_world_size_one": world == 1} if dp else None),
+        "losses": {k: round(v, 5) for k, v in losses.items()},
+        "release_library": release_library,
+    }
+    if not args.full and not args.trace_only:  # a plain run: the headline and nothing else
+        if rank == 0:
+            print(json.dumps(headline), file=json_out, flush=True)
+        if dp:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     # Parity AFTER the timed region (the step-0 check alone does not show that the timed steps did their work): the weights the
     # K + W steps left behind are the starting point of a second comparison with the oracle -- forward, losses and BOTH backward passes of
     # the HIP path on them, by the very calls the timed loop makes (eng.forward / eng.backward inside train_step), against the CPU oracle on
@@ -659,40 +744,14 @@ def main():
                 hbm["warp_cost_volume"]["largest_launch"] = {"level": big[1], "alg_MB": round(big[4], 2), "ms": round(big[2], 4),
                                                              "achieved_GBs": round(big[4] / big[2], 1),
                                                              "frac_of_8TBs": round(big[4] / big[2] / PEAK_HBM_GBS, 4)}
-        out = {
-            "metric": "frame-pairs/sec per adversarial step, DAVIS 480p batch4, 1/2/4/8 GPU",
-            "value": round(pairs_per_s, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms, 3),
-            # SURVEY 8d protocol: per-step times from HIP events on the launch stream over the same K timed steps
-            "ms_per_step_median": round(pct(0.5), 3), "ms_per_step_p95": round(pct(0.95), 3), "ms_per_step_min": round(step_ms[0], 3),
-            "ms_per_step_max": round(step_ms[-1], 3), "value_at_median": round(args.batch * world / (pct(0.5) * 1e-3), 3),
-            "resident_batches": NPAIRS,
-            "lanes": {"hardware_queues_in_use": lane_nq, "queue_of_lane": lane_q, "extra_streams": args.extra_streams},
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f16 x f16 -> f32 in the convolution MFMAs (fp32 tensors, losses, reductions, optimizer)" if args.fp16_convs else "f32",
-            "data": "synthetic (DAVIS-480p-shaped pairs, reader preprocessing applied before timing; random-init weights)",
-            "config": {"workload": ("BASELINE.json configs[4]: SegTrackV2-shaped pairs -> 384x640 (PWC) -> 192x384, batch %d/GPU, fp16 convs with "
-                                    "fp32 loss accumulation, PWC flow + generator + 3x inpainter fwd + both backward + clipped Adam" % args.batch)
-                                   if args.fp16_convs else
-                                   "BASELINE.json configs[%d]: DAVIS2016 480p -> 384x640 (PWC) -> 192x384, batch %d/GPU, "
-                                   "PWC flow + generator + 3x inpainter fwd + both backward + clipped Adam" % (1 if world == 1 else 2, args.batch),
-                       "global_batch": args.batch * world, "parallelism": "dp%d" % world,
-                       "alg_gflop_per_pair": ALG_GFLOP_PER_PAIR},
-            "step_tflops_algorithmic": round(alg_flops * world / (ms * 1e-3) / 1e12, 2),
+        out = dict(headline)
+        out.update({
             "roofline": roofline, "hbm_kernels": hbm,
             "profile_ms_per_step_serial": {k: round(v["ms"], 3) for k, v in prof.items() if v["groups"] > 0},
-            "execution": {"autotuned_shapes": getattr(st, "tuned_shapes", 0) or loaded, "tuned_configurations_loaded": loaded,
-                          "tune_rejected": int(lib.udet_tune_rejected()), "pipelined": nxt is not None,
-                          "note": "step = forward(prefetched PWC flow) + PWC flow of the next pair beside both backward passes "
-                                  "+ 2 applies; every timed step contains all of that work exactly once"},
             "allreduce_ms": allreduce_ms, "gradient_exchange": exchange,
-            "process_group": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                               "forced_at_world_size_one": world == 1} if dp else None),
             "reference_schedule": ref_cycle,
             "ensemble": ensemble,
-            "losses": {k: round(v, 5) for k, v in losses.items()},
-            "release_library": release_library,
-        }
+        })
         if w0 is not None:
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(w0, img1.cpu(), img2.cpu(), gpu_first, args.cpu_reps,
                                                                     tol=2e-2 if args.fp16_convs else None)

@@ -19,7 +19,7 @@ def test_two_ranks_complete_and_report_once():
     env = dict(os.environ, UDET_BENCH_ONE_GPU="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cycles", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -44,7 +44,7 @@ def test_gpus_flag_without_a_launcher_starts_the_ranks_itself():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(UDET_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--cycles", "0", "--no-cpu-baseline",
-           "--ensemble-frames", "0"]
+           "--ensemble-frames", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -65,7 +65,7 @@ def test_rccl_branch_at_world_size_one():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "UDET_BENCH_ONE_GPU")}
     env.update(UDET_DP_WORLD1="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--cycles", "1", "--no-cpu-baseline",
-           "--ensemble-frames", "0"]
+           "--ensemble-frames", "0", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -80,6 +80,42 @@ def test_rccl_branch_at_world_size_one():
     # round 6: the line names the library that produced it (the release build has no experiment knobs) and carries the algorithmic bytes
     assert out["release_library"] == {"file": "libudet.so", "experiment_knobs": "compiled out", "debug_hooks_loaded": False}
     assert out["roofline"]["alg_bytes_per_step"] > 4e9 and out["roofline"]["alg_bytes_forward"] > 2e9
+
+
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps and the headline line -- none of the extra legs -- and --dump-outputs
+    writes the last timed step's arrays (float32, at most 64 MB) whose losses are the line's.  A second run of the same arguments
+    writes the same bits: the committed kernel configurations leave no timing-dependent choice in the path."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "UDET_BENCH_ONE_GPU",
+                                                            "UDET_DP_WORLD1")}
+    outs = []
+    for run in ("a", "b"):
+        dump = tmp_path / run
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+        r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+    out = outs[1]
+    assert out["execution"]["shipped_configurations_loaded"] > 0
+    assert out["unit"] == "frame-pairs/s" and out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 3
+    assert out["ms_per_step"] > 0 and abs(out["value"] - 4 / (out["ms_per_step"] * 1e-3)) < 1e-2 * out["value"]
+    for extra in ("cpu_baseline", "parity_check", "reference_schedule", "ensemble", "roofline", "allreduce_ms"):
+        assert extra not in out
+    files = {p.name: np.load(p) for p in dump.iterdir()}
+    assert set(files) == {n + ".npy" for n in ("losses", "flow", "mask", "pred", "grad_generator", "grad_recover", "weights_generator",
+                                               "weights_recover")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert sum(p.stat().st_size for p in dump.iterdir()) <= 64 * 10 ** 6
+    assert files["pred.npy"].shape[:3] == (12, 192, 384) and files["weights_recover.npy"].size > 3e6
+    for i, k in enumerate(("generator", "recover")):
+        assert abs(float(files["losses.npy"][i]) - out["losses"][k]) < 1e-4 * max(1.0, abs(out["losses"][k]))
+    for name, a in files.items():
+        assert np.array_equal(a, np.load(tmp_path / "a" / name)), name
 
 
 def test_experiment_build_is_refused_and_labelled():

@@ -7,8 +7,8 @@ import torch
 import os
 
 pytestmark = [pytest.mark.gpu,
-              pytest.mark.skipif("GPU_MAX_HW_QUEUES" in os.environ, reason="the layout asserted here is that of ROCm's default of four hardware "
-                                 "queues; GPU_MAX_HW_QUEUES is exported")]
+              pytest.mark.skipif(os.environ.get("GPU_MAX_HW_QUEUES", "4") != "4", reason="the layout asserted here is that of ROCm's default "
+                                 "of four hardware queues; GPU_MAX_HW_QUEUES sets another number")]
 
 LAYOUT = [0, 1, 0, 2, 3, 3]  # {caller's stream, lane 2} {1} {3} {4, 5}
 

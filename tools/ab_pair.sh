@@ -4,7 +4,7 @@
 # the repository: build it from the revision to compare with (make -C unsupervised_detection_amd/csrc at that revision) and copy it to
 # gpurun_exp/libudet_base.so (git-ignored, but it travels to the GPU box).  Output: profiles/r06_ab_ladder.txt has the round's runs.
 mkdir -p gpurun_out/r6t; O=gpurun_out/r6t
-A="--steps 40 --no-cpu-baseline --cycles 0 --ensemble-frames 0"
+A="--full --steps 40 --no-cpu-baseline --cycles 0 --ensemble-frames 0"
 for i in 1 2; do
 python bench.py $A > $O/new$i.json 2>/dev/null
 python tools/ab_bench.py --lib gpurun_exp/libudet_base.so -- $A > $O/base$i.json 2>/dev/null

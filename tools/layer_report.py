@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch report of one profiled step.
 
-  UDET_PROF_DUMP=layers.csv python bench.py --steps 20 --warmup 5 --no-cpu-baseline --cycles 0
+  UDET_PROF_DUMP=layers.csv python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --cycles 0
   python tools/layer_report.py layers.csv [--rate 100] [--top 40]
 
 The CSV (one line per launch group of the serial profiling pass: category, layer, ms, algorithmic GFLOP, MB) is written by

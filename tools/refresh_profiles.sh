@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/prof
 mkdir -p "$O"
 cd "$R"
-UDET_TUNE_LOG=1 UDET_PROF_DUMP=$O/layers.csv python bench.py --tune-cache "$O/tune.txt" > "$O/bench.json" 2> "$O/bench.err"
+UDET_TUNE_LOG=1 UDET_PROF_DUMP=$O/layers.csv python bench.py --full --tune-cache "$O/tune.txt" > "$O/bench.json" 2> "$O/bench.err"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/tr_s /tmp/tr_p
 UDET_SERIAL=1 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_s -o steps -- \
@@ -28,9 +28,9 @@ python "$R/tools/pmc_step.py" --tune-cache "$O/tune.txt" --out "$O/pmc_step.json
 cd "$R"
 python tools/cv_bench.py > "$O/cv_bench.txt" 2>&1
 # 5. BASELINE configs[4] (fp16 convolution GEMMs, batch 2) beside fp32 at that batch; the RCCL branch at world size 1 (allreduce_ms of a one-rank group)
-python bench.py --fp16-convs --cycles 0 --ensemble-frames 0 > "$O/bench_fp16_convs.json" 2> "$O/bench_fp16.err"
-python bench.py --batch 2 --cycles 0 --ensemble-frames 0 --no-cpu-baseline > "$O/bench_fp32_batch2.json" 2> /dev/null
-UDET_DP_WORLD1=1 python bench.py --tune-cache "$O/tune.txt" --pmc-json "$O/pmc_step.json" --cycles 0 --ensemble-frames 0 --no-cpu-baseline > "$O/bench_rccl_world1.json" 2> "$O/bench_rccl_world1.err"
+python bench.py --full --fp16-convs --cycles 0 --ensemble-frames 0 > "$O/bench_fp16_convs.json" 2> "$O/bench_fp16.err"
+python bench.py --full --batch 2 --cycles 0 --ensemble-frames 0 --no-cpu-baseline > "$O/bench_fp32_batch2.json" 2> /dev/null
+UDET_DP_WORLD1=1 python bench.py --full --tune-cache "$O/tune.txt" --pmc-json "$O/pmc_step.json" --cycles 0 --ensemble-frames 0 --no-cpu-baseline > "$O/bench_rccl_world1.json" 2> "$O/bench_rccl_world1.err"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -Wno-unused-value -o /tmp/mfma_peak tools/mfma_peak.hip 2> /dev/null && /tmp/mfma_peak > "$O/mfma_peak.txt" 2>&1
 # 6. round 6: the F(4x4,3x3) prototype with its ablations, the fixed-cost anatomy of the Winograd / LDS-DMA launches (libudet_exp.so:
 #    make -C unsupervised_detection_amd/csrc exp), the Winograd per-stage / intercept fit
@@ -42,5 +42,5 @@ fi
 python tools/wino_fixed_cost.py 2> /dev/null | grep -v amdgpu.ids > "$O/wino_fixed_cost.txt"
 # 7. the bench line once more, on the configurations of step 1 and with THIS call's counters in roofline.traffic (step 1 ran before them)
 mv "$O/bench.json" "$O/bench_tuning_run.json"
-python bench.py --tune-cache "$O/tune.txt" --pmc-json "$O/pmc_step.json" > "$O/bench.json" 2> "$O/bench_final.err"
+python bench.py --full --tune-cache "$O/tune.txt" --pmc-json "$O/pmc_step.json" > "$O/bench.json" 2> "$O/bench_final.err"
 ls -la "$O"

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Per-step kernel table from a rocprofv3 kernel trace of TIMED STEPS ONLY.
 
-  # 1. a tuning run writes the configurations it picked (and the per-launch CSV of its measurement pass)
-  UDET_PROF_DUMP=gpurun_out/layers.csv python bench.py --tune-cache gpurun_out/tune.txt > gpurun_out/bench.json
+  # 1. a tuning run writes the configurations it picked (and, with --full, the per-launch CSV of its measurement pass)
+  UDET_PROF_DUMP=$OUT/layers.csv python bench.py --full --tune-cache $OUT/tune.txt > $OUT/bench.json
   # 2. a second process loads them (no tuning pass, no oracle leg, no measurement pass) and is traced
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats -d $REPO/gpurun_out/trace -o steps --output-format csv -- \
-      python $REPO/bench.py --tune-cache $REPO/gpurun_out/tune.txt --trace-only --steps 20 --warmup 2
-  # 3. this script
-  python tools/trace_report.py gpurun_out/trace --steps 22 --layers gpurun_out/layers.csv --out profiles/rNN_trace_report.json \
+  rocprofv3 --kernel-trace --stats -d $OUT/trace -o steps --output-format csv -- \
+      python $REPO/bench.py --tune-cache $OUT/tune.txt --trace-only --steps 20 --warmup 2
+  # 3. this script ($OUT: any absolute output directory)
+  python tools/trace_report.py $OUT/trace --steps 22 --layers $OUT/layers.csv --out profiles/rNN_trace_report.json \
       --copy-stats profiles/rNN_kernel_stats_steps.csv
 
 The trace holds plan construction (a few pack / memset kernels), 2 warm-up and 20 timed steps -- every step launches the same
