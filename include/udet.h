@@ -67,6 +67,15 @@ int udet_resize_bilinear_legacy_bwd(const float* dy, float* dx, int n, int h, in
  * dst [n,oh,ow,c] float32, params6 device int32 [n][6] = {y0, x0, crop_h, crop_w, flip_lr, flip_td} or NULL. */
 int udet_crop_flip_resize(const void* src, int src_is_u8, int nearest, int n, int h, int w, int c, const int* params6,
                           float* dst, int oh, int ow, float div, float add, void* stream);
+/* The same input stage over n sources of DIFFERENT sizes in one launch (mixed-resolution FBMS-59 / SegTrackV2 batches).
+ * src: packed uint8 or float32 elements; offsets: device int64 [n], element offset of sample i; hw: device int32 [n][2] =
+ * {h_i, w_i}; params6: device int32 [n][6] = {y0, x0, crop_h, crop_w, flip_lr, flip_td} relative to sample i's own h_i x w_i,
+ * or NULL (whole image, no flip).  Every sample has c channels; dst [n,oh,ow,c] float32.  dst[i] is bit-identical to
+ * udet_crop_flip_resize on sample i alone with params6[i].  Only the scalar arguments are checked here: the tables are
+ * device memory and must describe windows inside each sample and samples inside src (the Python wrapper validates them). */
+int udet_crop_flip_resize_ragged(const void* src, int src_is_u8, int nearest, int n, int c, const long long* offsets,
+                                 const int* hw, const int* params6, float* dst, int oh, int ow, float div, float add,
+                                 void* stream);
 
 /* Evaluation tail ("next" row N2): the per-sample sums behind compute_boundary_score / disambiguate_forw_back /
  * tf_iou_computation / compute_all_IoU (models/utils/general_utils.py:89-159) and compute_IoU / compute_mae

@@ -5,9 +5,11 @@
   python -m unsupervised_detection_amd.cli test_generator_ensemble --root_dir ... --test_save_dir ...       (test_generator_ensemble.py)
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
-counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  Like the reference, a missing
-dataset, an unsupported --dataset or a missing --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs
-and seeded random weights (benchmarks, smoke runs)."""
+counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
+DAVIS2016 (data.Davis2016Reader), FBMS (datasets.FBMS59Reader) or SEGTRACK (datasets.SegTrackV2Reader; --test_partition does
+not apply to it, as in the reference).  Like the reference, a missing dataset, an unsupported --dataset or a missing
+--flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
+runs)."""
 from __future__ import annotations
 
 import os
@@ -17,46 +19,69 @@ import numpy as np
 
 
 def _sources(flags, mode):
-    """data_source / val_source of the learner from the dataset flags (DAVIS2016 layout; adversarial_learner.py:45-70)."""
-    from . import data
+    """data_source / val_source of the learner from the dataset flags (adversarial_learner.py:30-70, 459-477, 537-552)."""
     if getattr(flags, "synthetic", False):
         return
-    if flags.dataset != "DAVIS2016":
-        # the FBMS / SegTrackV2 directory layouts are not built (their per-image pipeline is the DAVIS one); never fall back silently
-        raise IOError("Dataset should be DAVIS2016 (FBMS / SEGTRACK readers are not built in this port)")
+    dataset_sources(flags, mode)
+
+
+def _reader(flags, rank, world):
+    """The reader --dataset names, with the shard of this rank; a missing dataset root is an IOError."""
+    from . import data, datasets
     root = getattr(flags, "root_dir", "")
-    if not (root and os.path.isfile(os.path.join(root, "ImageSets", "480p", "val.txt"))):
-        raise IOError("Partition file not found under --root_dir {!r} (DAVIS2016 layout: ImageSets/480p/val.txt)".format(root))
+    kw = dict(max_temporal_len=flags.max_temporal_len, min_temporal_len=flags.min_temporal_len, num_threads=flags.num_threads,
+              seed=8964, shard=(rank, world))
+    if flags.dataset == "DAVIS2016":
+        if not (root and os.path.isfile(os.path.join(root, "ImageSets", "480p", "val.txt"))):
+            raise IOError("Partition file not found under --root_dir {!r} (DAVIS2016 layout: ImageSets/480p/val.txt)".format(root))
+        return data.Davis2016Reader(root, **kw)
+    if flags.dataset == "FBMS":
+        if not (root and os.path.isdir(root)):
+            raise IOError("Directory {!r} not found (FBMS layout: Trainingset/ and Testset/)".format(root))
+        return datasets.FBMS59Reader(root, **kw)
+    if flags.dataset == "SEGTRACK":
+        if not (root and os.path.isfile(os.path.join(root, "ImageSets", "all.txt"))):
+            raise IOError("Division file not found under --root_dir {!r} (SegTrackV2 layout: ImageSets/all.txt)".format(root))
+        return datasets.SegTrackV2Reader(root, **kw)
+    raise IOError("Dataset should be DAVIS2016 / FBMS / SEGTRACK")
+
+
+class _Listed(list):
+    """A one-pass test reader read out once: `n` batches (AdversarialLearner.setup_inference counts test samples by it)."""
+
+    def __init__(self, batches):
+        super().__init__(batches)
+        self.n = len(self)
+
+
+def dataset_sources(flags, mode):
+    """_sources without the --synthetic short cut: the readers of --dataset under --root_dir for `mode` (train / test /
+    ensemble), on flags.data_source (and flags.val_source when training)."""
     import torch.distributed as dist
     ddp = dist.is_available() and dist.is_initialized()
     rank, world = (dist.get_rank(), dist.get_world_size()) if ddp else (0, 1)
     # data-parallel training: one shuffle shared by the ranks, each takes its own rows of every global batch (disjoint pairs;
     # an epoch = the pair table once = num_samples_train / (batch_size * world) steps, see AdversarialLearner.train)
-    rd = data.Davis2016Reader(root, max_temporal_len=flags.max_temporal_len, min_temporal_len=flags.min_temporal_len,
-                              num_threads=flags.num_threads, seed=8964, shard=(rank, world))
+    rd = _reader(flags, rank, world)
+    segtrack = flags.dataset == "SEGTRACK"  # no partition argument (segtrackv2_data_utils.py)
+    part = lambda p: {} if segtrack else {"partition": p}
     if mode == "train":
-        flags.data_source = rd.image_inputs(batch_size=flags.batch_size, partition=flags.train_partition, train_crop=flags.train_crop)
+        flags.data_source = rd.image_inputs(batch_size=flags.batch_size, train_crop=flags.train_crop, **part(flags.train_partition))
 
         class _Val:
             def __iter__(self_inner):
                 # adversarial_learner.py:34-37: the validation reader uses test_temporal_shift / test_crop
-                return iter(rd.test_inputs(batch_size=flags.batch_size, partition="val", t_len=flags.test_temporal_shift,
-                                           test_crop=flags.test_crop))
+                return iter(rd.test_inputs(batch_size=flags.batch_size, t_len=flags.test_temporal_shift, test_crop=flags.test_crop,
+                                           **part("val")))
         flags.val_source = _Val()
     elif mode == "test":
-        src = list(rd.test_inputs(batch_size=flags.batch_size, partition=flags.test_partition, t_len=flags.test_temporal_shift,
-                                  with_fname=True, test_crop=flags.test_crop))
-
-        class _S(list):
-            n = len(src)
-        flags.data_source = _S(src)
+        flags.data_source = _Listed(rd.test_inputs(batch_size=flags.batch_size, t_len=flags.test_temporal_shift, with_fname=True,
+                                                   test_crop=flags.test_crop, **part(flags.test_partition)))
     else:
-        src = list(rd.test_inputs(batch_size=1, partition=flags.test_partition, t_len=flags.test_temporal_shift, with_fname=True,
-                                  test_crop=1.0))
-
-        class _S(list):
-            n = len(src)
-        flags.data_source = _S(src)
+        if flags.dataset == "FBMS":
+            assert "FBMS" in flags.root_dir  # adversarial_learner.py:542
+        flags.data_source = _Listed(rd.test_inputs(batch_size=1, t_len=flags.test_temporal_shift, with_fname=True, test_crop=1.0,
+                                                   **part(flags.test_partition)))
 
 
 def main(argv=None):

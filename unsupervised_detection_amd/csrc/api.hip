@@ -83,6 +83,11 @@ int udet_crop_flip_resize(const void* src, int src_is_u8, int nearest, int n, in
   if (n < 1 || h < 1 || w < 1 || c < 1 || oh < 1 || ow < 1 || !src || !dst) { set_error("crop_flip_resize: bad argument"); return UDET_ERR_ARG; }
   return launch_crop_flip_resize(src, src_is_u8, nearest, n, h, w, c, params6, dst, oh, ow, div, add, (hipStream_t)stream);
 }
+int udet_crop_flip_resize_ragged(const void* src, int src_is_u8, int nearest, int n, int c, const long long* offsets,
+                                 const int* hw, const int* params6, float* dst, int oh, int ow, float div, float add, void* stream) {
+  if (n < 1 || c < 1 || oh < 1 || ow < 1 || !src || !dst || !offsets || !hw) { set_error("crop_flip_resize_ragged: bad argument"); return UDET_ERR_ARG; }
+  return launch_crop_flip_resize_ragged(src, src_is_u8, nearest, n, c, offsets, hw, params6, dst, oh, ow, div, add, (hipStream_t)stream);
+}
 
 int udet_mask_stats(const float* pred_masks, const float* gt_masks, int n, int h, int w, float threshold, float gt_threshold,
                     double* stats8, void* stream) {

@@ -35,6 +35,8 @@ int launch_charbonnier(const float* gt, const float* pred, const float* mask, in
                        float* out, hipStream_t s);
 int launch_crop_flip_resize(const void* src, int src_u8, int nearest, int N, int H, int W, int C, const int* prm, float* dst, int OH,
                             int OW, float div, float add, hipStream_t s);
+int launch_crop_flip_resize_ragged(const void* src, int src_u8, int nearest, int N, int C, const long long* offsets, const int* hw,
+                                   const int* prm, float* dst, int OH, int OW, float div, float add, hipStream_t s);
 int launch_mask_stats(const float* pred, const float* gt, int N, int H, int W, float threshold, float gt_threshold, double* out,
                       hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);

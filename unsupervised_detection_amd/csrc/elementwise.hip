@@ -125,6 +125,63 @@ int launch_crop_flip_resize(const void* src, int src_u8, int nearest, int N, int
   return UDET_OK;
 }
 
+// The same input stage over N packed sources of different sizes (mixed-resolution FBMS-59 / SegTrackV2 batches), one launch.
+// blockIdx.y walks the samples, so the sample's descriptor (element offset, h, w, window, flips) is block-uniform and lands in
+// scalar registers; x covers the sample's OH*OW output pixels, one thread per pixel, the C channels in a loop.  Per sample the
+// float32 ops are those of crop_flip_resize_kernel in the same order (conversion per tap, then the legacy lerps), so dst[i] is
+// bit-identical to crop_flip_resize_kernel run on sample i alone.
+template <typename T, int NEAREST>
+__global__ __launch_bounds__(256) void crop_flip_resize_ragged_kernel(const T* __restrict__ src, int N, int C,
+                                                                      const long long* __restrict__ offsets, const int* __restrict__ hw,
+                                                                      const int* __restrict__ prm, float* __restrict__ dst, int OH,
+                                                                      int OW, float div, float add) {
+  const long npix = (long)OH * OW;
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    const T* __restrict__ img = src + offsets[n];
+    const int H = hw[n * 2], W = hw[n * 2 + 1];
+    int y0 = 0, x0 = 0, ch = H, cw = W, flr = 0, ftd = 0;
+    if (prm) { y0 = prm[n * 6]; x0 = prm[n * 6 + 1]; ch = prm[n * 6 + 2]; cw = prm[n * 6 + 3]; flr = prm[n * 6 + 4]; ftd = prm[n * 6 + 5]; }
+    const float sy = (float)ch / (float)OH, sx = (float)cw / (float)OW;
+    float* __restrict__ out = dst + (long)n * npix * C;
+    for (long pix = (long)blockIdx.x * 256 + threadIdx.x; pix < npix; pix += (long)gridDim.x * 256) {
+      const int ox = (int)(pix % OW), oy = (int)(pix / OW);
+      auto tap = [&](int cy, int cx, int c) -> float {
+        int yy = y0 + cy, xx = x0 + cx;
+        if (ftd) yy = H - 1 - yy;
+        if (flr) xx = W - 1 - xx;
+        float v = (float)img[((long)yy * W + xx) * C + c];
+        if (div != 1.f) v = v / div;
+        return v + add;
+      };
+      if (NEAREST) {  // ResizeNearestNeighbor, align_corners=False: min(floor(i*scale), in-1)
+        const int cy = min((int)floorf((float)oy * sy), ch - 1), cx = min((int)floorf((float)ox * sx), cw - 1);
+        for (int c = 0; c < C; ++c) out[pix * C + c] = tap(cy, cx, c);
+      } else {
+        int ly, hy, lx, hx;
+        float ty, tx;
+        legacy_coord(oy, sy, ch, ly, hy, ty);
+        legacy_coord(ox, sx, cw, lx, hx, tx);
+        for (int c = 0; c < C; ++c) {
+          const float tl = tap(ly, lx, c), tr = tap(ly, hx, c), bl = tap(hy, lx, c), br = tap(hy, hx, c);
+          const float top = tl + (tr - tl) * tx, bot = bl + (br - bl) * tx;
+          out[pix * C + c] = top + (bot - top) * ty;
+        }
+      }
+    }
+  }
+}
+int launch_crop_flip_resize_ragged(const void* src, int src_u8, int nearest, int N, int C, const long long* offsets, const int* hw,
+                                   const int* prm, float* dst, int OH, int OW, float div, float add, hipStream_t s) {
+  const int gy = N < 65535 ? N : 65535;
+  const dim3 g(grid_for((long)OH * OW, 1024), gy), b(256);
+  if (src_u8 && nearest) hipLaunchKernelGGL((crop_flip_resize_ragged_kernel<unsigned char, 1>), g, b, 0, s, (const unsigned char*)src, N, C, offsets, hw, prm, dst, OH, OW, div, add);
+  else if (src_u8) hipLaunchKernelGGL((crop_flip_resize_ragged_kernel<unsigned char, 0>), g, b, 0, s, (const unsigned char*)src, N, C, offsets, hw, prm, dst, OH, OW, div, add);
+  else if (nearest) hipLaunchKernelGGL((crop_flip_resize_ragged_kernel<float, 1>), g, b, 0, s, (const float*)src, N, C, offsets, hw, prm, dst, OH, OW, div, add);
+  else hipLaunchKernelGGL((crop_flip_resize_ragged_kernel<float, 0>), g, b, 0, s, (const float*)src, N, C, offsets, hw, prm, dst, OH, OW, div, add);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
 // the same resize, four channels per thread (channel windows that are float4-aligned: every slab of the decoder)
 __global__ __launch_bounds__(256) void resize_bilinear_fwd4_kernel(const float* __restrict__ x, int ldx, int x_coff, int N, int H,
                                                                    int W, float* __restrict__ y, int ldy, int y_coff, int OH,

@@ -280,3 +280,143 @@ def synthetic_davis_pairs(batch: int, seed: int, h: int = 480, w: int = 854, max
         f1[b] = np.round(img * 255).astype(np.uint8)
         f2[b] = np.round(warped * 255).astype(np.uint8)
     return f1, f2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Ragged input stage: frames of different sizes in one batch (FBMS-59, SegTrackV2; datasets.py).  One pinned staging buffer and one
+# H2D copy per batch, one udet_crop_flip_resize_ragged launch per resize; per sample bit-identical to crop_flip_resize.
+# ---------------------------------------------------------------------------------------------------------------------------------
+lib.udet_crop_flip_resize_ragged.restype = c_i
+lib.udet_crop_flip_resize_ragged.argtypes = [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p]
+
+
+def check_ragged_tables(offsets, hw, c, numel, params=None):
+    """Host validation of the tables of udet_crop_flip_resize_ragged (the C entry point does not read device tables).  Returns
+    (offsets int64 [n], hw int32 [n,2], params int32 [n,6] or None); raises ValueError on a sample outside the packed buffer of
+    `numel` elements, a crop window outside its own image or a flip flag other than 0 / 1."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    n = len(off)
+    if n < 1 or c < 1:
+        raise ValueError("ragged batch needs at least one sample and one channel")
+    size = np.asarray(hw, dtype=np.int64).reshape(n, 2)
+    if (size < 1).any() or (size > np.iinfo(np.int32).max).any():
+        raise ValueError("sample sizes must be at least 1x1")
+    if (off < 0).any() or (off + size[:, 0] * size[:, 1] * c > numel).any():
+        raise ValueError("sample outside the packed buffer (offset + h*w*c past its end)")
+    pa = None
+    if params is not None:
+        pa = np.ascontiguousarray(np.asarray(params, dtype=np.int32).reshape(n, 6))
+        if (pa[:, 0] < 0).any() or (pa[:, 1] < 0).any() or (pa[:, 2] < 1).any() or (pa[:, 3] < 1).any() or \
+                (pa[:, 0] + pa[:, 2] > size[:, 0]).any() or (pa[:, 1] + pa[:, 3] > size[:, 1]).any():
+            raise ValueError("crop window outside its own image")
+        if not np.isin(pa[:, 4:], (0, 1)).all():
+            raise ValueError("flip_lr / flip_td must be 0 or 1")
+    return off, np.ascontiguousarray(size.astype(np.int32)), pa
+
+
+def _upload_tables(arrays, device):
+    """Host int arrays -> one pinned buffer -> one non-blocking copy on the current stream; device views in the same order.
+    (A pinned block of torch's host allocator is not handed out again before the copy that read it has finished.)"""
+    raw = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in arrays]
+    pos = np.cumsum([0] + [len(r) for r in raw])
+    host = torch.from_numpy(np.concatenate(raw)).pin_memory()
+    dev = host.to(device, non_blocking=True)
+    return [dev[int(pos[i]):int(pos[i + 1])].view(torch.int64 if a.dtype == np.int64 else torch.int32) for i, a in enumerate(arrays)]
+
+
+def crop_flip_resize_ragged(src: torch.Tensor, offsets, hw, c: int, out_h: int, out_w: int, params=None, nearest: bool = False,
+                            div: float = 1.0, add: float = 0.0, device_tables=None) -> torch.Tensor:
+    """crop_flip_resize over n samples of different sizes, one launch.  src: 1-D contiguous uint8 / float32 GPU tensor, sample i
+    = [hw[i,0], hw[i,1], c] at element offsets[i]; offsets [n] and hw [n,2] host arrays; params [n,6] = (y0, x0, crop_h, crop_w,
+    flip_lr, flip_td) relative to each sample's own size, or None.  device_tables = (offsets, hw) already on the device (the
+    RaggedLoader's copy of these same host tables), else they are uploaded here.  Returns float32 [n,out_h,out_w,c]; row i is
+    bit-identical to crop_flip_resize of sample i alone.  The tables are validated on the host before anything is launched."""
+    off, size, pa = check_ragged_tables(offsets, hw, c, src.numel(), params)
+    if not (src.is_cuda and src.is_contiguous() and src.dtype in (torch.uint8, torch.float32) and src.dim() == 1):
+        raise ValueError("src must be a contiguous 1-D uint8/float32 CUDA(HIP) tensor of packed samples")
+    n = len(off)
+    if device_tables is None:
+        device_tables = _upload_tables([off, size], src.device)
+    d_off, d_hw = device_tables
+    if d_off.numel() != n or d_hw.numel() != 2 * n or d_off.dtype != torch.int64 or d_hw.dtype != torch.int32:
+        raise ValueError("device tables do not match the host tables")
+    prm = _upload_tables([pa], src.device)[0] if pa is not None else None
+    out = torch.empty((n, out_h, out_w, c), dtype=torch.float32, device=src.device)
+    check(lib.udet_crop_flip_resize_ragged(src.data_ptr(), int(src.dtype == torch.uint8), int(nearest), n, c, d_off.data_ptr(),
+                                           d_hw.data_ptr(), prm.data_ptr() if prm is not None else None, out.data_ptr(), out_h,
+                                           out_w, div, add, torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+class RaggedBatch(object):
+    """Decoded frames of different sizes packed on the device: data (1-D uint8), host tables offsets [n] / hw [n,2], their device
+    copies, c channels."""
+
+    def __init__(self, data, offsets, hw, c, dev_offsets, dev_hw):
+        self.data, self.offsets, self.hw, self.c = data, offsets, hw, c
+        self.dev_offsets, self.dev_hw = dev_offsets, dev_hw
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def resize(self, out_h, out_w, params=None, nearest=False, div=1.0, add=0.0):
+        return crop_flip_resize_ragged(self.data, self.offsets, self.hw, self.c, out_h, out_w, params, nearest, div, add,
+                                       (self.dev_offsets, self.dev_hw))
+
+    def preprocess_image(self):
+        """preprocess_image of every frame (uint8 -> /255 - 0.5, legacy bilinear to READER_H x READER_W)."""
+        return self.resize(READER_H, READER_W, None, False, 255.0, -0.5)
+
+    def preprocess_mask(self):
+        """preprocess_mask of every mask (uint8 -> /255, nearest-neighbour to READER_H x READER_W)."""
+        return self.resize(READER_H, READER_W, None, True, 255.0, 0.0)
+
+
+class RaggedLoader(object):
+    """Decodes a list of paths on a thread pool (loader(path, channels) -> uint8 [H,W,C], Pillow by default) and packs the
+    frames, whatever their sizes, with their offset / size tables into one pinned staging buffer: one non-blocking H2D copy
+    on the current stream per batch.  `slots` staging buffers are used in turn; each records an event after its copy and is
+    not written again before that event has completed (the copy of a previous batch may still be reading it)."""
+
+    def __init__(self, loader=None, num_threads=6, device="cuda", slots=2):
+        from concurrent.futures import ThreadPoolExecutor
+        self.loader = loader or _read_image
+        self.device = torch.device(device)
+        self.pool = ThreadPoolExecutor(max(1, num_threads))
+        self._slots, self._events, self._next = [None] * max(1, slots), [None] * max(1, slots), 0
+
+    def load(self, paths, channels, loader=None) -> RaggedBatch:
+        load = loader or self.loader
+        arrs = list(self.pool.map(lambda p: load(p, channels), list(paths)))
+        n = len(arrs)
+        if n == 0:
+            raise ValueError("empty batch")
+        for p, a in zip(paths, arrs):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != channels:
+                raise ValueError("%s: decoded to %s %s, expected uint8 [H,W,%d]" % (p, a.dtype, a.shape, channels))
+        hw = np.array([a.shape[:2] for a in arrs], dtype=np.int32).reshape(n, 2)
+        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * channels
+        off = np.zeros(n, np.int64)
+        off[1:] = np.cumsum(sizes)[:-1]
+        head = 16 * n  # int64 offsets [n] + int32 sizes [n,2], then the pixels
+        total = head + int(sizes.sum())
+        k = self._next
+        self._next = (k + 1) % len(self._slots)
+        if self._events[k] is not None:
+            self._events[k].synchronize()  # the copy out of this slot (batch - slots) has finished: safe to overwrite
+        if self._slots[k] is None or self._slots[k].numel() < total:
+            self._slots[k] = torch.empty(total + total // 4, dtype=torch.uint8, pin_memory=True)
+        host = self._slots[k].numpy()
+        host[:8 * n] = off.view(np.uint8)
+        host[8 * n:head] = hw.reshape(-1).view(np.uint8)
+
+        def put(i):
+            host[head + off[i]:head + off[i] + sizes[i]] = arrs[i].reshape(-1)
+        list(self.pool.map(put, range(n)))
+        dev = torch.empty(total, dtype=torch.uint8, device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        dev.copy_(self._slots[k][:total], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        self._events[k] = ev
+        return RaggedBatch(dev[head:], off, hw, channels, dev[:8 * n].view(torch.int64), dev[8 * n:head].view(torch.int32))

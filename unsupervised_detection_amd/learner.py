@@ -11,7 +11,8 @@ charbonnier_loss / preprocess_flow_batch on PyTorch-ROCm NHWC float32 tensors.
 `config` is any object with the attribute names of common_flags.py (config.FLAGS restates the defaults).
 Dataset readers are outside this path: batches come from `config.data_source`, an
 iterable of dicts {"img1","img2"[, "gt_mask","fname"]} holding reader-preprocessed tensors [B,384,640,3]
-in [-0.5,0.5]; without one, synthetic DAVIS-shaped pairs are used (there is no dataset on this machine)."""
+in [-0.5,0.5] -- data.Davis2016Reader, datasets.FBMS59Reader or datasets.SegTrackV2Reader, built by cli.py from
+--dataset / --root_dir; without one, synthetic DAVIS-shaped pairs are used when config.synthetic opts in."""
 from __future__ import annotations
 
 import math
