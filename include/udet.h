@@ -115,6 +115,48 @@ size_t udet_post_crf_workspace_bytes(int h, int w);
 int udet_post_dense_crf(const float* unary, const unsigned char* image_rgb, int h, int w, float sxy, float srgb, float compat, int iters,
                         int radius, float* q, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Visualisation and training summaries (models/utils/flow_utils.py:14-100, models/adversarial_learner.py:260-298,
+ * test_generator.py:93-117): the images and gradient histograms of a run, from buffers that already sit on the device.
+ *  - udet_flow_to_image: flow_to_image + compute_color (flow_utils.py:46-100) with the arithmetic the reference has on a float32
+ *    flow under numpy 2.x: a component with |u| > 1e7 or |v| > 1e7 zeroes both; each sample's maximum radius is float32 (sqrtf of the
+ *    float32 u*u + v*v, no FMA); sample i is divided by the RUNNING maximum over samples 0..i (the reference's maxrad lives across
+ *    its batch loop, :83-97) widened to double plus DBL_EPSILON, and everything after that division is double: rad = sqrt(u*u+v*v),
+ *    a = atan2(-v,-u)/pi, fk = (a+1)/2*54 + 1, k0 = floor(fk), k1 = k0+1 (56 -> 1), f = fk-k0, per channel
+ *    col = (1-f)*wheel[k0-1]/255 + f*wheel[k1-1]/255, col = rad <= 1 ? 1 - rad*(1-col) : col*0.75, out = floor(255*col); wheel =
+ *    make_color_wheel (:14-42).  The pixel that attains the maximum has rad within an ulp of 1: this precision mix decides its branch.
+ *    A NaN component paints the pixel black and is EXCLUDED from the maximum.  (In the reference a NaN reaches Python's
+ *    max(maxrad, nan), whose result depends on the argument order: an accident that turns every later sample of the batch black.)
+ *    mask [n,h,w,1] and stats8 (the device doubles udet_mask_stats wrote for that mask) are both NULL or both given: the mask is
+ *    then thresholded (> threshold) and complemented per sample when stats8[i][0] / (4w + 4h) >= 0.6 (disambiguate_forw_back,
+ *    general_utils.py:100-109), and a pixel inside the resulting object mask is written as (127,127,127) -- the zero of the
+ *    reference's img/255 - 0.5 image times (1 - mask) (adversarial_learner.py:269-272).  No host round trip in between.
+ *    flow [n,h,w,2] -> rgb [n,h,w,3] uint8.  Two launches: per-sample partial maxima into `workspace` (4-byte aligned,
+ *    >= udet_flow_to_image_workspace_bytes(n)), then the colouring, which takes the prefix maximum itself.
+ *  - udet_overlay_mask: test_generator.py:101-107 in one launch.  image [n,h,w,3] in [-0.5,0.5] -> postprocess_image ((x+0.5)*255 in
+ *    float32, truncated toward zero, clamped to 0..255); the disambiguated boolean mask (as above; stats8 NULL: never complemented)
+ *    -> postprocess_mask (0 / 255 in the middle channel only); cv2.addWeighted(img, 0.5, mask, 0.4, 0) in float32, rounded half to
+ *    even, saturated; cv2.resize to oh x ow, 8-bit INTER_LINEAR: fx = (float)((dx+0.5)*w/ow - 0.5), taps (floor(fx), +1) clamped at
+ *    the edges with weight 0 on the clamped side, coefficients round(weight*2048), horizontal pass in int32, vertical pass
+ *    (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2.  The four blended source pixels of an output pixel are computed on the fly.
+ *    out [n,oh,ow,3] uint8, RGB (the reference's BGR order is cv2.imwrite's convention).
+ *  - udet_grad_histogram: tf.summary.histogram (adversarial_learner.py:284-289) of every variable of a flat gradient buffer in one
+ *    call.  Segment s is g[seg_offsets[s] .. seg_offsets[s+1]) (device int64 [nseg+1], any ranges inside g).  Bucket limits are
+ *    TensorFlow's defaults (udet_histogram_limits: v = 1e-12, v *= 1.1 while v < 1e20 -- 774 values --, DBL_MAX, the negated mirror
+ *    and 0: UDET_HISTOGRAM_BUCKETS = 1551 ascending doubles, built once on the host and uploaded with every call).  A value counts
+ *    in the first limit strictly greater than it (upper_bound, compared in double); +inf and NaN, which have none, in the last.
+ *    counts [nseg][1551] uint32 (zeroed by the call); stats [nseg][5] doubles = {min, max, count, sum, sum of squares}, the sums by
+ *    a deterministic two-stage reduction.  workspace: 8-byte aligned, >= udet_grad_histogram_workspace_bytes(nseg). */
+#define UDET_HISTOGRAM_BUCKETS 1551
+size_t udet_flow_to_image_workspace_bytes(int n);
+int udet_flow_to_image(const float* flow, const float* mask, const double* stats8, float threshold, int n, int h, int w,
+                       unsigned char* rgb, void* workspace, size_t workspace_bytes, void* stream);
+int udet_overlay_mask(const float* image, const float* mask, const double* stats8, float threshold, int n, int h, int w,
+                      unsigned char* out, int oh, int ow, void* stream);
+int udet_histogram_limits(double* limits, int n); /* host memory */
+size_t udet_grad_histogram_workspace_bytes(int nseg);
+int udet_grad_histogram(const float* g, const long long* seg_offsets, int nseg, double* stats, unsigned* counts, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* tf.nn.conv2d / tf.layers.conv2d, padding='SAME', + bias + activation
  * (models/utils/convolution_utils.py:46,81-84; models/PWCNet/model_pwcnet.py:161-165,484-504,562-574).
  * upsample2x != 0 first applies tf.image.resize_nearest_neighbor(x2, align_corners=True)

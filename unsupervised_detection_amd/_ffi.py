@@ -70,6 +70,13 @@ _sig("udet_stream_wait_grads", c_i, c_p, c_i, c_p)
 _sig("udet_tune_rejected", c_i)
 _sig("udet_tune_save", c_i, ctypes.c_char_p)
 _sig("udet_tune_load", c_i, ctypes.c_char_p)
+# visualisation and training summaries (visualize.py)
+_sig("udet_flow_to_image_workspace_bytes", c_sz, c_i)
+_sig("udet_flow_to_image", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_sz, c_p)
+_sig("udet_overlay_mask", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p)
+_sig("udet_histogram_limits", c_i, c_p, c_i)
+_sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
+_sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)
 
 
 class UdetError(RuntimeError):

@@ -102,7 +102,7 @@ def main(argv=None):
         _sources(flags, "test")  # --ckpt_file is restored by the learner (every network the checkpoint holds)
         learner.setup_inference(flags, aug_test=False)
         from .evaluation import evaluate_masks
-        evaluate_masks(learner)
+        evaluate_masks(learner, save_dir=flags.test_save_dir if flags.generate_visualization else None)
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

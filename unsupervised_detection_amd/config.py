@@ -22,6 +22,9 @@ _DEFS = [
     # not a reference flag: the one-off kernel autotune of the training plan at start-up (~10 s; rank 0 tunes, the other ranks of a
     # data-parallel job load its configurations).  Untuned plans run on the built-in tile heuristics (12.3 instead of 10.9 ms per step at the benchmark shape).
     ("autotune", bool, True),
+    # not a reference flag: directory of the training summaries (visualize.SummaryWriter: scalars.jsonl, images/, histograms/ every
+    # summary_freq steps -- the reference writes TensorBoard events into checkpoint_dir); "" = off
+    ("summary_dir", str, ""),
 ]
 
 

@@ -1,0 +1,325 @@
+// Visualisation and training summaries on the GPU: what lets a person look at a run.
+//   models/utils/flow_utils.py        make_color_wheel :14-42, compute_color :46-72, flow_to_image :74-100
+//   models/adversarial_learner.py     collect_summaries :260-298 (flow images, the masked flow image, tf.summary.histogram of every
+//                                     variable's gradient)
+//   test_generator.py                 :93-117 (postprocess_image / postprocess_mask, cv2.addWeighted, cv2.resize to 384 x 640)
+// The inputs already sit in plan buffers (image, flow, mask, pred, the flat gradient buffers); these kernels turn them into the uint8
+// images and the bucket counts a writer stores, so that a summary step costs a few hundred microseconds of device time (profiles/NOTES.md) and two small copies.
+// Written for exact agreement with the reference's arithmetic, not for a roofline.  Compiled with -ffp-contract=off (Makefile): the
+// float32 radius u*u + v*v and every double expression below must round operation by operation like numpy.
+#include <float.h>
+#include <math.h>
+
+#include "common.h"
+
+namespace udet {
+
+template <typename T, typename Op>
+__device__ __forceinline__ T block_reduce256(T v, T* sm /*[4]*/, Op op) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return op(op(sm[0], sm[1]), op(sm[2], sm[3]));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// flow_to_image
+// ---------------------------------------------------------------------------------------------------------------------------------
+// make_color_wheel (:14-42) divided by 255 (compute_color :64-65 divides on every use; the quotient is the same double): six ramps
+// RY YG GC CB BM MR of 15, 6, 4, 11, 13, 6 entries, one channel at 255, one rising or falling as floor(255 i / len).  Built by the
+// compiler: the table lives in constant memory, a dynamically indexed local array would live in scratch.
+struct ColorWheel {
+  double c[55][3];
+};
+constexpr ColorWheel make_color_wheel() {
+  ColorWheel w{};
+  const int len[6] = {15, 6, 4, 11, 13, 6}, full[6] = {0, 1, 1, 2, 2, 0}, ramp[6] = {1, 0, 2, 1, 0, 2};
+  int col = 0;
+  for (int s = 0; s < 6; ++s)
+    for (int i = 0; i < len[s]; ++i, ++col) {
+      const int r = 255 * i / len[s];
+      for (int c = 0; c < 3; ++c) w.c[col][c] = 0.0;
+      w.c[col][full[s]] = 255.0 / 255.0;
+      w.c[col][ramp[s]] = (double)((s & 1) ? 255 - r : r) / 255.0;
+    }
+  return w;
+}
+__constant__ ColorWheel c_wheel = make_color_wheel();
+
+#define FI_SPLIT 16  // workgroups (and partial maxima) per sample
+// one flow sample as flow_to_image sees it (:85-89): a component beyond 1e7 zeroes both
+__device__ __forceinline__ float2 flow_known(const float* __restrict__ flow, long i) {
+  float2 v = *reinterpret_cast<const float2*>(flow + 2 * i);
+  if (fabsf(v.x) > 1e7f || fabsf(v.y) > 1e7f) v = make_float2(0.f, 0.f);
+  return v;
+}
+// stage 1: part[n][FI_SPLIT] = max over the workgroup's pixels of the float32 radius sqrtf(u*u + v*v), -1 (the reference's initial
+// maxrad, :83) when it saw none.  sqrtf is correctly rounded and monotonic: the maximum of the roots is the root of the maximum.
+// A NaN pixel is left out (see udet.h).
+__global__ __launch_bounds__(256) void flow_maxrad_kernel(const float* __restrict__ flow, long HW, float* __restrict__ part) {
+  __shared__ float sm[4];
+  const int n = blockIdx.y;
+  float m = -1.f;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < HW; p += (long)FI_SPLIT * 256) {
+    const float2 v = flow_known(flow, n * HW + p);
+    const float r2 = v.x * v.x + v.y * v.y;
+    if (!isnan(r2)) m = fmaxf(m, r2);
+  }
+  m = block_reduce256(m, sm, [](float a, float b) { return fmaxf(a, b); });
+  if (threadIdx.x == 0) part[n * FI_SPLIT + blockIdx.x] = m < 0.f ? -1.f : sqrtf(m);
+}
+// stage 2: compute_color (:46-72) of sample n divided by the running maximum over samples 0..n (:95-97), in double from the
+// division on; optionally the object mask painted (127,127,127)
+__global__ __launch_bounds__(256) void flow_colour_kernel(const float* __restrict__ flow, const float* __restrict__ mask,
+                                                          const double* __restrict__ stats8, float threshold, int H, int W,
+                                                          const float* __restrict__ part, unsigned char* __restrict__ rgb) {
+  __shared__ float sm[4];
+  const int n = blockIdx.y;
+  const long HW = (long)H * W;
+  float m = -1.f;
+  for (int i = threadIdx.x; i < (n + 1) * FI_SPLIT; i += 256) m = fmaxf(m, part[i]);
+  m = block_reduce256(m, sm, [](float a, float b) { return fmaxf(a, b); });
+  const double den = (double)m + DBL_EPSILON;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  unsigned char* o = rgb + (n * HW + p) * 3;
+  if (mask) {
+    // disambiguate_forw_back (general_utils.py:100-109): the mask is complemented when it covers the image borders
+    const bool flip = stats8[(long)n * 8] / (4.0 * W + 4.0 * H) >= 0.6;
+    if ((mask[n * HW + p] > threshold) != flip) {
+      o[0] = o[1] = o[2] = 127;
+      return;
+    }
+  }
+  const float2 v = flow_known(flow, n * HW + p);
+  if (isnan(v.x) || isnan(v.y)) {
+    o[0] = o[1] = o[2] = 0;
+    return;
+  }
+  const double u = (double)v.x / den, w = (double)v.y / den;
+  const double rad = sqrt(u * u + w * w);
+  const double a = atan2(-w, -u) / 3.141592653589793;
+  const double fk = (a + 1.0) / 2.0 * 54.0 + 1.0;
+  const int k0 = (int)floor(fk);
+  const int k1 = k0 + 1 == 56 ? 1 : k0 + 1;
+  const double f = fk - (double)k0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    double col = (1.0 - f) * c_wheel.c[k0 - 1][c] + f * c_wheel.c[k1 - 1][c];
+    col = rad <= 1.0 ? 1.0 - rad * (1.0 - col) : col * 0.75;
+    o[c] = (unsigned char)(int)floor(255.0 * col);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// overlay_mask
+// ---------------------------------------------------------------------------------------------------------------------------------
+// OpenCV's 8-bit INTER_LINEAR coordinates along one axis: f = (d + 0.5) * in / out - 0.5 in float, taps (s, s + 1) clamped into the
+// image with weight 0 on the clamped side, coefficients round(w * 2048)
+__device__ __forceinline__ void linear_taps(int d, double scale, int in, int& i0, int& i1, int& c0, int& c1) {
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  if (s < 0) { s = 0; f = 0.f; }
+  if (s >= in - 1) { s = in - 1; f = 0.f; }
+  i0 = s;
+  i1 = min(s + 1, in - 1);
+  c0 = (int)rintf((1.f - f) * 2048.f);
+  c1 = (int)rintf(f * 2048.f);
+}
+// postprocess_image of one value, postprocess_mask's byte m of that channel, cv2.addWeighted(img, 0.5, mask, 0.4, 0)
+__device__ __forceinline__ int overlay_blend(float x, int m) {
+  const float t = fminf(fmaxf((x + 0.5f) * 255.f, 0.f), 255.f);
+  const float b = (float)(int)t * 0.5f + (float)m * 0.4f;
+  const int r = (int)rintf(b);
+  return r < 0 ? 0 : (r > 255 ? 255 : r);
+}
+__global__ __launch_bounds__(256) void overlay_mask_kernel(const float* __restrict__ image, const float* __restrict__ mask,
+                                                           const double* __restrict__ stats8, float threshold, int H, int W,
+                                                           unsigned char* __restrict__ out, int OH, int OW, double sy, double sx) {
+  const int n = blockIdx.y;
+  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (long)OH * OW) return;
+  const int dy = (int)(q / OW), dx = (int)(q - (long)dy * OW);
+  const bool flip = stats8 && stats8[(long)n * 8] / (4.0 * W + 4.0 * H) >= 0.6;
+  int y0, y1, b0, b1, x0, x1, a0, a1;
+  linear_taps(dy, sy, H, y0, y1, b0, b1);
+  linear_taps(dx, sx, W, x0, x1, a0, a1);
+  const long base = (long)n * H * W;
+  const long p00 = base + (long)y0 * W + x0, p01 = base + (long)y0 * W + x1, p10 = base + (long)y1 * W + x0, p11 = base + (long)y1 * W + x1;
+  const int m00 = ((mask[p00] > threshold) != flip) ? 255 : 0, m01 = ((mask[p01] > threshold) != flip) ? 255 : 0;
+  const int m10 = ((mask[p10] > threshold) != flip) ? 255 : 0, m11 = ((mask[p11] > threshold) != flip) ? 255 : 0;
+  unsigned char* o = out + ((long)n * OH * OW + q) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int g = c == 1;  // the mask is painted into the middle channel only
+    const int S0 = overlay_blend(image[p00 * 3 + c], g * m00) * a0 + overlay_blend(image[p01 * 3 + c], g * m01) * a1;
+    const int S1 = overlay_blend(image[p10 * 3 + c], g * m10) * a0 + overlay_blend(image[p11 * 3 + c], g * m11) * a1;
+    const int r = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+    o[c] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// grad_histogram
+// ---------------------------------------------------------------------------------------------------------------------------------
+#define GH_BUCKETS UDET_HISTOGRAM_BUCKETS
+#define GH_SPLIT 128     // a segment is split over at most this many workgroups ...
+#define GH_MIN_CHUNK 2048  // ... of at least this many elements each
+__device__ __forceinline__ int gh_active(long len) {
+  const long a = (len + GH_MIN_CHUNK - 1) / GH_MIN_CHUNK;
+  return a < 1 ? 1 : (a > GH_SPLIT ? GH_SPLIT : (int)a);
+}
+// stage 1: workgroup (s, y) buckets its slice of segment s: limits in LDS, one binary search (upper_bound, compared in double) per
+// element, counts privatised in LDS and flushed with integer atomics; min / max / sum / sum of squares of the slice go to
+// part[s][y][4] (fixed order inside the workgroup: the sums do not depend on scheduling).
+__global__ __launch_bounds__(256) void grad_hist_kernel(const float* __restrict__ g, const long long* __restrict__ seg_offsets,
+                                                        const double* __restrict__ limits, unsigned* __restrict__ counts,
+                                                        double* __restrict__ part) {
+  __shared__ double lim[GH_BUCKETS];
+  __shared__ unsigned cnt[GH_BUCKETS];
+  __shared__ double sm[4];
+  const int s = blockIdx.x, y = blockIdx.y;
+  const long off = seg_offsets[s], len = seg_offsets[s + 1] - off;
+  const int active = gh_active(len);
+  if (y >= active) return;
+  for (int i = threadIdx.x; i < GH_BUCKETS; i += 256) {
+    lim[i] = limits[i];
+    cnt[i] = 0u;
+  }
+  __syncthreads();
+  const long b = len * y / active, e = len * (y + 1) / active;
+  double mn = INFINITY, mx = -INFINITY, sum = 0.0, sq = 0.0;
+  for (long i = b + threadIdx.x; i < e; i += 256) {
+    const double x = (double)g[off + i];
+    int lo = 0, hi = GH_BUCKETS;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (lim[mid] > x) hi = mid; else lo = mid + 1;
+    }
+    atomicAdd(&cnt[lo < GH_BUCKETS ? lo : GH_BUCKETS - 1], 1u);  // +inf and NaN have no limit above them: last bucket
+    mn = fmin(mn, x);
+    mx = fmax(mx, x);
+    sum += x;
+    sq += x * x;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < GH_BUCKETS; i += 256)
+    if (cnt[i]) atomicAdd(&counts[(long)s * GH_BUCKETS + i], cnt[i]);
+  mn = block_reduce256(mn, sm, [](double p, double q) { return fmin(p, q); });
+  mx = block_reduce256(mx, sm, [](double p, double q) { return fmax(p, q); });
+  sum = block_reduce256(sum, sm, [](double p, double q) { return p + q; });
+  sq = block_reduce256(sq, sm, [](double p, double q) { return p + q; });
+  if (threadIdx.x == 0) {
+    double* o = part + ((long)s * GH_SPLIT + y) * 4;
+    o[0] = mn; o[1] = mx; o[2] = sum; o[3] = sq;
+  }
+}
+// stage 2: stats[s] = {min, max, count, sum, sum of squares} from the segment's partials, in order
+__global__ __launch_bounds__(256) void grad_hist_finish_kernel(const long long* __restrict__ seg_offsets, int nseg,
+                                                               const double* __restrict__ part, double* __restrict__ stats) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= nseg) return;
+  const long len = seg_offsets[s + 1] - seg_offsets[s];
+  const int active = gh_active(len);
+  double mn = INFINITY, mx = -INFINITY, sum = 0.0, sq = 0.0;
+  for (int y = 0; y < active; ++y) {
+    const double* p = part + ((long)s * GH_SPLIT + y) * 4;
+    mn = fmin(mn, p[0]);
+    mx = fmax(mx, p[1]);
+    sum += p[2];
+    sq += p[3];
+  }
+  double* o = stats + (long)s * 5;
+  o[0] = mn; o[1] = mx; o[2] = (double)len; o[3] = sum; o[4] = sq;
+}
+
+// TensorFlow's default histogram bucket limits (tensorflow/core/lib/histogram/histogram.cc, InitDefaultBucketsInner), built once
+static const double* histogram_limits() {
+  static const struct Table {
+    double v[GH_BUCKETS];
+    Table() {
+      double pos[GH_BUCKETS / 2];
+      int n = 0;
+      for (double x = 1e-12; x < 1e20; x *= 1.1) pos[n++] = x;  // 774 values
+      pos[n++] = DBL_MAX;
+      for (int i = 0; i < n; ++i) {
+        v[i] = -pos[n - 1 - i];
+        v[n + 1 + i] = pos[i];
+      }
+      v[n] = 0.0;
+    }
+  } t;
+  return t.v;
+}
+static const size_t kLimitBytes = (GH_BUCKETS * sizeof(double) + 255) / 256 * 256;
+
+}  // namespace udet
+
+using namespace udet;
+
+extern "C" {
+
+size_t udet_flow_to_image_workspace_bytes(int n) { return n < 1 ? 0 : (size_t)n * FI_SPLIT * sizeof(float); }
+int udet_flow_to_image(const float* flow, const float* mask, const double* stats8, float threshold, int n, int h, int w,
+                       unsigned char* rgb, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!flow || !rgb || n < 1 || n > 65535 || h < 1 || w < 1 || (mask != nullptr) != (stats8 != nullptr)) {
+    set_error("flow_to_image: bad argument (mask and stats8 go together)");
+    return UDET_ERR_ARG;
+  }
+  if (!workspace || workspace_bytes < udet_flow_to_image_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 3)) {
+    set_error("flow_to_image: workspace needs %zu bytes, 4-byte aligned", udet_flow_to_image_workspace_bytes(n));
+    return UDET_ERR_ARG;
+  }
+  const long HW = (long)h * w;
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL(flow_maxrad_kernel, dim3(FI_SPLIT, n), dim3(256), 0, (hipStream_t)stream, flow, HW, part);
+  hipLaunchKernelGGL(flow_colour_kernel, dim3((unsigned)((HW + 255) / 256), n), dim3(256), 0, (hipStream_t)stream, flow, mask, stats8,
+                     threshold, h, w, part, rgb);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+int udet_overlay_mask(const float* image, const float* mask, const double* stats8, float threshold, int n, int h, int w,
+                      unsigned char* out, int oh, int ow, void* stream) {
+  if (!image || !mask || !out || n < 1 || n > 65535 || h < 1 || w < 1 || oh < 1 || ow < 1) {
+    set_error("overlay_mask: bad argument");
+    return UDET_ERR_ARG;
+  }
+  const long q = (long)oh * ow;
+  hipLaunchKernelGGL(overlay_mask_kernel, dim3((unsigned)((q + 255) / 256), n), dim3(256), 0, (hipStream_t)stream, image, mask, stats8,
+                     threshold, h, w, out, oh, ow, (double)h / oh, (double)w / ow);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+int udet_histogram_limits(double* limits, int n) {
+  if (!limits || n != GH_BUCKETS) { set_error("histogram_limits: the table has %d entries", GH_BUCKETS); return UDET_ERR_ARG; }
+  const double* t = histogram_limits();
+  for (int i = 0; i < n; ++i) limits[i] = t[i];
+  return UDET_OK;
+}
+size_t udet_grad_histogram_workspace_bytes(int nseg) {
+  return nseg < 1 ? 0 : kLimitBytes + (size_t)nseg * GH_SPLIT * 4 * sizeof(double);
+}
+int udet_grad_histogram(const float* g, const long long* seg_offsets, int nseg, double* stats, unsigned* counts, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!g || !seg_offsets || !stats || !counts || nseg < 1 || nseg > 65535) { set_error("grad_histogram: bad argument"); return UDET_ERR_ARG; }
+  if (!workspace || workspace_bytes < udet_grad_histogram_workspace_bytes(nseg) || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
+    set_error("grad_histogram: workspace needs %zu bytes, 8-byte aligned", udet_grad_histogram_workspace_bytes(nseg));
+    return UDET_ERR_ARG;
+  }
+  double* limits = (double*)workspace;
+  double* part = (double*)((char*)workspace + kLimitBytes);
+  UDET_HIP(hipMemcpyAsync(limits, histogram_limits(), GH_BUCKETS * sizeof(double), hipMemcpyHostToDevice, s));
+  UDET_HIP(hipMemsetAsync(counts, 0, (size_t)nseg * GH_BUCKETS * sizeof(unsigned), s));
+  hipLaunchKernelGGL(grad_hist_kernel, dim3(nseg, GH_SPLIT), dim3(256), 0, s, g, seg_offsets, limits, counts, part);
+  hipLaunchKernelGGL(grad_hist_finish_kernel, dim3((nseg + 255) / 256), dim3(256), 0, s, seg_offsets, nseg, part, stats);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+}  // extern "C"

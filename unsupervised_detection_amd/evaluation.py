@@ -12,6 +12,7 @@ The batch functions take device tensors [B,H,W,1]; one kernel pass produces ever
 the MAE need (exact counts, double accumulation), the few scalar operations that remain run on the host."""
 from __future__ import annotations
 
+import os
 
 import numpy as np
 import torch
@@ -106,9 +107,27 @@ def compute_mae(gt_mask, pred_mask_f) -> float:
     return float(np.mean(np.abs(np.asarray(gt_mask, dtype=np.float64) - np.asarray(pred_mask_f, dtype=np.float64))))
 
 
-def evaluate_masks(learner, n_steps=None, verbose=True):
+def _save_frame(d, k, frame_u8, inf, b, flipped):
+    """test_generator.py:95-117 for one frame: the overlay PNG and the .mat the offline tools read."""
+    import scipy.io as sio
+    from PIL import Image
+    from .visualize import postprocess_image
+    os.makedirs(d, exist_ok=True)
+    Image.fromarray(np.ascontiguousarray(frame_u8)).save(os.path.join(d, "frame_{:08d}.png".format(k)))
+    pred = np.asarray(inf["gen_masks"][b]) > 0.1
+    gt = inf["gt_masks"]
+    sio.savemat(os.path.join(d, "result_{}.mat".format(k)),
+                {"flow": inf["gt_flow"][b], "img1": postprocess_image(inf["input_image"][b]),
+                 "pred_mask": np.logical_not(pred) if flipped else pred,
+                 "gt_mask": np.zeros_like(pred, dtype=np.float32) if gt is None else gt[b]})
+
+
+def evaluate_masks(learner, n_steps=None, verbose=True, save_dir=None):
     """The loop of test_generator.py:_test_masks (:43-130) over learner.inference(): per-category IoU / MAE lists and
-    the three reported averages.  `learner` is an AdversarialLearner after setup_inference(config, aug_test=False)."""
+    the three reported averages.  `learner` is an AdversarialLearner after setup_inference(config, aug_test=False).
+    With `save_dir` (--generate_visualization, :93-117) every frame also leaves <save_dir>/<category>/frame_%08d.png -- the
+    image blended with the disambiguated mask at 384 x 640 (visualize.overlay_mask) -- and result_<k>.mat with flow, img1
+    (uint8 RGB), pred_mask (the disambiguated mask) and gt_mask; k counts the category's frames from 1."""
     cat_iou, cat_mae = {}, {}
     batch = getattr(learner.config, "batch_size", 1)
     if n_steps is None:
@@ -124,7 +143,11 @@ def evaluate_masks(learner, n_steps=None, verbose=True):
         pm = torch.as_tensor(np.ascontiguousarray(inf["gen_masks"], dtype=np.float32)).cuda()
         gm = torch.zeros_like(pm) if inf["gt_masks"] is None else \
             torch.as_tensor(np.ascontiguousarray(inf["gt_masks"], dtype=np.float32)).cuda()  # (synthetic data: no annotation)
-        iou, mae, _ = evaluate_batch(gm, pm)
+        iou, mae, flip = evaluate_batch(gm, pm)
+        if save_dir:
+            from .visualize import overlay_mask
+            img_dev = torch.as_tensor(np.ascontiguousarray(inf["input_image"], dtype=np.float32)).cuda()
+            frames_u8 = overlay_mask(img_dev, pm).cpu().numpy()
         for b in range(pm.shape[0]):
             name = inf["img_fname"][b]
             name = name.decode("utf-8") if isinstance(name, (bytes, bytearray)) else str(name)
@@ -133,6 +156,8 @@ def evaluate_masks(learner, n_steps=None, verbose=True):
             cat_iou.setdefault(category, []).append(float(iou[b]))
             cat_mae.setdefault(category, []).append(float(mae[b]))
             frames += 1
+            if save_dir:
+                _save_frame(os.path.join(save_dir, category), len(cat_iou[category]), frames_u8[b], inf, b, bool(flip[b]))
     tot_iou = sum(sum(v) for v in cat_iou.values())
     tot_mae = sum(sum(v) for v in cat_mae.values())
     per_cat = [float(np.mean(v)) for v in cat_iou.values()]

@@ -173,7 +173,10 @@ class AdversarialLearner(object):
 
     def train(self, config):
         """High level train function (adversarial_learner.py:312-420): alternates `iters_rec` recover steps and
-        `iters_gen` generator steps (step % (iters_rec+iters_gen) < iters_rec -> recover), each on a new batch."""
+        `iters_gen` generator steps (step % (iters_rec+iters_gen) < iters_rec -> recover), each on a new batch.
+        With config.summary_dir, every summary_freq steps the step's losses, images and the gradient histograms of the network it
+        trained are written there (visualize.write_training_summary; the reference logs both networks' gradients at such a step,
+        which would take a second backward pass).  The summary only reads the step's buffers behind the step."""
         self.config = config
         B = config.batch_size
         self.engine = Engine(_engine_config(config, B))
@@ -201,6 +204,10 @@ class AdversarialLearner(object):
                               "with config.synthetic / --synthetic")
             source = _SyntheticSource(B, max_steps)
         it = iter(source)
+        writer = None
+        if getattr(config, "summary_dir", "") and not (world > 1 and dist.get_rank() != 0):  # replicas are identical: rank 0 writes
+            from .visualize import SummaryWriter, write_training_summary
+            writer = SummaryWriter(config.summary_dir)
         # cross-step pipelining (trainer.train_step): one batch of look-ahead, so that the frozen PWC-Net's flow of the
         # next batch is computed beside this step's backward pass
         nxt = next(it, None)
@@ -221,6 +228,8 @@ class AdversarialLearner(object):
                 train_step_ = step - (train_epoch - 1) * self.train_steps_per_epoch
                 print("Epoch: [%2d] [%5d/%5d] time: %4.4f/it loss_generator: %4.4f loss_recover %4.4f"
                       % (train_epoch, train_step_, self.train_steps_per_epoch, time.time() - start_time, L["generator"], L["recover"]))
+                if writer is not None:  # collect_summaries (:260-291): losses, images, gradient histograms -- visualize.py
+                    write_training_summary(writer, step, self.engine, self.state, which, batch["img2"], L)
             if step % self.train_steps_per_epoch == 0:
                 train_epoch = int(step / self.train_steps_per_epoch)
                 self.epoch_end_callback(train_epoch)

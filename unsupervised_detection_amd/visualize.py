@@ -1,0 +1,218 @@
+"""Flow / mask visualisation and training summaries, computed on the device (csrc/visualize.hip):
+
+  flow_to_image(flow, mask=None, threshold=0.1)    models/utils/flow_utils.py:46-100 (+ the masked flow image of
+                                                   models/adversarial_learner.py:269-272 when `mask` is given)
+  overlay_mask(image, mask, out_hw=(384, 640))     test_generator.py:101-107 (postprocess_image / postprocess_mask, cv2.addWeighted,
+                                                   cv2.resize)
+  grad_histograms(g, net) / bucket_limits()        tf.summary.histogram of every variable's gradient (adversarial_learner.py:284-289)
+  postprocess_image / postprocess_mask             models/utils/general_utils.py:23-51 on host arrays (RGB order is kept)
+  SummaryWriter(dir)                               the step_sum summaries of collect_summaries (:260-291) as plain files:
+      scalars.jsonl                                one JSON object per call: {"step": s, <the eight losses{}>}
+      images/step_%08d_<tag>.png                   input_image, next_image, PWC_Flow, masked_flow, Rec_flow, Rec_flow_compl
+      histograms/step_%08d_<net>.npz               names [V], stats [V,5] = (min, max, count, sum, sum of squares), counts [V,1551],
+                                                   limits [1551]
+There is no TensorBoard event-file writer: the JSON-lines / PNG / npz layout is the interface.
+
+The device functions take and return device tensors and do not synchronise; the images and bucket counts come from the kernels of
+libudet.so (no PyTorch fallback), torch only holds the memory."""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import evaluation as _ev  # (declares udet_mask_stats)
+from . import weights as W
+from ._ffi import check, lib
+
+N_BUCKETS = 1551  # UDET_HISTOGRAM_BUCKETS
+DES_HW = (384, 640)  # test_generator.py:14-15
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _f32(t, name, last):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 4
+            and t.shape[-1] == last):
+        raise ValueError("%s must be a contiguous float32 CUDA(HIP) tensor [N,H,W,%d]" % (name, last))
+    return t
+
+
+def _mask_stats_device(mask, threshold):
+    """udet_mask_stats of `mask` against an empty annotation, left on the device: [N,8] float64 (column 0 is the border sum)."""
+    n, h, w, _ = mask.shape
+    st = torch.empty((n, 8), dtype=torch.float64, device=mask.device)
+    check(lib.udet_mask_stats(mask.data_ptr(), torch.zeros_like(mask).data_ptr(), n, h, w, threshold, 0.0, st.data_ptr(), _stream()))
+    return st
+
+
+def flow_to_image(flow: torch.Tensor, mask: torch.Tensor = None, threshold: float = 0.1) -> torch.Tensor:
+    """Colour-wheel image of a flow batch [N,H,W,2] -> uint8 device tensor [N,H,W,3] (flow_to_image of the reference: sample i is
+    normalised by the largest radius of samples 0..i).  With `mask` [N,H,W,1] the pixels of the disambiguated object mask
+    (mask > threshold, complemented per sample when it hugs the image border) are painted (127,127,127): the reference's
+    "masked_flow" summary.  The border statistics go from udet_mask_stats to the colouring kernel on the device."""
+    _f32(flow, "flow", 2)
+    n, h, w, _ = flow.shape
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=flow.device)
+    ws = torch.empty(int(lib.udet_flow_to_image_workspace_bytes(n)), dtype=torch.uint8, device=flow.device)
+    mp = sp = None
+    if mask is not None:
+        _f32(mask, "mask", 1)
+        if tuple(mask.shape[:3]) != (n, h, w):
+            raise ValueError("mask must be [N,H,W,1] like the flow")
+        st = _mask_stats_device(mask, threshold)
+        mp, sp = mask.data_ptr(), st.data_ptr()
+    check(lib.udet_flow_to_image(flow.data_ptr(), mp, sp, threshold, n, h, w, rgb.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+    return rgb
+
+
+def overlay_mask(image: torch.Tensor, mask: torch.Tensor, out_hw=DES_HW, threshold: float = 0.1) -> torch.Tensor:
+    """The frame the reference's test script saves (test_generator.py:101-107): image [N,H,W,3] in [-0.5,0.5] un-normalised to 8 bit,
+    blended 0.5 / 0.4 with the disambiguated mask [N,H,W,1] in the green channel, resized to out_hw with OpenCV's 8-bit bilinear
+    rule -> uint8 device tensor [N,oh,ow,3], RGB."""
+    _f32(image, "image", 3)
+    _f32(mask, "mask", 1)
+    n, h, w, _ = image.shape
+    if tuple(mask.shape[:3]) != (n, h, w):
+        raise ValueError("mask must be [N,H,W,1] like the image")
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    st = _mask_stats_device(mask, threshold)
+    out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=image.device)
+    check(lib.udet_overlay_mask(image.data_ptr(), mask.data_ptr(), st.data_ptr(), threshold, n, h, w, out.data_ptr(), oh, ow, _stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------- histograms ----
+def bucket_limits() -> np.ndarray:
+    """TensorFlow's default histogram bucket limits, as the library builds them: 1551 ascending float64."""
+    out = np.empty(N_BUCKETS, np.float64)
+    check(lib.udet_histogram_limits(out.ctypes.data, N_BUCKETS))
+    return out
+
+
+def segment_histograms(g: torch.Tensor, seg_offsets):
+    """udet_grad_histogram over the segments [seg_offsets[s], seg_offsets[s+1]) of the flat float32 device buffer g.  Returns host
+    arrays (stats [S,5] float64 = min, max, count, sum, sum of squares; counts [S,1551] uint32), fetched in ONE device-to-host copy.
+    seg_offsets: a sequence of S+1 integers or a device int64 tensor made by `device_offsets` (then it is not validated again)."""
+    if not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 1):
+        raise ValueError("g must be a flat contiguous float32 CUDA(HIP) tensor")
+    off = seg_offsets if isinstance(seg_offsets, torch.Tensor) else device_offsets(seg_offsets, g.numel(), g.device)
+    nseg = off.numel() - 1
+    nstat = nseg * 5 * 8
+    out = torch.empty(nstat + nseg * N_BUCKETS * 4, dtype=torch.uint8, device=g.device)  # stats, then counts: one copy
+    ws = torch.empty(int(lib.udet_grad_histogram_workspace_bytes(nseg)), dtype=torch.uint8, device=g.device)
+    check(lib.udet_grad_histogram(g.data_ptr(), off.data_ptr(), nseg, out.data_ptr(), out.data_ptr() + nstat, ws.data_ptr(),
+                                  ws.numel(), _stream()))
+    host = out.cpu().numpy()
+    return host[:nstat].view(np.float64).reshape(nseg, 5), host[nstat:].view(np.uint32).reshape(nseg, N_BUCKETS)
+
+
+def device_offsets(seg_offsets, total, device="cuda") -> torch.Tensor:
+    """Validated segment table on the device: S+1 offsets, non-decreasing pairwise ranges inside [0, total]."""
+    off = np.asarray(seg_offsets, dtype=np.int64).reshape(-1)
+    if off.size < 2 or off.min() < 0 or off.max() > total or np.any(off[1:] < off[:-1]):
+        raise ValueError("seg_offsets must be S+1 non-decreasing offsets inside the buffer")
+    return torch.from_numpy(off).to(device)
+
+
+_net_tables = {}
+
+
+def _net_table(net, device):
+    """(variable names, device offsets) of a network's flat buffer: variables are contiguous in TF creation order."""
+    key = (net, str(device))
+    if key not in _net_tables:
+        tab = W.param_table(net)
+        offs = [o for _, _, o in tab] + [W.param_total(net)]
+        _net_tables[key] = ([n for n, _, _ in tab], device_offsets(offs, W.param_total(net), device))
+    return _net_tables[key]
+
+
+def grad_histograms(g: torch.Tensor, net: int):
+    """{variable name: (stats [5], counts [1551])} of a network's flat gradient buffer (weights.param_table(net) gives the segments)."""
+    if g.numel() != W.param_total(net):
+        raise ValueError("g has %d elements, network %d has %d" % (g.numel(), net, W.param_total(net)))
+    names, off = _net_table(net, g.device)
+    stats, counts = segment_histograms(g, off)
+    return {n: (stats[i], counts[i]) for i, n in enumerate(names)}
+
+
+# ------------------------------------------------------------------------------------------------ host post-processing ----
+def postprocess_image(image) -> np.ndarray:
+    """general_utils.py:23-35: [H,W,3] in [-0.5,0.5] -> uint8.  RGB order is kept (the reference converts to BGR for cv2.imwrite)."""
+    return np.asarray(np.clip((np.asarray(image, np.float32) + np.float32(0.5)) * np.float32(255), 0, 255), np.uint8)
+
+
+def postprocess_mask(mask) -> np.ndarray:
+    """general_utils.py:37-51: [H,W,1] mask in [0,1] (or boolean) -> uint8 [H,W,3] with the mask in the middle channel."""
+    un = np.asarray(np.asarray(mask, np.float64) * 255.0, np.uint8)
+    tile = np.zeros_like(un, dtype=np.uint8)
+    return np.concatenate((tile, un, tile), axis=-1)
+
+
+# -------------------------------------------------------------------------------------------------------------- writer ----
+class SummaryWriter(object):
+    """Plain-file summaries under `dir` (layout in the module docstring).  Takes host arrays; nothing here touches the device."""
+
+    def __init__(self, dir):
+        self.dir = dir
+        os.makedirs(os.path.join(dir, "images"), exist_ok=True)
+        os.makedirs(os.path.join(dir, "histograms"), exist_ok=True)
+
+    def add_scalars(self, step, losses):
+        rec = {"step": int(step)}
+        rec.update({k: float(v) for k, v in losses.items()})
+        with open(os.path.join(self.dir, "scalars.jsonl"), "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+    def add_image(self, step, tag, image_u8):
+        from PIL import Image
+        a = np.ascontiguousarray(image_u8)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("image must be uint8 [H,W,3]")
+        path = os.path.join(self.dir, "images", "step_%08d_%s.png" % (step, tag))
+        Image.fromarray(a).save(path)
+        return path
+
+    def add_histograms(self, step, net_name, names, stats, counts):
+        path = os.path.join(self.dir, "histograms", "step_%08d_%s.npz" % (step, net_name))
+        np.savez_compressed(path, names=np.asarray(list(names)), stats=np.asarray(stats, np.float64),
+                            counts=np.asarray(counts, np.uint32), limits=bucket_limits())
+        return path
+
+
+IMAGE_TAGS = ("input_image", "next_image", "PWC_Flow", "masked_flow", "Rec_flow", "Rec_flow_compl")
+
+
+def write_training_summary(writer: SummaryWriter, step, engine, state, which, img2, losses=None):
+    """One summary step of AdversarialLearner.train: the eight losses, the six images of collect_summaries for sample 0
+    (max_outputs=1) and the gradient histograms of the network this step trained, read from its flat gradient buffer after
+    udet_apply (which left the clipped gradient -- what the reference logs -- there).
+
+    The reference evaluates BOTH networks' gradients at a summary step; that would need a second backward pass, so only the
+    trained network's histograms are written here.  Everything is enqueued on the caller's stream behind the step and only reads
+    plan buffers that stay untouched until the next step consumes its prefetch; two device-to-host copies are added."""
+    from . import data as _data
+    from .engine import GEN
+    e = engine
+    B = e.cfg.batch_size
+    image, flow, mask, pred = (e.buffer(k) for k in ("image", "flow", "mask", "pred"))
+    h, w = image.shape[1], image.shape[2]
+    to_u8 = lambda x: ((x + 0.5) * 255.0).clamp_(0.0, 255.0).to(torch.uint8)  # postprocess_image
+    nxt = _data.crop_flip_resize(img2[:1].contiguous(), h, w, None, False)  # the graph's resize of image_2_batch (:87-90)
+    flows = torch.cat([flow[:1], pred[:1], pred[B:B + 1]], 0).contiguous()
+    # each flow image is a call of its own in the reference: every one is normalised by its own maximum
+    pics = torch.cat([to_u8(image[:1]), to_u8(nxt), flow_to_image(flows[0:1]), flow_to_image(flows[0:1], mask[:1].contiguous()),
+                      flow_to_image(flows[1:2]), flow_to_image(flows[2:3])], 0).cpu().numpy()  # copy 1
+    net = W.NET_GEN if which & GEN else W.NET_REC
+    g = state.g_gen if which & GEN else state.g_rec
+    names, off = _net_table(net, g.device)
+    stats, counts = segment_histograms(g, off)  # copy 2
+    writer.add_scalars(step, losses if losses is not None else e.losses())
+    for tag, pic in zip(IMAGE_TAGS, pics):
+        writer.add_image(step, tag, pic)
+    writer.add_histograms(step, "generator" if net == W.NET_GEN else "recover", names, stats, counts)
