@@ -9,8 +9,9 @@ extern "C" {
 /* force (bm, bn, split-K) for every convolution launch (bm bit 16: non-specialised kernel, bit 17: LDS-DMA staging,
  * bit 18: tile-resident kernel with bm & 0xffff = tile height, bit 19: self-staging LDS-DMA kernel, bit 20: split-K summed by a
  * second launch, bit 21: split-K summed by the last-arriving workgroup, bit 22 / 23: LDS-DMA kernel with a 3 / 4 stage
- * ring, bit 24: the direct kernels for 2-channel inputs / outputs where the launch is eligible); (0,0,-1) restores.  A forced family a launch is not
- * eligible for falls back to the built-in choice.  Process-global state: never call it from product code. */
+ * ring, bit 24: the direct kernels for 2-channel inputs / outputs where the launch is eligible, bit 25: the Winograd F(2x2,3x3) family with
+ * bm & 0xffff = variant; ks + 256 r: tail split for r workgroup slots per CU); (0,0,-1) restores.  A forced family a launch is not eligible
+ * for, or a tile that is not instantiated, falls back to the built-in choice.  Process-global state: never call it from product code. */
 void udet_debug_force_conv(int bm, int bn, int ks);
 /* fp16 multiplication (fp32 accumulation) in the single-operator convolution entry points; plans take it from
  * udet_config.conv_fp16.  Process-global state: tests only. */
@@ -27,7 +28,7 @@ int udet_debug_last_wgrad(void);
  * level whose source has at least `v` pixels (batch included); v < 0 restores the default of 8192.  Tests use 0 on small plans. */
 void udet_debug_upb_min_pixels(long v);
 void udet_debug_set_tuning(int on);
-/* pair launches (two convolutions of the same geometry in ONE launch: the recover net's two encoders, csrc/conv_igemm.hip launch_conv_pair):
+/* pair launches (two convolutions of the same geometry in ONE launch: the recover net's two encoders, csrc/conv_select.hip launch_conv_pair):
  * on = 1 pairs every compatible couple whatever the tuner thinks, 0 never pairs, -1 restores (tuned / heuristic choice);
  * udet_debug_last_pair: 1 when the most recent pair call went out as one launch */
 void udet_debug_force_pair(int on);
@@ -42,7 +43,9 @@ int udet_debug_conv2d_pair(const float* xa, const float* xb, const float* wa, co
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */
 /* what the most recent convolution launch actually ran: family (0 plain, 1 wave-specialised, 2 LDS-DMA, 3 tile-resident,
- * 6 self-staging LDS-DMA, 7 / 8 direct kernel for two input / two output channels) | tile rows << 8 | split count << 20 | folded split-K << 28 */
+ * 4 / 5 LDS-DMA with a 3 / 4 stage ring, 6 self-staging LDS-DMA, 7 / 8 direct kernel for two input / two output channels,
+ * 9 Winograd F(2x2,3x3); csrc/conv_select.h) | tile rows << 8 (family 3: tile height, 9: variant) | split count << 20 |
+ * folded split-K << 28 | tail split << 29 | pair launch << 30 */
 int udet_debug_last_conv(void);
 #ifdef __cplusplus
 }

@@ -495,6 +495,97 @@ def test_conv_pair_launch(ops, case):
         assert float((y0 - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
 
 
+def _tune_file_lines(path):
+    """udet_tune_save to `path`: (header, set of entry lines)."""
+    from unsupervised_detection_amd import _ffi
+    assert _ffi.lib.udet_tune_save(str(path).encode()) == 0
+    lines = path.read_text().splitlines()
+    return lines[0], set(lines[1:])
+
+
+# a shape no other test uses: two 128-row tiles, K = 9 taps x 8 channels = three 32-wide stages, so the split capacity is 1
+TUNED_SHAPE = (1, 12, 20, 8, 24)
+
+
+def test_tuned_forward_entry_is_what_runs_and_a_loaded_one_is_validated(ops, force_conv, tmp_path):
+    """The autotuner's cache entry of a shape is the configuration its next launch runs, and an entry that arrives through udet_tune_load
+    is validated against the launch before it runs: family and tile as written where they are instantiated, the split count clamped to
+    the launch's capacity, a tile that does not exist replaced by a configuration that does."""
+    from unsupervised_detection_amd import _ffi
+    n, h, w, cin, cout = TUNED_SHAPE
+    x = rnd(n, h, w, cin, seed=131)
+    wt = rnd(3, 3, cin, cout, seed=132, scale=(2.0 / (9 * cin)) ** 0.5)
+    b = rnd(cout, seed=133, scale=0.1)
+    ref = _oracle_conv(x.double(), wt.double(), b.double(), 1, 1, "none", 0.0, False).float()
+    xg, wg, bg = x.cuda(), wt.cuda(), b.cuda()
+
+    def run():
+        y = ops.conv2d(xg, wg, bg, 1, 1, "none", 0.0, False).cpu()
+        assert (y - ref).abs().max() < 1e-4 * max(1.0, float(ref.abs().max()))
+        last = force_conv.udet_debug_last_conv()
+        return last & 0xff, (last >> 8) & 0xfff, (last >> 20) & 0xff  # family, bm field, split count
+
+    header, before = _tune_file_lines(tmp_path / "a.txt")
+    try:
+        force_conv.udet_debug_set_tuning(1)
+        run()
+    finally:
+        force_conv.udet_debug_set_tuning(0)
+    new = sorted(l for l in _tune_file_lines(tmp_path / "b.txt")[1] - before if l.startswith("c "))
+    assert len(new) == 1, new
+    key, bm, bn, ks, ws, fold, tail = (int(v) for v in new[0].split()[1:])
+    try:
+        fam, bm_ran, ks_ran = run()
+        assert (fam, ks_ran) == (ws, ks)
+        assert ws in (7, 8) or bm_ran == bm
+
+        def load(fields):
+            f = tmp_path / "load.txt"
+            f.write_text(f"{header}\nc {key} {fields}\n")
+            assert _ffi.lib.udet_tune_load(str(f).encode()) == 1
+            return run()
+
+        fam, bm_ran, _ = load("128 32 1 1 0 0")
+        assert (fam, bm_ran) == (1, 128)
+        assert load("128 32 1 0 0 0")[0] == 0
+        assert load("128 32 64 1 0 0")[2] == 1  # (the capacity)
+        fam, bm_ran, _ = load("77 32 1 1 0 0")  # no such tile
+        assert 0 <= fam <= 9 and bm_ran in (128, 256)
+    finally:
+        f = tmp_path / "restore.txt"
+        f.write_text(f"{header}\n{new[0]}\n")
+        _ffi.lib.udet_tune_load(str(f).encode())
+
+
+def test_tuned_filter_gradient_entry_is_what_runs(ops, force_conv, tmp_path):
+    """The filter-gradient tuner's cache entry (split count | variant << 20) is what the next launch of the shape reports."""
+    n, h, w, cin, cout = TUNED_SHAPE
+    x = rnd(n, h, w, cin, seed=134).double()
+    wt = rnd(3, 3, cin, cout, seed=135, scale=(2.0 / (9 * cin)) ** 0.5).double().requires_grad_(True)
+    b = rnd(cout, seed=136, scale=0.1).double().requires_grad_(True)
+    y = O.conv2d_same(x, wt, b, 1, 1)
+    dy = rnd(*y.shape, seed=137).double()
+    gw, gb = torch.autograd.grad((y * dy).sum(), [wt, b])
+    xg, dyg = x.float().cuda(), dy.float().cuda()
+
+    def run():
+        dw, db = ops.conv2d_backward_filter(xg, dyg, None, (3, 3), 1, 1, "none", 0.0, False)
+        tol = lambda ref: 2e-4 * max(1.0, float(ref.abs().max()))
+        assert (dw.cpu() - gw.float()).abs().max() < tol(gw)
+        assert (db.cpu() - gb.float()).abs().max() < tol(gb)
+        return force_conv.udet_debug_last_wgrad()
+
+    _, before = _tune_file_lines(tmp_path / "a.txt")
+    try:
+        force_conv.udet_debug_set_tuning(1)
+        run()
+    finally:
+        force_conv.udet_debug_set_tuning(0)
+    new = sorted(l for l in _tune_file_lines(tmp_path / "b.txt")[1] - before if l.startswith("w "))
+    assert len(new) == 1, new
+    assert run() == int(new[0].split()[2])
+
+
 def test_elu_accuracy(ops):
     """The ELU of the convolution epilogues (csrc/common.h elu_negative: exp(v) - 1 below -0.25, a degree-6 polynomial above) against
     float64 expm1 over the whole negative range, through a 1x1 identity convolution."""

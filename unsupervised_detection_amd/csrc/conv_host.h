@@ -4,7 +4,7 @@ namespace udet {
 void same_pad(int in, int k, int s, int d, int* before, int* out);
 void conv_setup_fwd(ConvParams& p, int N, int H, int W, int kh, int kw, int s, int d);
 int conv_dgrad_classes(int s, int H, int W);
-void conv_force_config(int bm, int bn, int ks);
+void conv_force_config(int bm, int bn, int ks);  // conv_select.hip; the bit layout of udet_debug_force_conv
 // direct kernels for the 2-channel heads (conv_thin.hip): eligibility of a launch / the launches
 bool conv_thin_n_ok(const ConvParams& p);
 bool conv_thin_k_ok(const ConvParams& p);
@@ -28,15 +28,13 @@ int launch_wino_pack(const float* src, float* dst, int R, int C, int Kc, int np,
 int launch_wino_from_packed(const ConvParams& p, float* dst, int np, hipStream_t stream);
 void conv_debug_f16(int on);  // fp16 multiplication in the single-operator launches (plans carry udet_config.conv_fp16)
 int conv_debug_f16_on();
-int conv_last_config();
+int conv_last_config();  // family | bm field << 8 | split count << 20 | ... of the most recent launch (conv_select.hip; udet_debug_last_conv)
 void conv_set_tuning(int on);   // autotuner: while on, unseen problem shapes are timed and the best configuration cached
-int conv_tuned_shapes();
-void conv_clear_tuning();
+// the tuning caches (conv_tune.hip): entries in all three, their text form (the lines behind udet_tune_save's header), one line back in
+int tuned_shapes();
+void tune_dump(FILE* f);
+bool tune_put_line(const char* line);
 int conv_tune_rejected();      // winners whose output differed from the reference configuration's (never cached)
-void conv_tune_note_reject();
-// tuning-time scratch (two device buffers of `floats` each, alive while tuning is on) and the max-abs comparison the tuners use
-float* tune_scratch(size_t floats, int which);
-bool tune_compare(const float* a, const float* b, size_t n, hipStream_t stream, float* diff_out, float* scale_out);
 void wgrad_set_tuning(int on);
 // Winograd-domain filter gradient (conv_wgrad_wino.hip): eligibility of a (plain-view) launch, the slice count for `wanted` (0: one
 // workgroup per CU), the GEMM launch into conv_wgrad.hip's slab layout
@@ -45,19 +43,10 @@ int wgrad_wino_slices(const WgradParams& p, int wanted);
 int launch_wgrad_wino(const WgradParams& q, int slices, int ldn, hipStream_t stream);
 int wgrad_last_config();  // split count | variant << 20 of the most recent launch_wgrad_T (variant 3: the Winograd-domain family)
 void wgrad_force(int nsplit, int dma);  // debug hook: nsplit > 0 pins the split count (clamped to the capacity), dma 0 / 1 / 2 the staging variant, 3 the Winograd-domain family where eligible (-1: as tuned)
-int wgrad_tuned_shapes();
-void conv_tune_dump(FILE* f);
-void conv_tune_put(unsigned long long key, int bm, int bn, int ks, int ws, int fold, int tail);
-void wgrad_tune_dump(FILE* f);
-void conv_pair_tune_dump(FILE* f);  // "p <pair key> bm bn ks ws" (ws < 0: the two problems stay apart)
-void conv_pair_tune_put(unsigned long long key, int bm, int bn, int ks, int ws);
-int conv_pair_tuned_shapes();
-void conv_pair_clear_tuning();
 void conv_force_pair(int on);  // test hook: 1 = pair every compatible couple, 0 = never, -1 = as tuned / heuristic
 int conv_last_pair();          // 1: the most recent launch_conv_pair went out as ONE launch
 // bumped whenever a kernel family, a tile set or a problem key changes: tuning files of another build are rejected (udet_tune_load)
 #define UDET_TUNE_ABI 6
-void wgrad_tune_put(unsigned long long key, int cfg);  // debugging / tuning hook: bm == 0 and ks < 0 restore the heuristics
 bool conv_setup_dgrad(ConvParams& p, int cls, int N, int H, int W, int kh, int kw, int s, int d);
 int launch_pack_weights(const float* src, float* dst, int T, int R, int C, int Kc, int ldw, int k_split, int k_gap,
                         int mode, const float* scale, hipStream_t stream);

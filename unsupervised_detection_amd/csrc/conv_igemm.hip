@@ -16,18 +16,15 @@
 // Replaces the TF-1.13 Conv2D / Conv2DBackpropInput kernels the reference calls through
 // tf.layers.conv2d / tf.nn.conv2d / tf.layers.conv2d_transpose
 // (models/utils/convolution_utils.py:46,81; models/PWCNet/model_pwcnet.py:161-165,286,484-504,562-574).
-#include <stdlib.h>
-
-#include <functional>
+//
+// This file holds the kernels and, at its end, the code that instantiates them: the table of tiles, launch_conv_gemm and
+// launch_conv_gemm_pair (conv_select.h).  Which configuration a launch runs is decided in conv_select.hip; the autotuner is
+// conv_tune.hip.
 #include <type_traits>
-#include <mutex>
-#include <unordered_map>
-#include <vector>
 
 #include "common.h"
 #include "conv_epilogue.h"
-#include "conv_host.h"
-#include <algorithm>
+#include "conv_select.h"
 
 namespace udet {
 
@@ -1378,7 +1375,7 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue4_pair_kernel(const C
 }
 
 // x-blocks of a launch: M tiles of every class / segment
-static int conv_xblocks(const ConvParams& p, int bm) {
+int conv_xblocks(const ConvParams& p, int bm) {
   if (p.nseg == 0) return p.ncls * ((p.N * p.OHq * p.OWq + bm - 1) / bm);
   int x = 0;
   for (int s = 0; s < p.nseg; ++s) x += (p.N * p.seg[s].h * p.seg[s].w + bm - 1) / bm;
@@ -1402,32 +1399,17 @@ int launch_splitk_second_pass(const ConvParams& p, hipStream_t stream) {
   return UDET_OK;
 }
 
-static int g_force_bm = 0, g_force_bn = 0, g_force_ks = -1, g_force_ws = -1, g_force_fold = -1, g_force_tail = 0;
-static int g_last_cfg = 0;  // kernel family / tile / split count of the most recent launch_conv (debug query)
-int conv_last_config() { return g_last_cfg; }
-void conv_force_config(int bm, int bn, int ks) {
-  g_force_bm = bm & 0xffff; g_force_bn = bn;
-  g_force_ks = ks < 0 ? ks : (ks & 0xff);
-  g_force_tail = ks < 0 ? 0 : ((ks >> 8) & 0xff);  // ks + 256 r: tail split for r workgroup slots per CU (ks & 255 slices; 0: as many as fill a round)
-  // bit 16: non-specialised, 17: LDS-DMA (wave-specialised), 18: tile kernel, 19: self-staging LDS-DMA (4 waves, BK 16);
-  // bit 20: split-K through the second launch, bit 21: split-K folded into the last-arriving workgroup;
-  // bit 22 / 23: LDS-DMA with a 3 / 4 stage ring; bit 24: the direct 2-channel-head kernels (conv_thin.hip) where a launch is eligible
-  g_force_fold = (bm >> 20) & 1 ? 0 : ((bm >> 21) & 1 ? 1 : -1);
-  // bit 25: the Winograd F(2x2,3x3) family (conv_wino.hip) where a launch is eligible; bm & 0xffff = variant (bit 0: 64 tiles x 64 channels / 128 x 32, bit 1: four / eight waves)
-  g_force_ws = (bm >> 16) & 1 ? 0 : ((bm >> 17) & 1 ? 2 : ((bm >> 18) & 1 ? 3 : ((bm >> 19) & 1 ? 6 : ((bm >> 22) & 1 ? 4 : ((bm >> 23) & 1 ? 5 : ((bm >> 24) & 1 ? 7 : ((bm >> 25) & 1 ? 9 : -1)))))));
-}
-
 template <int BM, int BN, int BK, int WAVES_M, int WAVES_N>
-static int launch_cfg(ConvParams& p, int ws, hipStream_t stream) {
-  const int Mtot = p.N * p.OHq * p.OWq;  // (tail split: unsegmented launches only, run_cfg)
+static int launch_cfg(ConvParams& p, int family, hipStream_t stream) {
+  const int Mtot = p.N * p.OHq * p.OWq;  // (tail split: unsegmented launches only, launch_conv_gemm)
   dim3 grid(conv_xblocks(p, BM), (p.Cout + BN - 1) / BN, p.ksplit > 1 ? p.ksplit : 1);
-  if (p.tail_ks > 1) {  // tail split (run_cfg checked the kernel family, the slab capacity and the alignment)
+  if (p.tail_ks > 1) {  // tail split (launch_conv_gemm checked the kernel family, the slab capacity and the alignment)
     const int mtiles = (Mtot + BM - 1) / BM;
     p.tail_prow0 = (p.tail_full / mtiles) * Mtot + (p.tail_full % mtiles) * BM;
     grid.x = p.tail_full + (grid.x - p.tail_full) * p.tail_ks;
     grid.z = 1;
   }
-  if (ws == 6) {
+  if (family == FAM_SELF_STAGING) {
     if constexpr (BM % 64 == 0 && BN % 64 == 0 && BM <= 128) {
       if (p.f16) UDET_LAUNCH((conv_igemm_dma4_kernel<BM, BN, 2, 2, true>), grid, dim3(256), 0, stream, p);
       else UDET_LAUNCH((conv_igemm_dma4_kernel<BM, BN, 2, 2>), grid, dim3(256), 0, stream, p);
@@ -1439,15 +1421,15 @@ static int launch_cfg(ConvParams& p, int ws, hipStream_t stream) {
       return UDET_ERR_UNSUPPORTED;
     }
   }
-  else if (ws == 2 && p.f16) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 2, true>), grid, dim3(512), 0, stream, p);
-  else if ((ws == 4 || ws == 5) && p.f16) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 3, true>), grid, dim3(512), 0, stream, p);
-  else if (ws == 2) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 2>), grid, dim3(512), 0, stream, p);
-  else if (ws == 4) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 3>), grid, dim3(512), 0, stream, p);
-  else if (ws == 5) {
+  else if (family == FAM_DMA2 && p.f16) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 2, true>), grid, dim3(512), 0, stream, p);
+  else if ((family == FAM_DMA3 || family == FAM_DMA4) && p.f16) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 3, true>), grid, dim3(512), 0, stream, p);
+  else if (family == FAM_DMA2) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 2>), grid, dim3(512), 0, stream, p);
+  else if (family == FAM_DMA3) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 3>), grid, dim3(512), 0, stream, p);
+  else if (family == FAM_DMA4) {
     if constexpr (BM <= 128) UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 4>), grid, dim3(512), 0, stream, p);
     else UDET_LAUNCH((conv_igemm_dma_kernel<BM, BN, WAVES_M, WAVES_N, 3>), grid, dim3(512), 0, stream, p);
   }
-  else if (ws) UDET_LAUNCH((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true>), grid, dim3(512), 0, stream, p);
+  else if (family != FAM_PLAIN) UDET_LAUNCH((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, true>), grid, dim3(512), 0, stream, p);
   else UDET_LAUNCH((conv_igemm_kernel<BM, BN, BK, WAVES_M, WAVES_N, false>), grid, dim3(256), 0, stream, p);
   UDET_HIP(hipGetLastError());
   if (p.tail_ks > 1) {
@@ -1460,578 +1442,13 @@ static int launch_cfg(ConvParams& p, int ws, hipStream_t stream) {
   return UDET_OK;
 }
 
-// ---- tile / split-K selection ---------------------------------------------------------------
-struct ConvCfg { int bm, bn, ks, ws, fold, tail; };  // fold: split-K summed by the last-arriving workgroup (no second launch);
-                                                    // tail > 0: x-blocks [0, tail) unsplit, the rest cut into ks slices (ConvParams::tail_full)
-static long cfg_tiles(const ConvParams& p, int bm, int bn) {
-  return (long)conv_xblocks(p, bm) * ((p.Cout + bn - 1) / bn);
-}
-static int max_class_taps(const ConvParams& p) {
-  int mx = 0;
-  for (int c = 0; c < p.nseg; ++c) mx = p.seg_tap[c + 1] - p.seg_tap[c] > mx ? p.seg_tap[c + 1] - p.seg_tap[c] : mx;
-  if (p.nseg) return mx;
-  for (int c = 0; c < p.ncls; ++c) mx = p.cls_tap[c + 1] - p.cls_tap[c] > mx ? p.cls_tap[c + 1] - p.cls_tap[c] : mx;
-  return mx;
-}
-static int max_ksplit(const ConvParams& p) {  // capacity / minimum-work bound on the split count
-  if (!p.partial) return 1;
-  const int nchunks = (max_class_taps(p) * p.Kc + 31) / 32;
-  int ks = nchunks / 2 > 64 ? 64 : nchunks / 2;
-  const size_t per_split = (size_t)p.Mall * ((p.Cout + 3) & ~3);
-  while (ks > 1 && per_split * ks > p.partial_cap) --ks;
-  return ks < 1 ? 1 : ks;
-}
-struct TileGeoms;
-size_t conv_tile_lds_bytes(const ConvParams& p, int th, int cbmax, TileGeoms* gout, bool* big);
-int launch_conv_tile(const ConvParams& p, int th, int cbmax, hipStream_t stream);
-static bool tile_ok(const ConvParams& p, int th, int cb = 32) {
-  if (p.nseg) return false;  // segmented launches: implicit-GEMM families only
-  if (cb == 16 && p.Kc <= 16) return false;  // (the same launch as cb = 32)
-  const size_t b = conv_tile_lds_bytes(p, th, cb, nullptr, nullptr);
-  // (<= 256 columns: the kernel walks 32-column blocks as blockIdx.y and re-reads the halo per block -- thin inputs with wide outputs,
-  // the backward-data view of the recover decoder: 32 -> 194 channels 163 -> 150 us; beyond that the implicit GEMM always won)
-  return b > 0 && b <= 96 * 1024 && p.Kc <= 256 && p.Cout <= 256;
-}
-static bool self_staging_tile(int bm, int bn) {  // tiles conv_igemm_dma4_kernel is instantiated for
-  return ((bm == 128 || bm == 64) && (bn == 64 || bn == 128)) || (bn == 32 && (bm == 128 || bm == 256));
-}
-static bool dma_ok(const ConvParams& p) { return p.xa == nullptr && p.zero16 != nullptr && !(reinterpret_cast<uintptr_t>(p.zero16) & 15); }
-// tail split for workgroups filling r slots per CU: x-blocks of the whole rounds stay unsplit (*full_x of them), the rest is cut
-// into *ks slices so that it fills one more round.  false: the tile count is a whole number of rounds, or less than one.
-static bool tail_for_rounds(const ConvParams& p, int bm, int bn, int r, int kcap, int* full_x, int* ks) {
-  if (p.nseg) return false;
-  const int Mtot = p.N * p.OHq * p.OWq, X = p.ncls * ((Mtot + bm - 1) / bm), Y = (p.Cout + bn - 1) / bn;
-  const long S = 256L * r, T = (long)X * Y, fullT = T / S * S;
-  if (fullT == 0 || fullT == T) return false;
-  const int fx = (int)(fullT / Y), rem_x = X - fx;
-  if (fx <= 0 || rem_x <= 0) return false;
-  long k = S / ((long)rem_x * Y);
-  if (k > kcap) k = kcap;
-  if (k < 2) return false;
-  *full_x = fx;
-  *ks = (int)k;
-  return true;
-}
-static ConvCfg heuristic_cfg(const ConvParams& p) {
-  // N tile from the channel count; M tile shrunk while the launch would leave CUs without a workgroup
-  ConvCfg c;
-  c.ws = 1; c.fold = 0; c.tail = 0;
-  if (p.Cout <= 32) { c.bn = 32; c.bm = 256; if (cfg_tiles(p, 256, 32) < 384) c.bm = 128; }
-  else if (p.Cout <= 64) { c.bn = 64; c.bm = 128; if (cfg_tiles(p, 128, 64) < 384) c.bm = 64; }
-  else if (p.Cout <= 96) { c.bn = 96; c.bm = 128; }
-  else { c.bn = 128; c.bm = 128; if (cfg_tiles(p, 128, 128) < 320) { c.bn = 64; if (cfg_tiles(p, 128, 64) < 384) c.bm = 64; } }
-  const long tiles = cfg_tiles(p, c.bm, c.bn);
-  c.ks = 1;
-  if (tiles < 256) {
-    int ks = (int)((512 + tiles - 1) / tiles);
-    const int cap = max_ksplit(p), half = cap / 2 > 0 ? cap / 2 : 1;  // keep >= 4 stages per split
-    c.ks = ks > half ? half : ks;
-  }
-  c.fold = 0;  // measured (r2a): the release / acquire of the folded form costs more than the second launch on almost every shape;
-               // the tuner still tries it for its winner
-  if (p.f16 && dma_ok(p)) c.ws = 2;  // fp16 multiplication exists in the LDS-DMA families only
-  return c;
-}
-static int run_cfg(ConvParams& p, const ConvCfg& c, hipStream_t stream) {
-  if (c.ws == 7 || c.ws == 8) {  // direct kernels for the 2-channel heads (conv_thin.hip): 7 two input channels, 8 two output channels
-    p.ksplit = 1; p.fold = 0; p.tail_full = 0; p.tail_ks = 0;
-    return c.ws == 7 ? launch_conv_thin_k(p, stream) : launch_conv_thin_n(p, stream);
-  }
-  if (c.ws == 9) return launch_conv_wino(p, c.bm, c.ks, stream);  // Winograd F(2x2,3x3) (conv_wino.hip); bm carries the variant
-  if (c.ws == 3) {  // tile-resident direct convolution (conv_tile.hip); bm carries the tile height
-    p.ksplit = 1;
-    p.fold = 0;
-    return launch_conv_tile(p, c.bm, c.bn == 16 ? 16 : 32, stream);  // bn carries the channels per pass
-  }
-  p.ksplit = c.ks > 1 ? c.ks : 1;
-  p.fold = 0;
-  p.tail_full = 0; p.tail_ks = 0; p.tail_prow0 = 0;
-  if (p.ksplit > 1) {
-    p.ldp = (p.Cout + 3) & ~3;
-    p.fold = c.fold && p.tickets && cfg_tiles(p, c.bm, c.bn) <= UDET_MAX_TICKETS;
-    const int Mtot = p.N * p.OHq * p.OWq, mtiles = (Mtot + c.bm - 1) / c.bm, xb = p.ncls * mtiles;
-    if (c.tail > 0 && c.tail < xb && !p.nseg && (c.ws == 2 || c.ws == 4 || c.ws == 5) && !(reinterpret_cast<uintptr_t>(p.partial) & 15)) {
-      const long prow0 = (long)(c.tail / mtiles) * Mtot + (long)(c.tail % mtiles) * c.bm;
-      if ((size_t)((long)p.ncls * Mtot - prow0) * p.ldp * p.ksplit <= p.partial_cap) {
-        p.tail_full = c.tail; p.tail_ks = p.ksplit; p.ksplit = 1; p.fold = 0;
-      }
-    }
-  }
-  if (c.bm == 256 && c.bn == 32) return launch_cfg<256, 32, 32, 4, 1>(p, c.ws, stream);
-  if (c.bm == 128 && c.bn == 32) return launch_cfg<128, 32, 32, 4, 1>(p, c.ws, stream);
-  if (c.bm == 128 && c.bn == 64) return launch_cfg<128, 64, 32, 2, 2>(p, c.ws, stream);
-  if (c.bm == 64 && c.bn == 64) return launch_cfg<64, 64, 32, 2, 2>(p, c.ws, stream);
-  if (c.bm == 128 && c.bn == 96) return launch_cfg<128, 96, 32, 4, 1>(p, c.ws, stream);
-  if (c.bm == 128 && c.bn == 128) return launch_cfg<128, 128, 32, 2, 2>(p, c.ws, stream);
-  set_error("conv: no kernel for tile %dx%d", c.bm, c.bn);
-  return UDET_ERR_UNSUPPORTED;
-}
-
-// ---- autotuner: while tuning is on, the first launch of every distinct problem shape times its candidate
-// (tile, split-K, wave-specialisation) configurations on the caller's stream and caches the fastest -------------
-static std::unordered_map<uint64_t, ConvCfg> g_cache;
-static std::mutex g_cache_mu;
-static int g_tuning = 0;
-static void tune_scratch_free();
-void conv_set_tuning(int on) { g_tuning = on; if (!on) tune_scratch_free(); }
-int conv_tuned_shapes() { std::lock_guard<std::mutex> l(g_cache_mu); return (int)g_cache.size(); }
-void conv_clear_tuning() { std::lock_guard<std::mutex> l(g_cache_mu); g_cache.clear(); }
-// text form of the cache ("c <problem key> bm bn ks ws fold tail" per line): lets a second process (a rocprofv3 trace of timed
-// steps only) run exactly the configurations a tuning run picked
-void conv_tune_dump(FILE* f) {
-  std::lock_guard<std::mutex> l(g_cache_mu);
-  for (auto& kv : g_cache)
-    fprintf(f, "c %llu %d %d %d %d %d %d\n", (unsigned long long)kv.first, kv.second.bm, kv.second.bn, kv.second.ks, kv.second.ws, kv.second.fold,
-            kv.second.tail);
-}
-void conv_tune_put(unsigned long long key, int bm, int bn, int ks, int ws, int fold, int tail) {
-  std::lock_guard<std::mutex> l(g_cache_mu);
-  g_cache[(uint64_t)key] = ConvCfg{bm, bn, ks, ws, fold, tail};
-}
-
-// ---- candidate verification -------------------------------------------------------------------------------------------
-// The tuner selects on time; a configuration that is fast because it computes something else must never be cached.  Before
-// a winner is stored its output on the tuning data is compared (max-abs, relative to the largest reference element) with the
-// output of the reference configuration (built-in heuristic, register-staged wave-specialised kernel).  The two result
-// buffers are temporary device allocations that live only while tuning is on (the one place where the library allocates).
-static float* g_vbuf[3] = {nullptr, nullptr, nullptr};  // two result buffers + {max|a-b|, max|a|}
-static size_t g_vcap = 0;
-static int g_rejected = 0;
-int conv_tune_rejected() { return g_rejected; }
-void conv_tune_note_reject() { ++g_rejected; }
-float* tune_scratch(size_t floats, int which) {
-  if (floats > g_vcap) {
-    for (int i = 0; i < 2; ++i) { if (g_vbuf[i]) (void)hipFree(g_vbuf[i]); g_vbuf[i] = nullptr; }
-    g_vcap = floats + floats / 4;
-    for (int i = 0; i < 2; ++i)
-      if (hipMalloc(reinterpret_cast<void**>(&g_vbuf[i]), g_vcap * sizeof(float)) != hipSuccess) { g_vbuf[i] = nullptr; g_vcap = 0; return nullptr; }
-  }
-  if (!g_vbuf[2] && hipMalloc(reinterpret_cast<void**>(&g_vbuf[2]), 2 * sizeof(float)) != hipSuccess) return nullptr;
-  return g_vbuf[which];
-}
-static void tune_scratch_free() {
-  for (int i = 0; i < 3; ++i) { if (g_vbuf[i]) (void)hipFree(g_vbuf[i]); g_vbuf[i] = nullptr; }
-  g_vcap = 0;
-}
-__global__ __launch_bounds__(256) void tune_maxdiff_kernel(const float* __restrict__ a, const float* __restrict__ b, long n, float* __restrict__ out) {
-  float d = 0.f, m = 0.f;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long)gridDim.x * 256) {
-    const float x = a[e], y = b[e];
-    float df = fabsf(x - y);
-    if (!(df == df)) df = 3.0e38f;  // NaN in either result
-    d = fmaxf(d, df);
-    m = fmaxf(m, fabsf(x));
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { d = fmaxf(d, __shfl_xor(d, o)); m = fmaxf(m, __shfl_xor(m, o)); }
-  if ((threadIdx.x & 63) == 0) {  // non-negative floats order like their bit patterns
-    atomicMax(reinterpret_cast<int*>(out), __float_as_int(d));
-    atomicMax(reinterpret_cast<int*>(out) + 1, __float_as_int(m));
-  }
-}
-// max|a-b| <= 2e-4 * max|a| + 1e-6 ?  (a = reference; split-K orders differ by ~1e-6 relative)
-bool tune_compare(const float* a, const float* b, size_t n, hipStream_t stream, float* diff_out, float* scale_out) {
-  float* res = g_vbuf[2];
-  if (!res) return false;
-  if (hipMemsetAsync(res, 0, 2 * sizeof(float), stream) != hipSuccess) return false;
-  long nbl = ((long)n + 255) / 256;
-  hipLaunchKernelGGL(tune_maxdiff_kernel, dim3((int)(nbl > 2048 ? 2048 : nbl)), dim3(256), 0, stream, a, b, (long)n, res);
-  float h[2] = {3.0e38f, 0.f};
-  if (hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) return false;
-  if (diff_out) *diff_out = h[0];
-  if (scale_out) *scale_out = h[1];
-  return h[0] <= 2e-4f * h[1] + 1e-6f;
-}
-
-static uint64_t conv_key(const ConvParams& p) {
-  const int f[] = {p.N, p.H, p.W, p.up_shift, p.Kc, p.Cout, p.ntaps, p.ncls, p.OHq, p.OWq, p.isy, p.osy, p.xa ? 1 : 0,
-                   p.ldx, p.ldy, p.accumulate, p.res ? 1 : 0, p.y2 ? 1 : 0, p.partial ? 1 : 0, p.cls_tap[1], p.uo ? 1 : 0, p.f16 ? 1 : 0, p.kreal,
-                   p.wino_u ? p.wino_np : 0, p.ntaps > 0 ? p.taps[0].dy : 0, p.ntaps > 0 ? p.taps[0].dx : 0};  // (first tap: the dilation -- it
-                                                                                         // decides what the Winograd sub-lattices look like)
-  uint64_t h = 1469598103934665603ull;
-  for (int v : f) { h ^= (uint64_t)(uint32_t)v; h *= 1099511628211ull; }
-  for (int s = 0; s < p.nseg; ++s)  // segmented launches: the segment grids and their tap counts (ncls / OHq / OWq / taps[] are zero)
-    for (int v : {p.seg[s].oy, p.seg[s].ox, p.seg[s].h, p.seg[s].w, p.seg_tap[s + 1]}) { h ^= (uint64_t)(uint32_t)v; h *= 1099511628211ull; }
-  return h;
-}
-static float time_cfg(ConvParams& p, const ConvCfg& c, int reps, hipStream_t stream) {
-  static hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
-  if (run_cfg(p, c, stream) != UDET_OK) return 1e30f;  // warm-up
-  (void)hipEventRecord(e0, stream);
-  for (int r = 0; r < reps; ++r) run_cfg(p, c, stream);
-  (void)hipEventRecord(e1, stream);
-  if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  return ms / reps;
-}
-static ConvCfg tune_cfg_impl(ConvParams& p, hipStream_t stream);
-static ConvCfg tune_cfg(ConvParams& p, hipStream_t stream) {
-  // candidates are launched hundreds of times: an accumulating launch would grow its output with every repetition and the layers
-  // behind it would be tuned (and verified) on ever larger data -- beyond the fp16 range in fp16 mode.  Timed as plain stores (one
-  // read of the output less per element).
-  const int acc = p.accumulate;
-  p.accumulate = 0;
-  const ConvCfg c = tune_cfg_impl(p, stream);
-  p.accumulate = acc;
-  return c;
-}
-static ConvCfg tune_cfg_impl(ConvParams& p, hipStream_t stream) {
-  const ConvCfg h = heuristic_cfg(p);
-  std::vector<ConvCfg> cand;
-  static const int TILES[6][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 96}, {128, 128}};
-  const int kcap = max_ksplit(p);
-  for (auto& t : TILES) {
-    const int bm = t[0], bn = t[1];
-    // N tiles wider than needed waste MFMA columns; much narrower ones re-read the A operand
-    if (p.Cout <= 32 && bn != 32) continue;
-    if (p.Cout > 32 && p.Cout <= 64 && bn > 64) continue;
-    if (p.Cout > 64 && p.Cout <= 96 && bn != 96 && bn != 32) continue;
-    if (p.Cout > 96 && bn < 64) continue;
-    if (p.Cout > 96 && bn == 96 && p.Cout % 96 != 0 && p.Cout <= 128) continue;
-    const long tiles = cfg_tiles(p, bm, bn);
-    std::vector<int> kss;
-    for (int ks = 1; ks <= kcap; ks *= 2) kss.push_back(ks);
-    // split counts that fill whole rounds of the 256 CUs (tiles*ks just below a multiple of 256): a 144-tile layer runs
-    // at 144/256 of the chip unsplit and at 1008/1024 with 7 splits
-    if (tiles < 512)
-      for (int k = 1; k <= 6; ++k) {
-        const int ks = (int)(256L * k / tiles);
-        if (ks >= 3 && ks <= kcap && (ks & (ks - 1)) != 0 && std::find(kss.begin(), kss.end(), ks) == kss.end()) kss.push_back(ks);
-      }
-    for (int ks : kss) {
-      if (ks > 1 && (tiles >= 512 || tiles * ks > 4096)) continue;
-      if (tiles * ks < 96 && ks * 2 <= kcap) continue;  // hopelessly under-filled
-      cand.push_back({bm, bn, ks, 1, 0});
-    }
-  }
-  cand.push_back(h);
-  ConvCfg best = h;
-  float best_ms = 1e30f;
-  for (auto& c : cand) {
-    float ms = time_cfg(p, c, 3, stream);
-    if (ms < best_ms * 1.15f && ms < 0.25f) ms = 0.5f * (ms + time_cfg(p, c, 6, stream));  // short launches: re-time the contenders
-    if (ms < best_ms) { best_ms = ms; best = c; }
-  }
-  ConvCfg alt = best;
-  alt.ws = 0;
-  float a = time_cfg(p, best, 5, stream), b = time_cfg(p, alt, 5, stream);
-  if (b < a * 0.97f) { best = alt; a = b; }
-  const bool f16 = p.f16 && dma_ok(p);  // only LDS-DMA configurations multiply in fp16: every candidate must, or results differ per shape
-  if (f16) { best = h; a = b = 1e30f; }
-  if (dma_ok(p)) {  // LDS-DMA staging: re-scan the tiles, the balance between staging and MFMA waves differs
-    for (auto& c : cand) {
-      ConvCfg d = c;
-      for (int ws : {2, 4, 5, 6}) {  // wave-specialised / self-staging (4 waves, 16-wide stages, 3-4 workgroups per CU)
-        if (ws == 6 && !self_staging_tile(d.bm, d.bn)) continue;
-        d.ws = ws;
-        const float ms = time_cfg(p, d, 3, stream);
-        if (ms < a * 0.98f) {
-          const float ms5 = time_cfg(p, d, 5, stream);
-          if (ms5 < a * 0.98f) { a = ms5; best = d; }
-        }
-        // Tail split of an unsplit candidate: a launch whose workgroups fill r slots per CU for k whole rounds and a fraction of
-        // another runs that last round on part of the chip (576 tiles of 64x64 on 256 CUs: three on 64 CUs, two on the rest).
-        // Cutting only the LAST round's tiles into K slices makes it a full round of short workgroups, at the slab traffic of
-        // those tiles alone.
-        if (d.ks <= 1 && ws != 6 && p.partial && kcap >= 2 && ms < a * 1.3f) {
-          long seen[4] = {0, 0, 0, 0};
-          for (int r = 1; r <= 4; ++r) {
-            int full_x = 0, ks = 0;
-            if (!tail_for_rounds(p, d.bm, d.bn, r, kcap, &full_x, &ks)) continue;
-            const long id = (long)full_x * 1024 + ks;
-            if (id == seen[0] || id == seen[1] || id == seen[2]) continue;
-            seen[r - 1] = id;
-            ConvCfg e = d;
-            e.ks = ks; e.tail = full_x; e.fold = 0;
-            const float mt = time_cfg(p, e, 3, stream);
-            if (mt < a * 0.98f) {
-              const float mt5 = time_cfg(p, e, 5, stream);
-              if (mt5 < a * 0.98f) { a = mt5; best = e; }
-            }
-          }
-        }
-      }
-    }
-    b = a;
-  }
-  for (int thcb : {8 * 64 + 32, 4 * 64 + 32, 8 * 64 + 16, 4 * 64 + 16}) {  // thin layers: tile-resident direct convolution (multiplies in fp16 too when asked to)
-    const int th = thcb >> 6, cb = thcb & 63;  // tile height x channels resident per pass
-    if (!tile_ok(p, th, cb)) continue;
-    const ConvCfg d = {th, cb, 1, 3, 0};
-    const float ms = time_cfg(p, d, 3, stream);
-    if (ms < a * 0.97f) {
-      const float ms5 = time_cfg(p, d, 5, stream);
-      if (ms5 < a * 0.97f) { a = b = ms5; best = d; }
-    }
-  }
-  for (int ws : {7, 8}) {  // the direct kernels for 2-channel inputs / outputs
-    if (!(ws == 7 ? conv_thin_k_ok(p) : conv_thin_n_ok(p)) || p.f16) continue;  // (fp16 mode: every configuration must multiply alike)
-    const ConvCfg d = {0, 0, 1, ws, 0, 0};
-    const float ms = time_cfg(p, d, 5, stream);
-    if (getenv("UDET_TUNE_LOG") && atoi(getenv("UDET_TUNE_LOG")) > 1)
-      fprintf(stderr, "[udet tune]   direct family %d: %.1f us against %.1f (N=%d %dx%d Kc=%d taps=%d Cout=%d)\n", ws, ms * 1e3f, (a < b ? a : b) * 1e3f, p.N, p.OHq, p.OWq, p.Kc, p.ntaps, p.Cout);
-    if (ms < (a < b ? a : b) * 0.97f) { a = b = ms; best = d; }
-  }
-  if (conv_wino_ok(p)) {  // Winograd F(2x2,3x3): 2.25x fewer multiplications; K slices where the tiles do not fill the chip
-    for (int v = 0; v < 5; ++v) {  // (bit 0: tile shape, bit 1: four / eight waves; 4: the half-size form, two workgroups per CU)
-      if (!conv_wino_variant_ok(p, v)) continue;
-      const long wgs = conv_wino_workgroups(p, v);
-      const int cap = conv_wino_max_ksplit(p, v);
-      std::vector<int> kss = {1};
-      if (wgs < 256 && cap >= 2) kss.push_back(2);  // (under one round of workgroups: two K slices even where no whole round results)
-      if (wgs < 384)
-        for (int r = 1; r <= 3; ++r) {
-          const int ks = (int)(256L * r / (wgs > 0 ? wgs : 1));
-          if (ks >= 2 && ks <= cap && std::find(kss.begin(), kss.end(), ks) == kss.end()) kss.push_back(ks);
-        }
-      for (int ks : kss) {
-        const ConvCfg d = {v, 0, ks, 9, 0, 0};
-        const float ms = time_cfg(p, d, 3, stream);
-        if (getenv("UDET_TUNE_LOG") && atoi(getenv("UDET_TUNE_LOG")) > 1)
-          fprintf(stderr, "[udet tune]   winograd variant %d ks=%d (%ld workgroups): %.1f us against %.1f (N=%d %dx%d Kc=%d Cout=%d)\n", v, ks, wgs, ms * 1e3f,
-                  (a < b ? a : b) * 1e3f, p.N, p.OHq, p.OWq, p.Kc, p.Cout);
-        if (ms < (a < b ? a : b) * 0.97f) {
-          const float ms5 = time_cfg(p, d, 5, stream);
-          if (ms5 < (a < b ? a : b) * 0.97f) { a = b = ms5; best = d; }
-        }
-      }
-    }
-  }
-  if (best.ks > 1 && best.ws != 3 && best.ws < 7 && best.tail == 0) {  // the other way of summing the slabs: last-arriving workgroup <-> second launch
-    const ConvCfg w = best;
-    for (int ks : {w.ks, w.ks / 2, w.ks / 4}) {  // the folded form sums its slabs in one workgroup: fewer slabs may suit it better
-      if (ks < 2) continue;
-      ConvCfg d = w;
-      d.fold = !w.fold;
-      d.ks = ks;
-      const float ms = time_cfg(p, d, 5, stream);
-      if (ms < (a < b ? a : b) * 0.98f) { a = b = ms; best = d; }
-    }
-  }
-  // verification against the reference configuration on the tuning data (see above)
-  if (best.bm != h.bm || best.bn != h.bn || best.ks != h.ks || best.ws != h.ws || best.fold != h.fold || best.tail != h.tail) {
-    const int ld = (p.Cout + 3) & ~3;
-    const size_t n = (size_t)p.N * p.OH * p.OW * ld;
-    float* r0 = tune_scratch(n, 0);
-    float* r1 = tune_scratch(n, 1);
-    bool ok = false;
-    float diff = 0.f, scale = 0.f;
-    if (r0 && r1) {
-      ConvParams q = p;
-      q.ldy = ld; q.y_coff = 0; q.accumulate = 0; q.y2 = nullptr; q.uo = nullptr;
-      (void)hipMemsetAsync(r0, 0, n * sizeof(float), stream);
-      (void)hipMemsetAsync(r1, 0, n * sizeof(float), stream);
-      q.y = r0;
-      int rc = run_cfg(q, h, stream);
-      q.y = r1;
-      if (rc == UDET_OK) rc = run_cfg(q, best, stream);
-      ok = rc == UDET_OK && tune_compare(r0, r1, n, stream, &diff, &scale);
-    }
-    if (!ok) {
-      fprintf(stderr, "[udet tune] REJECTED N=%d %dx%d Kc=%d taps=%d cls=%d Cout=%d: %dx%d ks=%d ws=%d fold=%d tail=%d differs from the reference "
-              "configuration (max|diff| %.3e, scale %.3e); keeping the heuristic\n", p.N, p.OHq, p.OWq, p.Kc, p.ntaps, p.ncls, p.Cout,
-              best.bm, best.bn, best.ks, best.ws, best.fold, best.tail, diff, scale);
-      conv_tune_note_reject();
-      best = h;
-    }
-  }
-  if (getenv("UDET_TUNE_LOG"))
-    fprintf(stderr, "[udet tune] N=%d %dx%d Kc=%d taps=%d cls=%d Cout=%d -> %dx%d ks=%d ws=%d fold=%d tail=%d  %.1f us (heuristic %dx%d ks=%d)\n", p.N,
-            p.OHq, p.OWq, p.Kc, p.ntaps, p.ncls, p.Cout, best.bm, best.bn, best.ks, best.ws, best.fold, best.tail, (a < b ? a : b) * 1e3f, h.bm, h.bn,
-            h.ks);
-  return best;
-}
-
-static int g_debug_f16 = 0;  // test hook: fp16 multiplication for the single-operator entry points too
-void conv_debug_f16(int on) { g_debug_f16 = on; }
-int conv_debug_f16_on() { return g_debug_f16; }
-// argument checks + the derived fields every kernel family reads (Mall, fast divisors, uniform-cursor flags, segment rows)
-static int conv_prepare(ConvParams& p) {
-  if (g_debug_f16) p.f16 = 1;
-  if (p.f16 && !(p.f16_xscale > 0.f)) p.f16_xscale = 1.f;
-  // the tuning pass repeats every launch hundreds of times on random data, accumulating launches included: its "gradients" are far
-  // larger than real ones and would overflow fp16 under the 4096 scale (every candidate NaN, every shape rejected); the scale does
-  // not change a launch's duration
-  if (p.f16 && g_tuning) p.f16_xscale = 1.f;
-  if (p.Kc % 4 != 0 || p.ldx % 4 != 0 || p.x_coff % 4 != 0 || p.ldw % 4 != 0) {
-    set_error("conv: Kc=%d ldx=%d x_coff=%d ldw=%d violate the 4-float alignment contract", p.Kc, p.ldx, p.x_coff, p.ldw);
-    return UDET_ERR_ALIGN;
-  }
-  if (p.ntaps < 0 || p.ntaps > UDET_MAX_TAPS) {
-    set_error("conv: ntaps=%d out of range", p.ntaps);
-    return UDET_ERR_SHAPE;
-  }
-  if ((reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.wp)) & 15) {
-    set_error("conv: x / packed weights must be 16-byte aligned");
-    return UDET_ERR_ALIGN;
-  }
-  if (p.nseg) {
-    if (p.nseg < 0 || p.nseg > UDET_MAX_SEGS || !p.tap_tab || p.up_shift || p.xa) {
-      set_error("conv: malformed segmented launch");
-      return UDET_ERR_ARG;
-    }
-    int prow = 0;
-    for (int s = 0; s < p.nseg; ++s) {
-      ConvSeg& g = p.seg[s];
-      if (g.h < 1 || g.w < 1 || p.seg_tap[s + 1] - p.seg_tap[s] > UDET_MAX_TAPS || p.seg_tap[s + 1] < p.seg_tap[s]) {
-        set_error("conv: segment %d is empty or has more than %d taps", s, UDET_MAX_TAPS);
-        return UDET_ERR_SHAPE;
-      }
-      g.prow0 = prow;
-      prow += p.N * g.h * g.w;
-      g.fd_hw = make_fastdiv((unsigned)(g.h * g.w));
-      g.fd_w = make_fastdiv((unsigned)g.w);
-    }
-    p.Mall = prow;
-    p.ncls = 1; p.ntaps = 0; p.cls_tap[0] = p.cls_tap[1] = 0;
-    p.OHq = p.seg[0].h; p.OWq = p.seg[0].w;  // (what the untuned heuristics and the log lines look at: the first, largest segment)
-  } else {
-    if (p.ncls != 4) {
-      p.ncls = 1;
-      p.cls_tap[0] = 0;
-      p.cls_tap[1] = p.ntaps;
-    }
-    p.Mall = p.ncls * p.N * p.OHq * p.OWq;
-  }
-  p.fd_ohw = make_fastdiv((unsigned)(p.OHq * p.OWq));
-  p.fd_ow = make_fastdiv((unsigned)p.OWq);
-  // uniform K cursors (no up-sampled read).  bit 0: Kc >= 32, 32-wide stages (wave-specialised kernel); bit 1: Kc >= 16, 16-wide
-  // stages (self-staging kernel); bit 2: Kc in {4, 8, 16}, 32 / Kc whole taps per 32-wide stage (wave-specialised kernel)
-  p.kfast = 0;
-  if (p.up_shift == 0) p.kfast = p.Kc >= 32 ? 3 : ((p.Kc >= 16 ? 2 : 0) | ((p.Kc == 4 || p.Kc == 8 || p.Kc == 16) ? 4 : 0));
-  return UDET_OK;
-}
-int launch_conv(ConvParams& p, hipStream_t stream) {
-  UDET_TRY(conv_prepare(p));
-  ConvCfg c;
-  bool have = false;
-  const uint64_t key = conv_key(p);
-  {
-    std::lock_guard<std::mutex> l(g_cache_mu);
-    auto it = g_cache.find(key);
-    if (it != g_cache.end()) { c = it->second; have = true; }
-  }
-  if (have) {
-    // a cached entry may come from a file (udet_tune_load): never trust it beyond what the launcher would choose itself --
-    // only instantiated tiles / families, the split count inside this launch's capacity, folding only where tickets exist
-    static const int TILES[6][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 96}, {128, 128}};
-    bool tile = false;
-    for (auto& t : TILES) tile = tile || (c.bm == t[0] && c.bn == t[1]);
-    if (c.ws == 3) tile = (c.bm == 4 || c.bm == 8) && (c.bn == 16 || c.bn == 32);
-    if (c.ws == 7 || c.ws == 8) tile = true;  // (the direct 2-channel kernels carry no tile; eligibility is re-checked below)
-    if (c.ws == 9) tile = c.bm >= 0 && c.bm <= 4;  // (Winograd: bm carries the variant; eligibility is re-checked below)
-    if (!tile || c.ws < 0 || c.ws > 9) {
-      c = heuristic_cfg(p);
-    } else {
-      const int cap = c.ws == 9 ? 16 : max_ksplit(p);  // (launch_conv_wino clamps to its own capacity)
-      if (c.ks < 1) c.ks = 1;
-      if (c.ks > cap) { c.ks = cap; c.tail = 0; }
-      c.fold = c.fold ? 1 : 0;
-      if (c.tail < 0) c.tail = 0;
-    }
-  }
-  if (!have) {
-    if (g_tuning) {
-      c = tune_cfg(p, stream);
-      std::lock_guard<std::mutex> l(g_cache_mu);
-      g_cache[key] = c;
-    } else {
-      c = heuristic_cfg(p);
-      // untuned default for the 2-channel heads: the direct kernels (an order of magnitude fewer padded multiplications)
-      // (not while a test pins an implicit-GEMM tile: udet_debug_force_conv)
-      if (!g_force_bm && !p.f16 && conv_thin_n_ok(p)) c.ws = 8;
-      else if (!g_force_bm && !p.f16 && conv_thin_k_ok(p)) c.ws = 7;
-    }
-  }
-  if (g_force_bm && g_force_ws != 9) { c.bm = g_force_bm; c.bn = g_force_bn; }
-  if (g_force_ks >= 0) { c.ks = (g_force_ks > max_ksplit(p) && g_force_ws != 9) ? max_ksplit(p) : g_force_ks; c.tail = 0; }
-  if (g_force_ws >= 0) c.ws = g_force_ws;
-  if (g_force_fold >= 0) c.fold = g_force_fold;
-  if (g_force_tail > 0) {
-    int fx = 0, k = 0;
-    if (tail_for_rounds(p, c.bm, c.bn, g_force_tail, max_ksplit(p), &fx, &k)) { c.tail = fx; c.ks = c.ks >= 2 ? c.ks : k; c.fold = 0; }
-  }
-  if ((c.ws == 2 || c.ws == 4 || c.ws == 5 || c.ws == 6) && !dma_ok(p)) c.ws = 1;
-  if (c.ws == 6 && !self_staging_tile(c.bm, c.bn)) c.ws = 2;
-  if (g_force_ws == 3) { c.ws = 3; c.bm = (g_force_bm == 4) ? 4 : 8; c.bn = g_force_bn == 16 ? 16 : 32; }
-  if (g_force_ws == 7) c.ws = conv_thin_k_ok(p) ? 7 : (conv_thin_n_ok(p) ? 8 : heuristic_cfg(p).ws);
-  if ((c.ws == 7 && !conv_thin_k_ok(p)) || (c.ws == 8 && !conv_thin_n_ok(p)) || ((c.ws == 7 || c.ws == 8) && p.f16)) c = heuristic_cfg(p);
-  if (c.ws == 3 && !tile_ok(p, c.bm, c.bn == 16 ? 16 : 32)) { c = heuristic_cfg(p); }
-  if (g_force_ws == 9) {  // test / tool hook: a single-operator launch carries no transformed weights -- build them here, from the packed ones
-    int d9, w9[9];
-    if (!p.wino_u && !p.f16 && !p.xa && p.Kc % 8 == 0 && p.Kc >= 8 && conv_wino_geometry(p, &d9, w9)) {
-      static float* g_wino_scratch = nullptr;
-      static size_t g_wino_cap = 0;
-      static std::mutex mu;
-      std::lock_guard<std::mutex> l(mu);
-      const int np9 = conv_wino_np(p.Cout);
-      const size_t need = (size_t)(p.Kc / 8) * 16 * 2 * np9 * 4;
-      if (need > g_wino_cap) {
-        (void)hipStreamSynchronize(stream);
-        if (g_wino_scratch) (void)hipFree(g_wino_scratch);
-        g_wino_scratch = nullptr; g_wino_cap = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&g_wino_scratch), need * sizeof(float)) == hipSuccess) g_wino_cap = need;
-      }
-      if (g_wino_scratch && launch_wino_from_packed(p, g_wino_scratch, np9, stream) == UDET_OK) { p.wino_u = g_wino_scratch; p.wino_np = np9; }
-    }
-    const int v9 = (g_force_bm & 7) == 4 ? 4 : (g_force_bm & 3);
-    if (conv_wino_ok(p) && (conv_wino_variant_ok(p, v9) || conv_wino_variant_ok(p, v9 ^ 1))) {
-      c.ws = 9; c.bm = conv_wino_variant_ok(p, v9) ? v9 : (v9 ^ 1); c.bn = 0; c.fold = 0; c.tail = 0;
-      if (g_force_ks < 0) c.ks = 1;
-    } else if (c.ws == 9) c = heuristic_cfg(p);
-  }
-  if (c.ws == 9 && (!conv_wino_ok(p) || !conv_wino_variant_ok(p, c.bm))) c = heuristic_cfg(p);
-  g_last_cfg = (c.ws & 0xff) | ((c.bm & 0xfff) << 8) | ((c.ks & 0xff) << 20) | ((c.ks > 1 && c.fold && c.ws != 3 && p.tickets ? 1 : 0) << 28) |
-               ((c.ks > 1 && c.tail > 0 ? 1 : 0) << 29);
-  return run_cfg(p, c, stream);
-}
-
-
-// ---- pair launches (two problems, one grid; conv_igemm_dma_pair_kernel) -----------------------------------------------------------------
-// Eligible: two unsegmented fp32 problems the LDS-DMA family can take, with the same K depth, output width, tap geometry, class
-// structure and strides (batch, operands, epilogue may differ).  The pair has ONE configuration (tile, K slices, stage ring), tuned as
-// a unit and cached under the pair's own key; ws < 0 in the cache = "these two are faster apart".
-static std::unordered_map<uint64_t, ConvCfg> g_pair_cache;
-static int g_force_pair = -1;  // test hook (libudet_debug): 1 pairs whatever the tuner thinks, 0 never pairs
-void conv_force_pair(int on) { g_force_pair = on; }
-static int g_last_pair = 0;
-int conv_last_pair() { return g_last_pair; }
-static bool pair_compatible(const ConvParams& a, const ConvParams& b) {
-  if (a.nseg || b.nseg || a.f16 || b.f16 || a.up_shift || b.up_shift || !dma_ok(a) || !dma_ok(b)) return false;
-  if (a.Kc != b.Kc || a.Cout != b.Cout || a.ldw != b.ldw || a.ntaps != b.ntaps || a.ncls != b.ncls) return false;
-  if (a.isy != b.isy || a.isx != b.isx || a.osy != b.osy || a.osx != b.osx || a.kfast != b.kfast) return false;
-  if (!a.partial || a.partial != b.partial) return false;  // (one scratch region, carved in two below)
-  for (int c = 0; c <= a.ncls; ++c)
-    if (a.cls_tap[c] != b.cls_tap[c]) return false;
-  for (int t = 0; t < a.ntaps; ++t)
-    if (a.taps[t].dy != b.taps[t].dy || a.taps[t].dx != b.taps[t].dx) return false;
-  return true;
-}
-static uint64_t pair_key(const ConvParams& a, const ConvParams& b) {
-  uint64_t h = conv_key(a) * 1099511628211ull ^ conv_key(b);
-  h ^= 0x9e3779b97f4a7c15ull;
-  return h * 1099511628211ull;
-}
-void conv_pair_tune_dump(FILE* f) {
-  std::lock_guard<std::mutex> l(g_cache_mu);
-  for (auto& kv : g_pair_cache) fprintf(f, "p %llu %d %d %d %d\n", (unsigned long long)kv.first, kv.second.bm, kv.second.bn, kv.second.ks, kv.second.ws);
-}
-void conv_pair_tune_put(unsigned long long key, int bm, int bn, int ks, int ws) {
-  std::lock_guard<std::mutex> l(g_cache_mu);
-  g_pair_cache[(uint64_t)key] = ConvCfg{bm, bn, ks, ws, 0, 0};
-}
-int conv_pair_tuned_shapes() { std::lock_guard<std::mutex> l(g_cache_mu); return (int)g_pair_cache.size(); }
-void conv_pair_clear_tuning() { std::lock_guard<std::mutex> l(g_cache_mu); g_pair_cache.clear(); }
-
 template <int BM, int BN, int WAVES_M, int WAVES_N>
-static int launch_pair_cfg(ConvParams& a, ConvParams& b, int ws, hipStream_t stream) {
+static int launch_pair_cfg(ConvParams& a, ConvParams& b, int family, hipStream_t stream) {
   ConvPair pp;
   pp.p[0] = a; pp.p[1] = b;
   pp.xa = conv_xblocks(a, BM);
   dim3 grid(pp.xa + conv_xblocks(b, BM), (a.Cout + BN - 1) / BN, a.ksplit > 1 ? a.ksplit : 1);
-  if (ws == 4) UDET_LAUNCH((conv_igemm_dma_pair_kernel<BM, BN, WAVES_M, WAVES_N, 3>), grid, dim3(512), 0, stream, pp);
+  if (family == FAM_DMA3) UDET_LAUNCH((conv_igemm_dma_pair_kernel<BM, BN, WAVES_M, WAVES_N, 3>), grid, dim3(512), 0, stream, pp);
   else UDET_LAUNCH((conv_igemm_dma_pair_kernel<BM, BN, WAVES_M, WAVES_N, 2>), grid, dim3(512), 0, stream, pp);
   UDET_HIP(hipGetLastError());
   if (a.ksplit > 1) {
@@ -2043,15 +1460,47 @@ static int launch_pair_cfg(ConvParams& a, ConvParams& b, int ws, hipStream_t str
   }
   return UDET_OK;
 }
-// slab capacity of a pair: both problems' K slices side by side in the launch lane's scratch
-static int pair_max_ksplit(const ConvParams& a, const ConvParams& b) {
-  const int nchunks = (max_class_taps(a) * a.Kc + 31) / 32;
-  int ks = nchunks / 2 > 64 ? 64 : nchunks / 2;
-  const size_t per_split = ((size_t)a.Mall + b.Mall) * ((a.Cout + 3) & ~3) + 64;
-  while (ks > 1 && per_split * ks > a.partial_cap) --ks;
-  return ks < 1 ? 1 : ks;
+
+// ---- the instantiated tiles: the one map from a (bm, bn) pair to a template instantiation ---------------------------------------
+// X(BM, BN, WAVES_M, WAVES_N), in the order the tuners scan them
+#define UDET_GEMM_TILES(X) X(256, 32, 4, 1) X(128, 32, 4, 1) X(128, 64, 2, 2) X(64, 64, 2, 2) X(128, 96, 4, 1) X(128, 128, 2, 2)
+#define UDET_TILE_ROW(BM, BN, WM, WN) {BM, BN},
+const int CONV_GEMM_TILES[CONV_GEMM_NTILES][2] = {UDET_GEMM_TILES(UDET_TILE_ROW)};
+#undef UDET_TILE_ROW
+bool conv_gemm_tile(int bm, int bn) {
+  for (auto& t : CONV_GEMM_TILES)
+    if (bm == t[0] && bn == t[1]) return true;
+  return false;
 }
-static int run_pair_cfg(ConvParams& a, ConvParams& b, const ConvCfg& c, hipStream_t stream) {
+static int no_tile(const char* what, const ConvCfg& c) {
+  set_error("%s: no kernel for tile %dx%d", what, c.bm, c.bn);
+  return UDET_ERR_UNSUPPORTED;
+}
+bool conv_self_staging_tile(int bm, int bn) {  // tiles conv_igemm_dma4_kernel is instantiated for (launch_cfg)
+  return ((bm == 128 || bm == 64) && (bn == 64 || bn == 128)) || (bn == 32 && (bm == 128 || bm == 256));
+}
+
+int launch_conv_gemm(ConvParams& p, const ConvCfg& c, hipStream_t stream) {
+  p.ksplit = c.ks > 1 ? c.ks : 1;
+  p.fold = 0;
+  p.tail_full = 0; p.tail_ks = 0; p.tail_prow0 = 0;
+  if (p.ksplit > 1) {
+    p.ldp = (p.Cout + 3) & ~3;
+    p.fold = c.fold && p.tickets && cfg_tiles(p, c.bm, c.bn) <= UDET_MAX_TICKETS;
+    const int Mtot = p.N * p.OHq * p.OWq, mtiles = (Mtot + c.bm - 1) / c.bm, xb = p.ncls * mtiles;
+    if (c.tail > 0 && c.tail < xb && !p.nseg && is_lds_dma(c.family) && !(reinterpret_cast<uintptr_t>(p.partial) & 15)) {
+      const long prow0 = (long)(c.tail / mtiles) * Mtot + (long)(c.tail % mtiles) * c.bm;
+      if ((size_t)((long)p.ncls * Mtot - prow0) * p.ldp * p.ksplit <= p.partial_cap) {
+        p.tail_full = c.tail; p.tail_ks = p.ksplit; p.ksplit = 1; p.fold = 0;
+      }
+    }
+  }
+#define UDET_TILE_LAUNCH(BM, BN, WM, WN) c.bm == BM && c.bn == BN ? launch_cfg<BM, BN, 32, WM, WN>(p, c.family, stream) :
+  return UDET_GEMM_TILES(UDET_TILE_LAUNCH) no_tile("conv", c);
+#undef UDET_TILE_LAUNCH
+}
+
+int launch_conv_gemm_pair(ConvParams& a, ConvParams& b, const ConvCfg& c, hipStream_t stream) {
   const int cap = pair_max_ksplit(a, b);
   const int ks = c.ks > cap ? cap : (c.ks < 1 ? 1 : c.ks);
   for (ConvParams* q : {&a, &b}) {
@@ -2065,158 +1514,11 @@ static int run_pair_cfg(ConvParams& a, ConvParams& b, const ConvCfg& c, hipStrea
     off = (off + 15) & ~(size_t)15;
     b.partial = base + off;
   }
-  int rc;
-  if (c.bm == 256 && c.bn == 32) rc = launch_pair_cfg<256, 32, 4, 1>(a, b, c.ws, stream);
-  else if (c.bm == 128 && c.bn == 32) rc = launch_pair_cfg<128, 32, 4, 1>(a, b, c.ws, stream);
-  else if (c.bm == 128 && c.bn == 64) rc = launch_pair_cfg<128, 64, 2, 2>(a, b, c.ws, stream);
-  else if (c.bm == 64 && c.bn == 64) rc = launch_pair_cfg<64, 64, 2, 2>(a, b, c.ws, stream);
-  else if (c.bm == 128 && c.bn == 96) rc = launch_pair_cfg<128, 96, 4, 1>(a, b, c.ws, stream);
-  else if (c.bm == 128 && c.bn == 128) rc = launch_pair_cfg<128, 128, 2, 2>(a, b, c.ws, stream);
-  else { set_error("conv pair: no kernel for tile %dx%d", c.bm, c.bn); rc = UDET_ERR_UNSUPPORTED; }
+#define UDET_TILE_LAUNCH(BM, BN, WM, WN) c.bm == BM && c.bn == BN ? launch_pair_cfg<BM, BN, WM, WN>(a, b, c.family, stream) :
+  const int rc = UDET_GEMM_TILES(UDET_TILE_LAUNCH) no_tile("conv pair", c);
+#undef UDET_TILE_LAUNCH
   b.partial = base;
   return rc;
-}
-static ConvCfg pair_heuristic(const ConvParams& a, const ConvParams& b) {
-  ConvCfg c = heuristic_cfg(b.Mall >= a.Mall ? b : a);
-  c.ws = 2; c.fold = 0; c.tail = 0;
-  const long tiles = cfg_tiles(a, c.bm, c.bn) + cfg_tiles(b, c.bm, c.bn);
-  c.ks = 1;
-  if (tiles < 256) {
-    const int cap = pair_max_ksplit(a, b), half = cap / 2 > 0 ? cap / 2 : 1;
-    const int ks = (int)((512 + tiles - 1) / tiles);
-    c.ks = ks > half ? half : ks;
-  }
-  return c;
-}
-static float time_calls(const std::function<int()>& fn, int reps, hipStream_t stream) {
-  static hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
-  if (fn() != UDET_OK) return 1e30f;
-  (void)hipEventRecord(e0, stream);
-  for (int r = 0; r < reps; ++r) (void)fn();
-  (void)hipEventRecord(e1, stream);
-  if (hipEventSynchronize(e1) != hipSuccess) return 1e30f;
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, e0, e1);
-  return ms / reps;
-}
-static ConvCfg tune_pair(ConvParams& a, ConvParams& b, hipStream_t stream) {
-  const int acc_a = a.accumulate, acc_b = b.accumulate;
-  a.accumulate = b.accumulate = 0;  // (see tune_cfg: repeated accumulation would grow the data)
-  // what the two cost apart, each on its own tuned configuration (launch_conv tunes a shape the first time it sees it)
-  auto apart = [&]() -> int { ConvParams x = a, y = b; int rc = launch_conv(x, stream); return rc != UDET_OK ? rc : launch_conv(y, stream); };
-  (void)apart();
-  float t_apart = time_calls(apart, 5, stream);
-  t_apart = 0.5f * (t_apart + time_calls(apart, 5, stream));
-  static const int TILES[6][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 96}, {128, 128}};
-  const int kcap = pair_max_ksplit(a, b);
-  ConvCfg best = {0, 0, 1, -1, 0, 0};
-  float best_ms = 1e30f;
-  for (auto& t : TILES) {
-    const int bm = t[0], bn = t[1];
-    if (a.Cout <= 32 && bn != 32) continue;
-    if (a.Cout > 32 && a.Cout <= 64 && bn > 64) continue;
-    if (a.Cout > 64 && a.Cout <= 96 && bn != 96 && bn != 32) continue;
-    if (a.Cout > 96 && bn < 64) continue;
-    if (a.Cout > 96 && bn == 96 && a.Cout % 96 != 0 && a.Cout <= 128) continue;
-    const long tiles = cfg_tiles(a, bm, bn) + cfg_tiles(b, bm, bn);
-    std::vector<int> kss;
-    for (int ks = 1; ks <= kcap; ks *= 2) kss.push_back(ks);
-    if (tiles < 512)
-      for (int k = 1; k <= 4; ++k) {
-        const int ks = (int)(256L * k / tiles);
-        if (ks >= 3 && ks <= kcap && (ks & (ks - 1)) != 0 && std::find(kss.begin(), kss.end(), ks) == kss.end()) kss.push_back(ks);
-      }
-    for (int ks : kss) {
-      if (ks > 1 && (tiles >= 512 || tiles * ks > 4096)) continue;
-      if (tiles * ks < 96 && ks * 2 <= kcap) continue;
-      for (int ws : {2, 4}) {
-        const ConvCfg c = {bm, bn, ks, ws, 0, 0};
-        float ms = time_calls([&]() { return run_pair_cfg(a, b, c, stream); }, 3, stream);
-        if (ms < best_ms * 1.1f) ms = 0.5f * (ms + time_calls([&]() { return run_pair_cfg(a, b, c, stream); }, 6, stream));
-        if (ms < best_ms) { best_ms = ms; best = c; }
-      }
-    }
-  }
-  // verification: each problem's output of the pair launch against its own stand-alone launch on the built-in configuration
-  bool ok = best.ws >= 0;
-  float diff = 0.f, scale = 0.f;
-  for (int which = 0; ok && which < 2; ++which) {
-    ConvParams& p = which ? b : a;
-    const int ld = (p.Cout + 3) & ~3;
-    const size_t n = (size_t)p.N * p.OH * p.OW * ld;
-    float* r0 = tune_scratch(n, 0);
-    float* r1 = tune_scratch(n, 1);
-    if (!r0 || !r1) { ok = false; break; }
-    (void)hipMemsetAsync(r0, 0, n * sizeof(float), stream);
-    (void)hipMemsetAsync(r1, 0, n * sizeof(float), stream);
-    ConvParams q = p;
-    q.ldy = ld; q.y_coff = 0; q.accumulate = 0; q.y2 = nullptr; q.uo = nullptr;
-    q.y = r0;
-    int rc = run_cfg(q, heuristic_cfg(q), stream);
-    ConvParams qa = a, qb = b;
-    ConvParams& qq = which ? qb : qa;
-    qq.ldy = ld; qq.y_coff = 0; qq.accumulate = 0; qq.y2 = nullptr; qq.uo = nullptr; qq.y = r1;
-    if (rc == UDET_OK) rc = run_pair_cfg(qa, qb, best, stream);
-    ok = rc == UDET_OK && tune_compare(r0, r1, n, stream, &diff, &scale);
-  }
-  if (best.ws >= 0 && !ok) {
-    fprintf(stderr, "[udet tune] REJECTED pair N=%d+%d %dx%d Kc=%d taps=%d cls=%d Cout=%d: %dx%d ks=%d ws=%d differs from the stand-alone "
-            "launches (max|diff| %.3e, scale %.3e); launching them apart\n", a.N, b.N, a.OHq, a.OWq, a.Kc, a.ntaps, a.ncls, a.Cout, best.bm, best.bn,
-            best.ks, best.ws, diff, scale);
-    conv_tune_note_reject();
-    best.ws = -1;
-  }
-  if (getenv("UDET_TUNE_LOG"))
-    fprintf(stderr, "[udet tune] pair N=%d+%d %dx%d Kc=%d taps=%d cls=%d Cout=%d -> %dx%d ks=%d ws=%d  %.1f us, apart %.1f us%s\n", a.N, b.N, a.OHq,
-            a.OWq, a.Kc, a.ntaps, a.ncls, a.Cout, best.bm, best.bn, best.ks, best.ws, best_ms * 1e3f, t_apart * 1e3f,
-            best_ms < t_apart * 0.97f ? "" : " (kept apart)");
-  if (!(best_ms < t_apart * 0.97f)) best.ws = -1;
-  a.accumulate = acc_a; b.accumulate = acc_b;
-  return best;
-}
-// Both problems in one launch where that is eligible and (tuned) faster; otherwise the two ordinary launches, a first.
-int launch_conv_pair(ConvParams& a, ConvParams& b, hipStream_t stream) {
-  g_last_pair = 0;
-  UDET_TRY(conv_prepare(a));
-  UDET_TRY(conv_prepare(b));
-  const bool forced_family = g_force_bm || g_force_ws >= 0 || g_force_ks >= 0;  // (a test pins a family for single launches: respect it)
-  if (g_force_pair == 0 || (forced_family && g_force_pair != 1) || !pair_compatible(a, b)) {
-    UDET_TRY(launch_conv(a, stream));
-    return launch_conv(b, stream);
-  }
-  ConvCfg c;
-  bool have = false;
-  const uint64_t key = pair_key(a, b);
-  {
-    std::lock_guard<std::mutex> l(g_cache_mu);
-    auto it = g_pair_cache.find(key);
-    if (it != g_pair_cache.end()) { c = it->second; have = true; }
-  }
-  if (have && c.ws >= 0) {  // (an entry from a file: instantiated tiles and ring depths only)
-    static const int TILES[6][2] = {{256, 32}, {128, 32}, {128, 64}, {64, 64}, {128, 96}, {128, 128}};
-    bool tile = false;
-    for (auto& t : TILES) tile = tile || (c.bm == t[0] && c.bn == t[1]);
-    if (!tile || (c.ws != 2 && c.ws != 4)) c = pair_heuristic(a, b);
-    if (c.ks < 1) c.ks = 1;
-  }
-  if (!have) {
-    if (g_tuning) {
-      c = tune_pair(a, b, stream);
-      std::lock_guard<std::mutex> l(g_cache_mu);
-      g_pair_cache[key] = c;
-    } else {
-      c = pair_heuristic(a, b);
-    }
-  }
-  if (g_force_pair == 1 && c.ws < 0) c = pair_heuristic(a, b);
-  if (c.ws < 0) {
-    UDET_TRY(launch_conv(a, stream));
-    return launch_conv(b, stream);
-  }
-  g_last_pair = 1;
-  g_last_cfg = (c.ws & 0xff) | ((c.bm & 0xfff) << 8) | ((c.ks & 0xff) << 20) | (1 << 30);
-  return run_pair_cfg(a, b, c, stream);
 }
 
 }  // namespace udet

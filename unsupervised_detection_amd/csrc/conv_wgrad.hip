@@ -5,13 +5,8 @@
 // through optimizer.compute_gradients (models/utils/loss_utils.py:18).
 #include <stdlib.h>
 
-#include <mutex>
-#include <unordered_map>
-
 #include "common.h"
-#include <algorithm>
-#include <vector>
-#include "conv_host.h"
+#include "conv_select.h"
 #include "plan.h"
 
 namespace udet {
@@ -652,19 +647,6 @@ static int g_force_wsplit = 0, g_force_wdma = -1;  // test / tool hook (libudet_
 static int g_wlast = 0;                             // configuration of the most recent launch_wgrad_T: split count | variant << 20 (3: Winograd family)
 int wgrad_last_config() { return g_wlast; }
 void wgrad_force(int nsplit, int dma) { g_force_wsplit = nsplit > 0 ? nsplit : 0; g_force_wdma = dma; }
-static std::unordered_map<uint64_t, int> g_wcache;  // problem shape -> split count | (LDS-DMA variant: 1 / 2 for a 2- / 3-stage ring) << 20
-static std::mutex g_wcache_mu;
-static int g_wtuning = 0;
-void wgrad_set_tuning(int on) { g_wtuning = on; }
-int wgrad_tuned_shapes() { std::lock_guard<std::mutex> l(g_wcache_mu); return (int)g_wcache.size(); }
-void wgrad_tune_dump(FILE* f) {
-  std::lock_guard<std::mutex> l(g_wcache_mu);
-  for (auto& kv : g_wcache) fprintf(f, "w %llu %d\n", (unsigned long long)kv.first, kv.second);
-}
-void wgrad_tune_put(unsigned long long key, int cfg) {
-  std::lock_guard<std::mutex> l(g_wcache_mu);
-  g_wcache[(uint64_t)key] = cfg;
-}
 
 template <int BM, int BN, int WM_, int WN_>
 static void wgrad_launch(const WgradParams& p, int m_tiles, int co_tiles, int nsplit, int dma, hipStream_t stream) {  // dma: 0 off, 1 / 2: 2- / 3-stage ring
@@ -679,7 +661,7 @@ static void wgrad_launch(const WgradParams& p, int m_tiles, int co_tiles, int ns
 int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
   if (conv_debug_f16_on()) p.f16 = 1;
   if (p.f16 && !(p.f16_yscale > 0.f)) p.f16_yscale = 1.f;
-  if (p.f16 && g_wtuning) p.f16_yscale = 1.f;  // (tuning data: see launch_conv)
+  if (p.f16 && wgrad_tuning_on()) p.f16_yscale = 1.f;  // (tuning data: see launch_conv)
   if (p.ldx % 4 || p.x_coff % 4 || p.ldy % 4 || p.y_coff % 4) {
     set_error("wgrad: ldx=%d x_coff=%d ldy=%d y_coff=%d must be multiples of 4", p.ldx, p.x_coff, p.ldy, p.y_coff);
     return UDET_ERR_ALIGN;
@@ -777,10 +759,9 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
       if (ns < 1) ns = 1;
       q.partial = base + (size_t)ns * bgroups * ldn;
     }
-    if (dma == 3) {}
-    else if (bn == 128) wgrad_launch<128, 128, 2, 2>(q, m_tiles, co_tiles, ns, dma, stream);
-    else if (bn == 64) wgrad_launch<128, 64, 2, 2>(q, m_tiles, co_tiles, ns, dma, stream);
-    else wgrad_launch<128, 32, 4, 1>(q, m_tiles, co_tiles, ns, dma, stream);
+    if (dma != 3 && bn == 128) wgrad_launch<128, 128, 2, 2>(q, m_tiles, co_tiles, ns, dma, stream);
+    else if (dma != 3 && bn == 64) wgrad_launch<128, 64, 2, 2>(q, m_tiles, co_tiles, ns, dma, stream);
+    else if (dma != 3) wgrad_launch<128, 32, 4, 1>(q, m_tiles, co_tiles, ns, dma, stream);
     if (fused_bn) {  // reduction + scaling + dot partials, then the one-block finish
       const int cw = g.Cout > 64 ? 128 : (g.Cout > 32 ? 64 : (g.Cout > 16 ? 32 : 16));
       const int rg = 256 / cw;
@@ -810,95 +791,16 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
     else UDET_LAUNCH(wgrad_reduce_kernel<1>, dim3(nb), dim3(256), 0, stream, q, ldn, ns);
     return UDET_OK;
   };
-  // autotuned split count (see conv_igemm.hip): kernel + reduction timed together
+  // tuned split count / variant (conv_tune.hip): kernel + reduction timed together
   {
-    const int f[] = {p.N, p.H, p.W, p.up_shift, p.Cin, p.Cout, p.ntaps, p.OH, p.OW, p.isy, p.ya ? 1 : 0, p.ldx, p.ldy, cap, dma_ok ? 1 : 0, g.swapped, p.ycls, p.f16 ? 1 : 0,
-                     p.ntaps > 0 ? p.taps[0].dy : 0, p.ntaps > 0 ? p.taps[0].dx : 0};  // (the first tap's offsets: the dilation, which the Winograd family's tile grid depends on)
-    uint64_t key = 1469598103934665603ull;
-    for (int v : f) { key ^= (uint64_t)(uint32_t)v; key *= 1099511628211ull; }
-    bool have = false;
-    {
-      std::lock_guard<std::mutex> l(g_wcache_mu);
-      auto it = g_wcache.find(key);
-      if (it != g_wcache.end()) {
-        // a cached entry may come from a file (udet_tune_load): only known variants, the slice count inside this launch's capacity
-        const int hv = nsplit, v = it->second >> 20, ns = it->second & 0xfffff;
-        if (v < 0 || v > 3 || ns < 1) nsplit = hv;
-        else nsplit = (v != 3 && ns > cap ? cap : ns) | (v << 20);  // (variant 3 is clamped to its strips / the workspace below)
-        have = true;
-      }
-    }
-    if (!have && g_wtuning) {
-      static hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (!e0) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); }
-      const int h = nsplit;
-      float best_ms = 1e30f;
-      int best = h;
-      // candidates: powers of two around the heuristic + the split counts that fill whole rounds of the 256 CUs
-      const int hc = h & 0xfffff;  // (the heuristic carries the staging variant in bit 20 in fp16 mode)
-      std::vector<int> nss = {hc / 8, hc / 4, hc / 2, hc, hc * 2, hc * 4};
-      for (int k : {1, 2, 3, 4, 6, 8}) {
-        const int ns = (int)(256L * k / tiles);
-        if (ns >= 1 && std::find(nss.begin(), nss.end(), ns) == nss.end()) nss.push_back(ns);
-      }
-      for (int dma = (p.f16 && dma_ok) ? 1 : 0; dma <= (dma_ok ? (p.f16 ? 1 : 2) : 0); ++dma)
-        for (int ns : nss) {
-          if (ns < 1 || ns > cap) continue;
-          const int cfg = ns | (dma << 20);
-          run(cfg);
-          (void)hipEventRecord(e0, stream);
-          for (int r = 0; r < 3; ++r) run(cfg);
-          (void)hipEventRecord(e1, stream);
-          if (hipEventSynchronize(e1) != hipSuccess) continue;
-          float ms = 0.f;
-          (void)hipEventElapsedTime(&ms, e0, e1);
-          if (ms < best_ms) { best_ms = ms; best = cfg; }
-        }
-      if (wino_ok) {  // the Winograd-domain family: one workgroup per CU and channel-block pair, or a few more / fewer slices
-        const int blocks = (g.Cin / 64) * (g.Cout / 64);
-        for (int wg : {256, 192, 384}) {
-          const int ns = wgrad_wino_slices(g, (wg + blocks - 1) / blocks);
-          if (ns < 1 || (size_t)ns > maxs) continue;
-          const int cfg = ns | (3 << 20);
-          run(cfg);
-          (void)hipEventRecord(e0, stream);
-          for (int r = 0; r < 3; ++r) run(cfg);
-          (void)hipEventRecord(e1, stream);
-          if (hipEventSynchronize(e1) != hipSuccess) continue;
-          float ms = 0.f;
-          (void)hipEventElapsedTime(&ms, e0, e1);
-          if (getenv("UDET_TUNE_LOG") && atoi(getenv("UDET_TUNE_LOG")) > 1)
-            fprintf(stderr, "[udet tune]   wgrad winograd %d slices: %.1f us against %.1f (N=%d %dx%d Cin=%d Cout=%d)\n", ns, ms / 3 * 1e3f, best_ms / 3 * 1e3f, p.N, p.OH,
-                    p.OW, p.Cin, p.Cout);
-          if (ms < best_ms * 0.97f) { best_ms = ms; best = cfg; }
-        }
-      }
-      nsplit = best;
-      // the winner's filter / bias gradient must equal the heuristic configuration's (see conv_igemm.hip: candidate verification)
-      if (best != h) {
-        float* r0 = tune_scratch(wsz + (size_t)p.Cout, 0);
-        bool ok = false;
-        float diff = 0.f, scale = 0.f;
-        if (r0) {
-          run(h);
-          (void)hipMemcpyAsync(r0, p.dw, wsz * sizeof(float), hipMemcpyDeviceToDevice, stream);
-          if (p.db) (void)hipMemcpyAsync(r0 + wsz, p.db, (size_t)p.Cout * sizeof(float), hipMemcpyDeviceToDevice, stream);
-          run(best);
-          ok = tune_compare(r0, p.dw, wsz, stream, &diff, &scale);
-          if (ok && p.db) ok = tune_compare(r0 + wsz, p.db, (size_t)p.Cout, stream, &diff, &scale);
-        }
-        if (!ok) {
-          fprintf(stderr, "[udet tune] REJECTED wgrad N=%d %dx%d Cin=%d Cout=%d taps=%d: nsplit=%d dma=%d differs from the heuristic "
-                  "configuration (max|diff| %.3e, scale %.3e)\n", p.N, p.OH, p.OW, p.Cin, p.Cout, p.ntaps, best & 0xfffff, best >> 20, diff, scale);
-          conv_tune_note_reject();
-          nsplit = h;
-        }
-      }
-      if (getenv("UDET_TUNE_LOG"))
-        fprintf(stderr, "[udet tune] wgrad N=%d %dx%d Cin=%d Cout=%d taps=%d -> nsplit=%d dma=%d (heuristic %d) %.1f us\n", p.N, p.OH,
-                p.OW, p.Cin, p.Cout, p.ntaps, nsplit & 0xfffff, nsplit >> 20, h & 0xfffff, best_ms / 3 * 1e3f);
-      std::lock_guard<std::mutex> l(g_wcache_mu);
-      g_wcache[key] = nsplit;
+    const uint64_t key = wgrad_key(p, cap, dma_ok, g.swapped);
+    int cached;
+    if (wgrad_cache_find(key, &cached)) {
+      // a cached entry may come from a file (udet_tune_load): only known variants, the slice count inside this launch's capacity
+      const int v = cached >> 20, ns = cached & 0xfffff;
+      if (v >= 0 && v <= 3 && ns >= 1) nsplit = (v != 3 && ns > cap ? cap : ns) | (v << 20);  // (variant 3 is clamped to its strips / the workspace below)
+    } else if (wgrad_tuning_on()) {
+      nsplit = tune_wgrad(WgradTuneInfo{p, g, tiles, cap, maxs, dma_ok, wino_ok, wsz}, nsplit, key, run, stream);
     }
   }
   if (g_force_wsplit > 0) {
