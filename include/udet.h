@@ -85,6 +85,31 @@ int udet_crop_flip_resize_ragged(const void* src, int src_is_u8, int nearest, in
 int udet_mask_stats(const float* pred_masks, const float* gt_masks, int n, int h, int w, float threshold, float gt_threshold,
                     double* stats8, void* stream);
 
+/* DAVIS contour accuracy: the four integers per frame behind the boundary F-measure of the DAVIS-2016 benchmark table.  A
+ * restatement of the published measure db_eval_boundary (Perazzi et al., CVPR 2016, and the benchmark's toolkit); the reference has
+ * no code for it (its authors ran the external toolkit).  pred_masks, gt_masks [n,h,w,1] device float32, thresholded like
+ * udet_mask_stats (seg = mask > threshold, gt = gt_mask > gt_threshold); stats8: the device doubles udet_mask_stats wrote for the
+ * same prediction, or NULL: sample i's prediction is complemented when stats8[i][0] / (4w + 4h) >= 0.6 (disambiguate_forw_back, the
+ * rule of udet_flow_to_image / udet_overlay_mask; NULL: never).  For each of the two boolean masks seg [h,w]:
+ *  - boundary map b [h,w]: with e[y,x] = seg[y,x+1], s[y,x] = seg[y+1,x], se[y,x] = seg[y+1,x+1] (0 where the shift leaves the
+ *    mask), b = (seg^e) | (seg^s) | (seg^se); then the last row b[h-1,:] = seg^e, the last column b[:,w-1] = seg^s and the corner
+ *    b[h-1,w-1] = 0.  An all-ones and an all-zeros mask both have an empty boundary.
+ *  - a boundary pixel of A matches when B has a boundary pixel at squared distance dx^2 + dy^2 <= radius^2, i.e.
+ *    A_boundary & binary_dilation(B_boundary, disk(radius)) with zeros outside the image.  The caller derives the radius from the
+ *    benchmark's bound_th: radius = bound_th >= 1 ? bound_th : ceil(bound_th * sqrt(h^2 + w^2)), default bound_th = 0.008 (4 at
+ *    192 x 384, 8 at 480 x 854, 36 at 2160 x 3840).
+ * counts4: device uint64 [n][4] = {n_fg, n_gt, fg_match, gt_match} (boundary pixels of the prediction / of the ground truth, and how
+ * many of each match the other), zeroed by the call; exact integers, independent of the order of accumulation.  Precision, recall
+ * and F are the host's: (1, 0) when n_fg = 0 < n_gt, (0, 1) when n_gt = 0 < n_fg, (1, 1) when both are 0, else fg_match / n_fg and
+ * gt_match / n_gt; F = 2pr / (p + r), 0 when p + r = 0.  bmap_pred, bmap_gt: optional device uint8 [n,h,w] (0 / 1), the two boundary
+ * maps themselves.  One launch: bit-packed rows in LDS, tiles of 32 (radius <= 16) or 64 rows x 256 columns plus the halo, no
+ * workspace.  1 <= radius <= UDET_BOUNDARY_MAX_RADIUS (one 64-column halo word per side); above: UDET_ERR_UNSUPPORTED; radius < 1, a
+ * NULL mask or counts4, n outside 1..65535 or h, w < 1: UDET_ERR_ARG.  Nothing is enqueued on an error. */
+#define UDET_BOUNDARY_MAX_RADIUS 63
+int udet_boundary_stats(const float* pred_masks, const float* gt_masks, const double* stats8, int n, int h, int w, float threshold,
+                        float gt_threshold, int radius, unsigned long long* counts4, unsigned char* bmap_pred, unsigned char* bmap_gt,
+                        void* stream);
+
 /* Post-processing stage ("next" row N4; post_processing/generate_soft_score_from_buffer.py, crf_refine.py).  The third-party
  * routines those scripts call are absent from the reference tree; each entry point names the routine it restates and the call
  * site that fixes its arguments.  Frames are small (192x384): one workgroup reductions, double accumulation like numpy float64.

@@ -3,6 +3,12 @@
   python -m unsupervised_detection_amd.cli train --dataset DAVIS2016 --root_dir ... [--flow_ckpt ...]        (train.py)
   python -m unsupervised_detection_amd.cli test_generator --root_dir ... --ckpt_file ...                    (test_generator.py)
   python -m unsupervised_detection_amd.cli test_generator_ensemble --root_dir ... --test_save_dir ...       (test_generator_ensemble.py)
+  python -m unsupervised_detection_amd.cli davis_eval --results_dir D [--mask_key pred_mask|mask|soft_mask] [--threshold T]
+                                                      [--bound_th B] [--keep_ends]                          (no reference script)
+
+test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
+davis_eval scores a folder of <sequence>/result_<k>.mat files (what test_generator --generate_visualization and the
+post-processing stages write) against their gt_mask key the same way and writes D/davis_eval.json.
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
 counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
@@ -84,11 +90,28 @@ def dataset_sources(flags, mode):
                                                    **part(flags.test_partition)))
 
 
+def parse_davis_eval_args(argv):
+    """The arguments of the davis_eval subcommand."""
+    import argparse
+    ap = argparse.ArgumentParser(prog="davis_eval")
+    ap.add_argument("--results_dir", required=True)
+    ap.add_argument("--mask_key", default="pred_mask", choices=("pred_mask", "mask", "soft_mask"))
+    ap.add_argument("--threshold", type=float, default=0.5)
+    ap.add_argument("--bound_th", type=float, default=0.008)
+    ap.add_argument("--keep_ends", action="store_true", help="score the first and last frame of a sequence too")
+    return ap.parse_args(argv)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] not in ("train", "test_generator", "test_generator_ensemble"):
+    if not argv or argv[0] not in ("train", "test_generator", "test_generator_ensemble", "davis_eval"):
         print(__doc__)
         return 2
+    if argv[0] == "davis_eval":
+        a = parse_davis_eval_args(argv[1:])
+        from .evaluation import evaluate_results_dir
+        evaluate_results_dir(a.results_dir, a.mask_key, a.threshold, a.bound_th, skip_ends=not a.keep_ends)
+        return 0
     from .config import parse_flags
     from .learner import AdversarialLearner
     cmd, flags = argv[0], parse_flags(argv[1:])
@@ -102,7 +125,8 @@ def main(argv=None):
         _sources(flags, "test")  # --ckpt_file is restored by the learner (every network the checkpoint holds)
         learner.setup_inference(flags, aug_test=False)
         from .evaluation import evaluate_masks
-        evaluate_masks(learner, save_dir=flags.test_save_dir if flags.generate_visualization else None)
+        evaluate_masks(learner, save_dir=flags.test_save_dir if flags.generate_visualization else None,
+                       davis_metrics=flags.davis_metrics)
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

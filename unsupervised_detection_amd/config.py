@@ -25,6 +25,9 @@ _DEFS = [
     # not a reference flag: directory of the training summaries (visualize.SummaryWriter: scalars.jsonl, images/, histograms/ every
     # summary_freq steps -- the reference writes TensorBoard events into checkpoint_dir); "" = off
     ("summary_dir", str, ""),
+    # not a reference flag: test_generator also reports the DAVIS-2016 benchmark measures (J and F: mean, recall, decay), which the
+    # reference leaves to the external DAVIS toolkit
+    ("davis_metrics", bool, False),
 ]
 
 

@@ -95,6 +95,21 @@ int udet_mask_stats(const float* pred_masks, const float* gt_masks, int n, int h
   return launch_mask_stats(pred_masks, gt_masks, n, h, w, threshold, gt_threshold, stats8, (hipStream_t)stream);
 }
 
+int udet_boundary_stats(const float* pred_masks, const float* gt_masks, const double* stats8, int n, int h, int w, float threshold,
+                        float gt_threshold, int radius, unsigned long long* counts4, unsigned char* bmap_pred, unsigned char* bmap_gt,
+                        void* stream) {
+  if (n < 1 || n > 65535 || h < 1 || w < 1 || radius < 1 || !pred_masks || !gt_masks || !counts4) {
+    set_error("boundary_stats: bad argument (n = %d in 1..65535, h = %d, w = %d, radius = %d >= 1, non-null masks and counts)", n, h, w, radius);
+    return UDET_ERR_ARG;
+  }
+  if (radius > UDET_BOUNDARY_MAX_RADIUS) {
+    set_error("boundary_stats: radius %d is above the supported maximum %d", radius, UDET_BOUNDARY_MAX_RADIUS);
+    return UDET_ERR_UNSUPPORTED;
+  }
+  return launch_boundary_stats(pred_masks, gt_masks, stats8, n, h, w, threshold, gt_threshold, radius, counts4, bmap_pred, bmap_gt,
+                               (hipStream_t)stream);
+}
+
 size_t udet_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int kh, int kw, int upsample2x) {
   const int kc = round_up(cin > cout ? cin : cout, 8), ldw = round_up(cin > cout ? cin : cout, 4);
   const size_t pix_in = (size_t)n * h * w, pix_out = pix_in * (upsample2x ? 4 : 1);

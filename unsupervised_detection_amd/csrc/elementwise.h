@@ -39,6 +39,10 @@ int launch_crop_flip_resize_ragged(const void* src, int src_u8, int nearest, int
                                    const int* prm, float* dst, int OH, int OW, float div, float add, hipStream_t s);
 int launch_mask_stats(const float* pred, const float* gt, int N, int H, int W, float threshold, float gt_threshold, double* out,
                       hipStream_t s);
+// metrics.hip: udet_boundary_stats (arguments already checked)
+int launch_boundary_stats(const float* pred, const float* gt, const double* stats8, int N, int H, int W, float threshold,
+                          float gt_threshold, int radius, unsigned long long* counts4, unsigned char* bmap_pred,
+                          unsigned char* bmap_gt, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
 int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet
