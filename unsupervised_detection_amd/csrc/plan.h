@@ -60,7 +60,7 @@ struct Layer {
   // corner} back to back (forward: wupb_off, backward-data: wupbT_off), segments and device tap tables built by plan_build
   // BUFFER CONTRACT: for a upb layer `x` (rec.r{k+1}, the up-sampled tensor) is NOT written by the forward; it is valid only between the
   // rebuild inside rec_backward (recover-loss pass, filter-gradient lane) and the end of that level's filter gradient.  Debug dumps of it
-  // after a forward show the previous step's data; run_fwd refuses the generic path for these layers.
+  // after a forward show the previous step's data; run_fwd always takes the ringed low-resolution form for these layers.
   bool upb = false;
   bool upb_bwd = false;      // backward-data too (the deepest level has too few low-resolution pixels to fill the chip: forward only)
   bool upb_split = false;    // forward: interior as an ordinary four-class launch + the border segments (see run_fwd_upb)
@@ -81,6 +81,38 @@ struct Layer {
   bool col2im = false;
   int ldz = 0, zbuf = -1;
   size_t wz_off = 0;
+  // recover encoders: the input is a concat slab segment that already holds the decoder's gradient when the backward pass gets here
+  // (the layer's backward-data launch accumulates) / encoder A: the output is a skip tensor the decoder reads, fanned out from the B
+  // images to the samples of the other calls (plan_step.hip: share_enc_a_output)
+  bool x_in_slab = false, y_fanned_out = false;
+  std::string pair_name;  // encoder A: profiling name of the launch that carries this layer and its encoder-B twin
+};
+
+// Everything the step's walk (plan_step.hip) addresses by name, resolved ONCE by plan_build (resolve_names; a miss fails the build):
+// layers as indices into Plan::pwc / Plan::rec, buffers as buffer ids, arrays indexed by the pyramid / decoder level itself.
+struct Resolved {
+  struct {
+    int pyr[7][3];                                       // levels 1-6: conv{l}a, aa, b
+    int est[7][5], flow[7], ctx[7][7];                   // levels 2-6
+    int up_feat[7], up_flow[7];                          // levels 3-6
+  } pwc;
+  struct {
+    int enc[2][9];                                       // [encoder a / b][conv1 .. conv6]
+    int deconv[6], flow[6], upflow[6];                   // levels 1-5 (upflow: 1-4)
+  } rec;
+  int image, flow, mask, pred, image_next, flow_next, d_mask, flow_full;
+  int pwc_x8, pwc_rflow2, pwc_c[7], pwc_slab[7];         // levels 2-6
+  int gen_in, gen_a17, gen_d[18], gen_u[18];             // gen.d{k} / gen.u{k}, k = 1 .. 17
+  int rec_imgin, rec_fin, rec_conv6, rec_concat[6], rec_r[7], rec_rf[6], rec_flow[6];  // rec.r{2..6}, rec.rf{2..5}
+  // One family of recover-side gradient buffers ("rec.d.*" with "d.pred": recover-loss pass; "rec.e.*", "e.pred": generator-loss pass)
+  // and its dU mirrors ("rec.ud.*" / "rec.ue.*": gradient * act'(activation))
+  struct Grad {
+    int pred, fin, conv6, u_conv6;
+    int flow[6], concat[6], u_concat[6], r[7], rf[6];
+    int p[6];                                            // ringed gradient grid rec.<f>.p{2..5}; -1: the level's backward-data pass keeps the up-sampled form
+    int enc_du[2][9];                                    // encoder layer: dU of its output
+    int enc_dx[2][9], enc_ux[2][9];                      // ... gradient / dU of its input (conv2 on)
+  } grad[2];                                             // 0: "d", 1: "e"
 };
 
 struct Config {
@@ -157,9 +189,10 @@ struct Plan {
   long ovf_skipped = 0;          // optimizer updates dropped so far
   int ovf_report_values = 0, ovf_report_nets = 0;  // dropped updates no call has reported yet (non-finite values, network bits)
   bool pwc_packed = false;
+  Resolved R;
   int add_buf(const std::string& name, int n, int h, int w, int ld);
   const Buf& buf(int id) const { return bufs[id]; }
-  int bid(const std::string& name) const;
+  int bid(const std::string& name) const;  // -1: no such buffer (plan_build and the by-name views only; the step uses Plan::R)
 };
 
 // capacity (entries) of a network's device PackJob table; plan_init_workspace refuses to copy more

@@ -255,6 +255,88 @@ static void build_upb_launches(Layer& L, int h, int w) {
   B.seg_tap[B.nseg] = (int)B.taps.size();
 }
 
+// ------------------------------------------------------- name resolution ----
+// The one place the step's names are looked up: a miss is reported once (the first), plan_build then fails.
+namespace {
+struct Lookup {
+  const Plan* P;
+  bool ok = true;
+  int miss(const char* kind, const std::string& name) {
+    if (ok) set_error("plan_build: no %s '%s'", kind, name.c_str());
+    ok = false;
+    return -1;
+  }
+  int buf(const std::string& name) {
+    const int id = P->bid(name);
+    return id >= 0 ? id : miss("buffer", name);
+  }
+  int layer(const std::vector<Layer>& v, const std::string& name) {
+    for (size_t i = 0; i < v.size(); ++i)
+      if (v[i].name == name) return (int)i;
+    return miss("layer", name);
+  }
+};
+}  // namespace
+
+static bool resolve_names(Plan* P) {
+  Lookup f{P};
+  Resolved& R = P->R;
+  memset(&R, 0xff, sizeof(R));  // (every index the loops below leave out: -1)
+  for (int l = 1; l <= 6; ++l) {
+    const char* suf[3] = {"a", "aa", "b"};
+    for (int j = 0; j < 3; ++j) R.pwc.pyr[l][j] = f.layer(P->pwc, S("pwcnet/featpyr/conv%d%s", l, suf[j]));
+  }
+  for (int l = 2; l <= 6; ++l) {
+    for (int i = 0; i < 5; ++i) R.pwc.est[l][i] = f.layer(P->pwc, S("pwcnet/predict_flow/conv%d_%d", l, i));
+    R.pwc.flow[l] = f.layer(P->pwc, S("pwcnet/predict_flow/flow%d", l));
+    for (int i = 0; i < 7; ++i) R.pwc.ctx[l][i] = f.layer(P->pwc, S("pwcnet/ctxt/dc_conv%d%d", l, i + 1));
+    if (l != 2) {
+      R.pwc.up_feat[l] = f.layer(P->pwc, S("pwcnet/upsample/up_feat%d", l));
+      R.pwc.up_flow[l] = f.layer(P->pwc, S("pwcnet/upsample/up_flow%d", l));
+    }
+    R.pwc_c[l] = f.buf(S("pwc.c%d", l));
+    R.pwc_slab[l] = f.buf(S("pwc.slab%d", l));
+  }
+  R.pwc_x8 = f.buf("pwc.x8"); R.pwc_rflow2 = f.buf("pwc.rflow2"); R.flow_full = f.buf("flow_full");
+  R.image = f.buf("image"); R.flow = f.buf("flow"); R.mask = f.buf("mask"); R.pred = f.buf("pred");
+  R.image_next = f.buf("image.next"); R.flow_next = f.buf("flow.next"); R.d_mask = f.buf("d.mask");
+  R.gen_in = f.buf("gen.in"); R.gen_a17 = f.buf("gen.a17");
+  for (int k = 1; k <= 17; ++k) { R.gen_d[k] = f.buf(S("gen.d%d", k)); R.gen_u[k] = f.buf(S("gen.u%d", k)); }
+  R.rec_imgin = f.buf("rec.imgin"); R.rec_fin = f.buf("rec.fin"); R.rec_conv6 = f.buf("rec.conv6");
+  for (int e = 0; e < 2; ++e)
+    for (int i = 0; i < 9; ++i) R.rec.enc[e][i] = f.layer(P->rec, S("%c%s", e ? 'b' : 'a', ENC[i].suf));
+  for (int k = 1; k <= 5; ++k) {
+    R.rec.deconv[k] = f.layer(P->rec, S("deconv%d", k));
+    R.rec.flow[k] = f.layer(P->rec, S("flow%d", k));
+    if (k < 5) R.rec.upflow[k] = f.layer(P->rec, S("upflow%d", k));
+    R.rec_concat[k] = f.buf(S("rec.concat%d", k));
+    R.rec_flow[k] = f.buf(S("rec.flow%d", k));
+    R.rec_r[k + 1] = f.buf(S("rec.r%d", k + 1));
+    if (k < 5) R.rec_rf[k + 1] = f.buf(S("rec.rf%d", k + 1));
+  }
+  // the tensor an encoder conv writes, as its gradient buffers are named (the slab of a skip level, or the encoder's own intermediate)
+  static const char* const ENC_OUT[9] = {"concat1", "concat2", "%c3", "concat3", "%c4", "concat4", "%c5", "concat5", "conv6"};
+  for (int g = 0; g < 2; ++g) {
+    Resolved::Grad& G = R.grad[g];
+    const char fam = g ? 'e' : 'd';
+    auto D = [&](const std::string& n) { return f.buf(S("rec.%c.", fam) + n); };
+    auto U = [&](const std::string& n) { return f.buf(S("rec.u%c.", fam) + n); };
+    G.pred = f.buf(S("%c.pred", fam)); G.fin = D("fin"); G.conv6 = D("conv6"); G.u_conv6 = U("conv6");
+    for (int k = 1; k <= 5; ++k) {
+      G.flow[k] = D(S("flow%d", k)); G.concat[k] = D(S("concat%d", k)); G.u_concat[k] = U(S("concat%d", k));
+      G.r[k + 1] = D(S("r%d", k + 1));
+      if (k < 5) G.rf[k + 1] = D(S("rf%d", k + 1));
+      if (k < 5 && f.ok && P->rec[R.rec.deconv[k]].upb_bwd) G.p[k + 1] = D(S("p%d", k + 1));
+    }
+    for (int e = 0; e < 2; ++e)
+      for (int i = 0; i < 9; ++i) {
+        G.enc_du[e][i] = U(S(ENC_OUT[i], e ? 'b' : 'a'));
+        if (i > 0) { G.enc_dx[e][i] = D(S(ENC_OUT[i - 1], e ? 'b' : 'a')); G.enc_ux[e][i] = U(S(ENC_OUT[i - 1], e ? 'b' : 'a')); }
+      }
+  }
+  return f.ok;
+}
+
 Plan* plan_build(const Config& cfg) {
   if (cfg.batch > 16) {
     set_error("plan: batch %d > 16 per GPU is not laid out (reduction scratch); shard over more ranks", cfg.batch);
@@ -454,6 +536,12 @@ Plan* plan_build(const Config& cfg) {
                            ENC[i].s, 1, ACT_LEAKY, 0.2f);
         L.x = io[i].x; L.x_coff = io[i].xc; L.y = io[i].y; L.y_coff = io[i].yc;
         L.H = hs[io[i].lvl_in]; L.W = wsz[io[i].lvl_in];
+        for (int k = 1; k <= 5; ++k) {
+          if (L.x == concat[k]) L.x_in_slab = true;
+          if (e == 0 && L.y == concat[k]) L.y_fanned_out = true;
+        }
+        if (e == 0 && L.y == conv6) L.y_fanned_out = true;
+        if (e == 0) L.pair_name = nm + "+b" + ENC[i].suf;
         P->rec.push_back(L);
       }
     }
@@ -625,6 +713,10 @@ Plan* plan_build(const Config& cfg) {
   for (auto& v : views) {
     const int id = P->add_buf(v.n, v.a, 1, 1, v.d);
     P->bufs[id].off = P->small_off + v.o;
+  }
+  if (!resolve_names(P)) {  // (the error text names the buffer or layer)
+    delete P;
+    return nullptr;
   }
   return P;
 }
