@@ -110,6 +110,33 @@ int udet_boundary_stats(const float* pred_masks, const float* gt_masks, const do
                         float gt_threshold, int radius, unsigned long long* counts4, unsigned char* bmap_pred, unsigned char* bmap_gt,
                         void* stream);
 
+/* Native-resolution restore of a batch of masks (post_processing/crf_refine.py:84-97 run_crf_original_resolution,
+ * post_processing/post_processing.py:32-46): what the benchmarks score -- every frame at its own size, the strip outside the central
+ * crop counted as background.  masks: n soft masks [n,mh,mw] device float32, all of one size.  data: packed device uint8, sample i =
+ * H_i x W_i bytes at byte offset offsets[i] (device int64 [n]).  tables12: device int32 [n][12] =
+ *   {y0, x0, h, w, H, W,  hk, hb, hks,  vk, vb, vks}
+ * the box of the patch inside the frame (restore_box: h = int(H * crop), w = int(W * crop), y0 = (H - h) / 2, x0 = (W - w) / 2; the
+ * whole frame when crop >= 1), the frame's size, and for the horizontal (mw -> w) and the vertical (mh -> h) pass the int32 offsets
+ * into coef of that pass's Pillow coefficients kk [out][ks] (22-bit fixed point) and bounds [out][2] = (first tap, taps), computed
+ * by the host exactly as Pillow's Resample.c does (BILINEAR); hk / vk = -1: the pass's output length equals its input length and the
+ * pass is skipped (not run with identity weights).  Per sample:
+ *   byte = uint8(clip((v - mn) * (255 / cscale), 0, 255) + 0.5) in double, mn / mx over the WHOLE mask, cscale = mx - mn or 1 if 0
+ *          (scipy.misc.bytescale as udet_post_bytescale defines it);
+ *   horizontal pass, uint8 intermediate, vertical pass, each ss = 1 << 21; ss += pixel * kk; clip8(ss >> 22) (udet_post_resample_u8);
+ *   the patch lands at (y0, x0), every other byte of the sample is 0; amax[i] (device int32 [n]) = the largest byte of the patch;
+ *   binary (optional, NULL: off): packed like data, 1 where (double)byte / (amax + 1e-8) > threshold (a real float64 division,
+ *          crf_refine.py:94), else 0.  A constant mask restores to zeros, amax = 0, binary zeros.
+ * At most three launches whatever n is (min / max partials; bytescale + both passes + placement on 64 x 16 tiles of each frame,
+ * integer atomicMax into amax; the binary mask), many workgroups per sample.  max_h / max_w: the largest H_i / W_i (sizes the grid).
+ * workspace: udet_restore_workspace_bytes(n) bytes, 4-byte aligned.  amax is zeroed by the call.  Only the scalars and pointers
+ * are checked here (UDET_ERR_ARG; nothing is enqueued on an error): the tables are device memory, and every index the kernels form is
+ * bounded by them -- offsets inside data, boxes inside their frames, coefficient windows inside coef and taps inside the mask must
+ * hold (native_results.check_restore_tables validates them on the host before every launch). */
+size_t udet_restore_workspace_bytes(int n);
+int udet_restore_masks_ragged(const float* masks, int n, int mh, int mw, const long long* offsets, const int* tables12, const int* coef,
+                              int max_h, int max_w, unsigned char* data, int* amax, unsigned char* binary, double threshold,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* Post-processing stage ("next" row N4; post_processing/generate_soft_score_from_buffer.py, crf_refine.py).  The third-party
  * routines those scripts call are absent from the reference tree; each entry point names the routine it restates and the call
  * site that fixes its arguments.  Frames are small (192x384): one workgroup reductions, double accumulation like numpy float64.

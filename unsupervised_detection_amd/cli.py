@@ -5,10 +5,17 @@
   python -m unsupervised_detection_amd.cli test_generator_ensemble --root_dir ... --test_save_dir ...       (test_generator_ensemble.py)
   python -m unsupervised_detection_amd.cli davis_eval --results_dir D [--mask_key pred_mask|mask|soft_mask] [--threshold T]
                                                       [--bound_th B] [--keep_ends]                          (no reference script)
+  python -m unsupervised_detection_amd.cli restore_results --results_dir D --out_dir O --dataset ... --root_dir ...
+                                                      [--test_partition val] [--test_temporal_shift 1] [--mask_key pred_mask|mask|soft_mask]
+                                                      [--crop 0.9] [--threshold 0.5] [--keep_ends]         (crf_refine.py:84-97)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
 davis_eval scores a folder of <sequence>/result_<k>.mat files (what test_generator --generate_visualization and the
-post-processing stages write) against their gt_mask key the same way and writes D/davis_eval.json.
+post-processing stages write) against their gt_mask key the same way and writes D/davis_eval.json.  restore_results brings such a
+folder back to every frame's own size (the mask is the central --crop of the frame, the strip around it background), scores it there
+against the untouched annotations and writes O/<sequence>/<frame>.png (0 / 255, the DAVIS tools' layout), O/<sequence>/result_<k>.mat
+and O/native_eval.json; test_generator --native_resolution (with --generate_visualization --test_save_dir D) does the same for the
+masks it has just saved, into D/native.
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
 counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
@@ -102,11 +109,48 @@ def parse_davis_eval_args(argv):
     return ap.parse_args(argv)
 
 
+def parse_restore_results_args(argv):
+    """The arguments of the restore_results subcommand: its own and, for the reader of --dataset, the flags of common_flags.py."""
+    import argparse
+    from .config import default_flags
+    ap = argparse.ArgumentParser(prog="restore_results")
+    ap.add_argument("--results_dir", required=True)
+    ap.add_argument("--out_dir", required=True)
+    ap.add_argument("--dataset", default="DAVIS2016", choices=("DAVIS2016", "FBMS", "SEGTRACK"))
+    ap.add_argument("--root_dir", required=True)
+    ap.add_argument("--test_partition", default="val")
+    ap.add_argument("--test_temporal_shift", type=int, default=1)
+    ap.add_argument("--mask_key", default="mask", choices=("pred_mask", "mask", "soft_mask"))
+    ap.add_argument("--crop", type=float, default=0.9)
+    ap.add_argument("--threshold", type=float, default=0.5)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--keep_ends", action="store_true", help="score the first and last frame of a sequence too")
+    a = ap.parse_args(argv)
+    flags = default_flags()
+    for k, v in vars(a).items():
+        setattr(flags, k, v)
+    return flags
+
+
+def check_native_flags(flags):
+    """--native_resolution works on the masks test_generator saves: it needs --generate_visualization --test_save_dir and a dataset."""
+    if getattr(flags, "native_resolution", False) and not (flags.generate_visualization and flags.test_save_dir):
+        raise SystemExit("--native_resolution requires --generate_visualization --test_save_dir D")
+    if getattr(flags, "native_resolution", False) and getattr(flags, "synthetic", False):
+        raise SystemExit("--native_resolution needs the annotations of a dataset (not --synthetic)")
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    if not argv or argv[0] not in ("train", "test_generator", "test_generator_ensemble", "davis_eval"):
+    if not argv or argv[0] not in ("train", "test_generator", "test_generator_ensemble", "davis_eval", "restore_results"):
         print(__doc__)
         return 2
+    if argv[0] == "restore_results":
+        a = parse_restore_results_args(argv[1:])
+        from .native_results import frame_lists_from_reader, restore_results_dir
+        restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
+                            batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends)
+        return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
         from .evaluation import evaluate_results_dir
@@ -115,6 +159,8 @@ def main(argv=None):
     from .config import parse_flags
     from .learner import AdversarialLearner
     cmd, flags = argv[0], parse_flags(argv[1:])
+    if cmd == "test_generator":
+        check_native_flags(flags)
     np.random.seed(8964)  # train.py:18
     learner = AdversarialLearner()
     if cmd == "train":
@@ -127,6 +173,10 @@ def main(argv=None):
         from .evaluation import evaluate_masks
         evaluate_masks(learner, save_dir=flags.test_save_dir if flags.generate_visualization else None,
                        davis_metrics=flags.davis_metrics)
+        if flags.native_resolution:
+            from .native_results import frame_lists_from_reader, restore_results_dir
+            restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
+                                mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset)
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

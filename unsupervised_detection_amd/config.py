@@ -28,6 +28,9 @@ _DEFS = [
     # not a reference flag: test_generator also reports the DAVIS-2016 benchmark measures (J and F: mean, recall, decay), which the
     # reference leaves to the external DAVIS toolkit
     ("davis_metrics", bool, False),
+    # not a reference flag: after test_generator --generate_visualization --test_save_dir D, restore the saved masks to every frame's
+    # own size (test_crop pasted into a zero canvas), score them there and export them under D/native (native_results.py)
+    ("native_resolution", bool, False),
 ]
 
 

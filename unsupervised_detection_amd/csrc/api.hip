@@ -110,6 +110,28 @@ int udet_boundary_stats(const float* pred_masks, const float* gt_masks, const do
                                (hipStream_t)stream);
 }
 
+size_t udet_restore_workspace_bytes(int n) { return n < 1 ? 0 : restore_workspace_bytes(n); }
+int udet_restore_masks_ragged(const float* masks, int n, int mh, int mw, const long long* offsets, const int* tables12, const int* coef,
+                              int max_h, int max_w, unsigned char* data, int* amax, unsigned char* binary, double threshold,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (n < 1 || n > 65535 || mh < 1 || mw < 1 || (long)mh * mw > 0x7fffffffL || max_h < 1 || max_w < 1 || !masks || !offsets || !tables12 ||
+      !coef || !data || !amax) {
+    set_error("restore_masks_ragged: bad argument (n = %d in 1..65535, mask %d x %d, largest frame %d x %d, non-null masks, tables, data and amax)",
+              n, mh, mw, max_h, max_w);
+    return UDET_ERR_ARG;
+  }
+  if (binary && (!(threshold >= 0.0) || isinf(threshold) || binary == data)) {
+    set_error("restore_masks_ragged: the binary mask needs a finite threshold >= 0 and a buffer of its own");
+    return UDET_ERR_ARG;
+  }
+  if (!workspace || workspace_bytes < restore_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 3)) {
+    set_error("restore_masks_ragged: workspace needs %zu bytes, 4-byte aligned", restore_workspace_bytes(n));
+    return UDET_ERR_ARG;
+  }
+  return launch_restore_masks_ragged(masks, n, mh, mw, offsets, tables12, coef, max_h, max_w, data, amax, binary, threshold, workspace,
+                                     (hipStream_t)stream);
+}
+
 size_t udet_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int kh, int kw, int upsample2x) {
   const int kc = round_up(cin > cout ? cin : cout, 8), ldw = round_up(cin > cout ? cin : cout, 4);
   const size_t pix_in = (size_t)n * h * w, pix_out = pix_in * (upsample2x ? 4 : 1);

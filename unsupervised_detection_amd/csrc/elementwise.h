@@ -43,6 +43,11 @@ int launch_mask_stats(const float* pred, const float* gt, int N, int H, int W, f
 int launch_boundary_stats(const float* pred, const float* gt, const double* stats8, int N, int H, int W, float threshold,
                           float gt_threshold, int radius, unsigned long long* counts4, unsigned char* bmap_pred,
                           unsigned char* bmap_gt, hipStream_t s);
+// restore.hip: udet_restore_masks_ragged (arguments already checked)
+size_t restore_workspace_bytes(int n);
+int launch_restore_masks_ragged(const float* masks, int n, int mh, int mw, const long long* offsets, const int* tab, const int* coef,
+                                int max_h, int max_w, unsigned char* out, int* amax, unsigned char* binary, double threshold,
+                                void* workspace, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
 int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet

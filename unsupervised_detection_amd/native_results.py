@@ -1,0 +1,392 @@
+"""Output stage at native resolution: restore a batch of masks to each frame's own size, score them there and export them.
+
+Every mask the networks produce is img_height x img_width (192 x 384) and covers the central test_crop (0.9) of the frame; the
+benchmarks (DAVIS-2016, FBMS-59, SegTrackV2) are scored on the full frame at each frame's own size with the strip outside the crop
+counted as background.  The reference has that step in post_processing/crf_refine.py:84-97 (run_crf_original_resolution) and
+post_processing/post_processing.py:32-46:
+
+    soft = imresize(soft, (int(0.9 H), int(0.9 W)));  soft = soft / (amax(soft) + 1e-8);  zeros((H, W))[dh:dh+h, dw:dw+w] = soft
+
+  restore_box(H, W, crop)                       the patch's box (y0, x0, h, w) inside an H x W frame
+  build_restore_tables / check_restore_tables   the host tables of udet_restore_masks_ragged and their validation (no GPU needed)
+  restore_masks(masks, native_hw, ...)          one call of the ragged kernel (csrc/restore.hip) -> RestoredMasks
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore + J / F + <sequence>/<frame>.png, result_<k>.mat, native_eval.json
+  frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order
+
+scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  Not here: the full-resolution
+CRF (sxy = 60) and the "best connected candidate" the reference only mentions in a comment."""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from ._ffi import c_i, c_p, c_sz, check, lib
+from .post_processing import _pil_coeffs_host
+
+lib.udet_restore_workspace_bytes.restype = c_sz
+lib.udet_restore_workspace_bytes.argtypes = [c_i]
+lib.udet_restore_masks_ragged.restype = c_i
+lib.udet_restore_masks_ragged.argtypes = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, c_p, c_sz, c_p]
+
+TAB = 12  # int32 per sample: y0 x0 h w H W | hk hb hks | vk vb vks   (include/udet.h)
+
+
+def restore_box(H, W, crop):
+    """(y0, x0, h, w) of the restored patch in an H x W frame: h = int(H * crop), w = int(W * crop) (Python float product,
+    truncated, crf_refine.py:91-92), y0 = (H - h) // 2, x0 = (W - w) // 2; crop >= 1: the whole frame.  h, w >= 1."""
+    H, W, crop = int(H), int(W), float(crop)
+    if H < 1 or W < 1 or not crop > 0:
+        raise ValueError("restore_box: frame {} x {} and crop {} must be positive".format(H, W, crop))
+    if crop >= 1:
+        return 0, 0, H, W
+    h, w = int(H * crop), int(W * crop)
+    if h < 1 or w < 1:
+        raise ValueError("restore_box: the crop {} of a {} x {} frame is empty".format(crop, H, W))
+    return (H - h) // 2, (W - w) // 2, h, w
+
+
+_host_coeffs = {}
+
+
+def _coeffs(in_size, out_size):
+    key = (int(in_size), int(out_size))
+    if key not in _host_coeffs:
+        _host_coeffs[key] = _pil_coeffs_host(*key)
+    return _host_coeffs[key]
+
+
+def build_restore_tables(native_hw, mh, mw, crop=0.9, offsets=None):
+    """Host tables of udet_restore_masks_ragged for masks of mh x mw restored into frames native_hw [n,2]: (offsets int64 [n],
+    tab int32 [n,12], coef int32 [m]).  offsets default to the packed layout (sample i right after sample i-1).  One coefficient
+    table (kk [out][ks] then bounds [out][2]) per distinct (in, out) length, concatenated in coef; a pass whose output length
+    equals its input length gets index -1 (skipped)."""
+    hw = np.asarray(native_hw, dtype=np.int64).reshape(-1, 2)
+    n = len(hw)
+    if n < 1:
+        raise ValueError("restore needs at least one sample")
+    if (hw < 1).any() or (hw[:, 0] * hw[:, 1] > np.iinfo(np.int32).max).any():
+        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
+    if offsets is None:
+        off = np.zeros(n, np.int64)
+        off[1:] = np.cumsum(hw[:, 0] * hw[:, 1])[:-1]
+    else:
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        if len(off) != n:
+            raise ValueError("one offset per sample")
+    tab = np.zeros((n, TAB), np.int32)
+    chunks, where, pos = [], {}, 0
+
+    def table(in_size, out_size):
+        nonlocal pos
+        if in_size == out_size:
+            return -1, -1, 0
+        key = (in_size, out_size)
+        if key not in where:
+            kk, bounds, ks = _coeffs(in_size, out_size)
+            where[key] = (pos, pos + kk.size, ks)
+            chunks.extend([kk.reshape(-1), bounds.reshape(-1)])
+            pos += kk.size + bounds.size
+        return where[key]
+    for i, (H, W) in enumerate(hw):
+        y0, x0, h, w = restore_box(H, W, crop)
+        tab[i] = (y0, x0, h, w, H, W) + tuple(table(int(mw), w)) + tuple(table(int(mh), h))
+    coef = np.concatenate(chunks).astype(np.int32) if chunks else np.zeros(1, np.int32)
+    return off, tab, np.ascontiguousarray(coef)
+
+
+def check_restore_tables(offsets, tab, coef, numel, mh, mw):
+    """Host validation of the device tables of udet_restore_masks_ragged (its C entry point does not read device memory): raises
+    ValueError on a sample outside the output buffer of `numel` bytes, overlapping samples, a box outside its own frame, a
+    coefficient window outside coef, or a tap outside the mask.  Returns the three arrays in the dtypes the kernel reads."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    tab = np.ascontiguousarray(np.asarray(tab, dtype=np.int32).reshape(-1, TAB))
+    coef = np.ascontiguousarray(np.asarray(coef, dtype=np.int32).reshape(-1))
+    n = len(off)
+    if n < 1 or len(tab) != n or mh < 1 or mw < 1:
+        raise ValueError("restore needs at least one sample, one table row per sample and a mask of at least 1x1")
+    t = tab.astype(np.int64)
+    y0, x0, h, w, H, W = (t[:, k] for k in range(6))
+    if (H < 1).any() or (W < 1).any() or (H * W > np.iinfo(np.int32).max).any():
+        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
+    if (off < 0).any() or (off + H * W > numel).any():
+        raise ValueError("sample outside the output buffer (offset + H*W past its end)")
+    order = np.argsort(off, kind="stable")
+    if (off[order][1:] < (off + H * W)[order][:-1]).any():
+        raise ValueError("samples overlap in the output buffer")
+    if (y0 < 0).any() or (x0 < 0).any() or (h < 1).any() or (w < 1).any() or (y0 + h > H).any() or (x0 + w > W).any():
+        raise ValueError("box outside its own frame")
+    seen = set()
+    for i in range(n):
+        for name, (k0, b0, ks), n_in, n_out in (("horizontal", t[i, 6:9], mw, w[i]), ("vertical", t[i, 9:12], mh, h[i])):
+            key = (int(k0), int(b0), int(ks), int(n_in), int(n_out))
+            if key in seen:
+                continue
+            seen.add(key)
+            if (k0 < 0) != (b0 < 0):
+                raise ValueError("sample {}: {} coefficient index outside the coefficient buffer".format(i, name))
+            if k0 < 0:
+                if n_in != n_out:
+                    raise ValueError("sample {}: the {} pass {} -> {} cannot be skipped".format(i, name, n_in, n_out))
+                continue
+            if ks < 1 or k0 + n_out * ks > len(coef) or b0 + 2 * n_out > len(coef):
+                raise ValueError("sample {}: {} coefficient index outside the coefficient buffer".format(i, name))
+            b = coef[b0:b0 + 2 * n_out].reshape(-1, 2).astype(np.int64)
+            if (b[:, 0] < 0).any() or (b[:, 1] < 1).any() or (b[:, 1] > ks).any() or (b.sum(1) > n_in).any():
+                raise ValueError("sample {}: a {} tap lies outside the mask or the coefficient row".format(i, name))
+            if (np.diff(b[:, 0]) < 0).any() or (np.diff(b.sum(1)) < 0).any():
+                raise ValueError("sample {}: {} tap windows must not move backwards".format(i, name))
+    return off, tab, coef
+
+
+class RestoredMasks(object):
+    """Result of restore_masks: data (packed uint8, device), binary (same layout, 0 / 1, or None), host offsets [n] / hw [n,2],
+    amax (device int32 [n])."""
+
+    def __init__(self, data, binary, offsets, hw, amax):
+        self.data, self.binary, self.offsets, self.hw, self.amax = data, binary, offsets, hw, amax
+
+    def __len__(self):
+        return len(self.offsets)
+
+    def _view(self, buf, i):
+        H, W = (int(v) for v in self.hw[i])
+        o = int(self.offsets[i])
+        return buf[o:o + H * W].view(H, W)
+
+    def sample(self, i):
+        """[H_i, W_i] uint8 view of sample i."""
+        return self._view(self.data, i)
+
+    def binary_sample(self, i):
+        if self.binary is None:
+            raise ValueError("restored without a threshold: no binary mask")
+        return self._view(self.binary, i)
+
+    def soft(self, i):
+        """float64 [H_i, W_i] = byte / (amax + 1e-8): the mask run_crf_original_resolution hands to its CRF (crf_refine.py:94)."""
+        return self.sample(i).double() / (self.amax[i].double() + 1e-8)
+
+    def stack(self, idx):
+        """[k,H,W,1] float32 0 / 1 tensor of the binary masks of samples idx (all of one size): what the metrics kernels take."""
+        idx = list(idx)
+        if len({tuple(int(v) for v in self.hw[i]) for i in idx}) != 1:
+            raise ValueError("stack: the samples must be of one size")
+        return torch.stack([self.binary_sample(i) for i in idx]).to(torch.float32).unsqueeze(-1).contiguous()
+
+
+_checked, _table_cache = set(), {}
+
+
+def _table_key(off, tab, coef, numel, mh, mw):
+    """Everything check_restore_tables reads: a batch with the tables of an earlier one (every DAVIS batch) is validated and
+    uploaded once."""
+    return (off.tobytes(), tab.tobytes(), coef.tobytes(), int(numel), int(mh), int(mw))
+
+
+def _device_tables(key, off, tab, coef, device):
+    from .data import _upload_tables
+    key = key + (str(device),)
+    if key not in _table_cache:
+        if len(_table_cache) >= 16:
+            _table_cache.clear()
+        _table_cache[key] = _upload_tables([off, tab, coef], device)
+        torch.cuda.current_stream(device).synchronize()  # once per table set: a later call may run on another stream
+    return _table_cache[key]
+
+
+def restore_masks(masks, native_hw, crop=0.9, threshold=None, offsets=None, out=None, binary_out=None) -> RestoredMasks:
+    """n soft masks [n,mh,mw] or [n,mh,mw,1] (device float32, or an array) -> each restored to its own native_hw[i] = (H_i, W_i):
+    bytescale over the whole mask, Pillow's 8-bit bilinear resize to restore_box(H_i, W_i, crop), pasted into zeros; amax[i] = the
+    patch's largest byte; threshold (float, optional): also the binary mask byte / (amax + 1e-8) > threshold (float64).  One call
+    of udet_restore_masks_ragged: at most three launches for the whole batch.  offsets / out / binary_out: a caller-owned packed
+    uint8 buffer and the byte offset of every sample in it (default: a fresh buffer, samples back to back).  The tables are
+    validated on the host before anything is launched (ValueError)."""
+    m = masks if isinstance(masks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(masks, dtype=np.float32))
+    if m.dim() == 4 and m.shape[-1] == 1:
+        m = m[..., 0]
+    if m.dim() != 3:
+        raise ValueError("masks must be [n,mh,mw] or [n,mh,mw,1]")
+    n, mh, mw = (int(v) for v in m.shape)
+    hw = np.asarray(native_hw, dtype=np.int64).reshape(-1, 2)
+    if len(hw) != n:
+        raise ValueError("one native size per mask")
+    off, tab, coef = build_restore_tables(hw, mh, mw, crop, offsets)
+    total = int((hw[:, 0] * hw[:, 1]).sum()) if out is None else int(out.numel())
+    if threshold is not None and not (0.0 <= float(threshold) < float("inf")):
+        raise ValueError("threshold must be finite and >= 0")
+    key = _table_key(off, tab, coef, total, mh, mw)
+    if key not in _checked:  # before the device is touched
+        off, tab, coef = check_restore_tables(off, tab, coef, total, mh, mw)
+        if len(_checked) >= 64:
+            _checked.clear()
+        _checked.add(key)
+    m = m.to("cuda", torch.float32).contiguous()
+    dev = m.device
+    for buf, name in ((out, "out"), (binary_out, "binary_out")):
+        if buf is not None and not (buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous() and
+                                    buf.numel() == total):
+            raise ValueError("{} must be a contiguous 1-D uint8 CUDA(HIP) tensor of the output buffer's size".format(name))
+    data = torch.empty(total, dtype=torch.uint8, device=dev) if out is None else out
+    binary = None
+    if threshold is not None:
+        binary = torch.empty(total, dtype=torch.uint8, device=dev) if binary_out is None else binary_out
+    d_off, d_tab, d_coef = _device_tables(key, off, tab, coef, dev)
+    amax = torch.empty(n, dtype=torch.int32, device=dev)  # zeroed by the call
+    ws = torch.empty(max(int(lib.udet_restore_workspace_bytes(n)), 4), dtype=torch.uint8, device=dev)
+    check(lib.udet_restore_masks_ragged(m.data_ptr(), n, mh, mw, d_off.data_ptr(), d_tab.data_ptr(), d_coef.data_ptr(),
+                                        int(hw[:, 0].max()), int(hw[:, 1].max()), data.data_ptr(), amax.data_ptr(),
+                                        None if binary is None else binary.data_ptr(), 0.0 if threshold is None else float(threshold),
+                                        ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return RestoredMasks(data, binary, off, hw.astype(np.int32), amax)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Ground truth at native size, scoring and export
+# ---------------------------------------------------------------------------------------------------------------------------
+class GtRule(object):
+    """How a dataset's annotation becomes a boolean mask at native size: loader(path, channels) -> uint8 [H,W,1] on the host (None:
+    the 8-bit grey decode of data._read_image), then value / 255 > threshold on the device."""
+
+    def __init__(self, loader=None, threshold=0.1):
+        self.loader, self.threshold = loader, float(threshold)
+
+
+def _fbms_loader(path, channels):
+    from . import data, datasets
+    return datasets.fbms_gt_mask(path, data._read_image(path, 3))
+
+
+def _segtrack_loader(path, channels):
+    from . import datasets
+    return datasets.read_decode_jpeg(path, 1)
+
+
+# DAVIS and SegTrackV2: scipy.misc.imread(gt) / 255. > 0.1 (crf_refine.py:89,131).  FBMS: datasets.fbms_gt_mask -- the per-sequence
+# binarisation of the source annotation and the JPEG round trip of the reference's converted files; 0.5 undoes the round trip's
+# ringing and gives back the binarised annotation.
+GT_RULES = {"DAVIS2016": GtRule(None, 0.1), "SEGTRACK": GtRule(_segtrack_loader, 0.1), "FBMS": GtRule(_fbms_loader, 0.5)}
+
+
+class GtBatch(object):
+    """Annotations of one batch, binarised at native size: data (packed uint8 0 / 1), host offsets / hw."""
+
+    def __init__(self, data, offsets, hw):
+        self.data, self.offsets, self.hw = data, offsets, hw
+
+    def sample(self, i):
+        H, W = (int(v) for v in self.hw[i])
+        o = int(self.offsets[i])
+        return self.data[o:o + H * W].reshape(H, W)
+
+    def stack(self, idx):
+        return torch.stack([self.sample(i) for i in idx]).to(torch.float32).unsqueeze(-1).contiguous()
+
+
+_ragged_loader = None
+
+
+def load_gt_device(paths, rule):
+    """The annotations of a batch through data.RaggedLoader (mixed sizes: one pinned buffer, one copy), binarised on the device."""
+    global _ragged_loader
+    from . import data
+    if _ragged_loader is None:
+        _ragged_loader = data.RaggedLoader()
+    rb = _ragged_loader.load(list(paths), 1, loader=rule.loader)
+    return GtBatch((rb.data.double() / 255.0 > rule.threshold).to(torch.uint8), rb.offsets, rb.hw)
+
+
+def score_device(gt_stack, pred_stack, bound_th):
+    """(J, F) per frame of [k,H,W,1] 0 / 1 stacks, scored as they are (no fg/bg flip)."""
+    from .evaluation import evaluate_batch_davis
+    _, _, _, j, f = evaluate_batch_davis(gt_stack, pred_stack, 0.5, bound_th, disambiguate=False)
+    return j, f
+
+
+def _host(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
+                        gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True):
+    """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
+    post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
+    reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
+    DAVIS that of crf_refine.py:86-88).  A category whose .mat count differs from its list is an IOError.  Per category, `batch`
+    masks (mat[mask_key]) at a time are restored to the sizes of their annotations (restore: restore_masks), the annotations
+    binarised by gt_rule (a GT_RULES name or a GtRule) at native size, J and F computed per distinct frame shape
+    (evaluation.evaluate_batch_davis, disambiguate=False).  Writes <out_dir>/<category>/<frame stem>.png (8-bit, 0 / 255),
+    <out_dir>/<category>/result_<k>.mat (mask uint8 0 / 1, soft_mask float32, gt_mask uint8 0 / 1: `davis_eval --results_dir
+    <out_dir> --mask_key mask` reads them unchanged) and <out_dir>/native_eval.json; returns the json's content.
+    restore / load_gt / score are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    import json
+    import re
+    import scipy.io as sio
+    from PIL import Image
+    from .evaluation import BOUND_TH, _davis_summary, _nanmean, _print_davis_table
+    bound_th = BOUND_TH if bound_th is None else bound_th
+    rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
+    batch = max(1, int(batch))
+    cat_j, cat_f = {}, {}
+    for cat, entries in frame_lists.items():
+        d = os.path.join(results_dir, cat)
+        ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
+        if ks != list(range(1, len(entries) + 1)):
+            raise IOError("category {!r}: {} result_<k>.mat under {!r} for {} listed frames".format(cat, len(ks), d, len(entries)))
+        od = os.path.join(out_dir, cat)
+        os.makedirs(od, exist_ok=True)
+        j, f = np.empty(len(entries)), np.empty(len(entries))
+        for s in range(0, len(entries), batch):
+            rows = entries[s:s + batch]
+            masks = []
+            for k in range(s + 1, s + len(rows) + 1):
+                mat = sio.loadmat(os.path.join(d, "result_{}.mat".format(k)))
+                if mask_key not in mat:
+                    raise KeyError("{}: result_{}.mat has no {!r}".format(d, k, mask_key))
+                masks.append(np.squeeze(mat[mask_key]).astype(np.float32))
+                if masks[-1].ndim != 2 or masks[-1].shape != masks[0].shape:
+                    raise ValueError("{}: result_{}.mat: masks must be 2-D and of one shape".format(d, k))
+            gt = load_gt([a for _, a in rows], rule)
+            res = restore(np.stack(masks), gt.hw, crop, threshold)
+            shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
+            for shape in sorted(set(shapes)):
+                idx = [i for i, sh in enumerate(shapes) if sh == shape]
+                jj, ff = score(gt.stack(idx), res.stack(idx), bound_th)
+                j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
+            for i, (img, _) in enumerate(rows):
+                binm = _host(res.binary_sample(i)).astype(np.uint8)
+                Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, os.path.splitext(os.path.basename(img))[0] + ".png"))
+                sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)),
+                            {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32), "gt_mask": _host(gt.sample(i)).astype(np.uint8)})
+        cat_j[cat], cat_f[cat] = j.tolist(), f.tolist()
+    if not cat_j:
+        raise IOError("no category to restore")
+    per, tot = _davis_summary(cat_j, cat_f, skip_ends)
+    cat_iou = {c: _nanmean(cat_j[c]) for c in cat_j}
+    out = {"mask_key": mask_key, "threshold": threshold, "crop": crop, "bound_th": bound_th, "skip_ends": bool(skip_ends),
+           "sequences": {c: dict(per[c], frames=len(cat_j[c])) for c in per}, "J": tot["J"], "F": tot["F"], "J&F": tot["J&F"],
+           "category_iou": cat_iou, "sequence_iou": _nanmean(list(cat_iou.values()))}
+    if verbose:
+        print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
+        _print_davis_table(per, tot)
+    with open(os.path.join(out_dir, "native_eval.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    return out
+
+
+def frame_lists_from_reader(flags):
+    """{category: [(image_path, annotation_path), ...]} of the test pass of --dataset under --root_dir, in the order the reader's
+    test_inputs visits a category's frames; categories named as evaluate_masks names them (fname.split("/")[-2])."""
+    from .cli import _reader
+    rd = _reader(flags, 0, 1)
+    if flags.dataset == "FBMS":
+        pairs = [(t[0], t[2]) for t in rd.get_test_tuples(flags.test_partition, flags.test_temporal_shift)]
+    else:
+        imgs, anns = rd.get_filenames_list() if flags.dataset == "SEGTRACK" else rd.get_filenames_list(flags.test_partition)
+        pairs = [(i, a) for seq_i, seq_a in zip(imgs, anns) for i, a in zip(seq_i, seq_a)]
+    lists = {}
+    for img, ann in pairs:
+        lists.setdefault(str(img).split("/")[-2], []).append((str(img), str(ann)))
+    return lists

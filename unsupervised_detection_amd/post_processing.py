@@ -52,33 +52,39 @@ def _dev(x, dtype):
 _coeff_cache = {}
 
 
-def _pil_coeffs(in_size: int, out_size: int):
+def _pil_coeffs_host(in_size: int, out_size: int):
     """Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter (host side, exactly Pillow's double
-    arithmetic): device int32 tables kk [out][ksize] and bounds [out][2]."""
+    arithmetic): int32 arrays kk [out][ksize] and bounds [out][2] = (first tap, taps), and ksize."""
+    scale = filterscale = in_size / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    kk = np.zeros((out_size, ksize), np.int32)
+    bounds = np.zeros((out_size, 2), np.int32)
+    ss = 1.0 / filterscale
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [0.0] * ksize
+        ww = 0.0
+        for x in range(xmax):
+            v = abs((x + xmin - center + 0.5) * ss)
+            w[x] = 1.0 - v if v < 1.0 else 0.0
+            ww += w[x]
+        for x in range(ksize):
+            v = w[x] / ww if (x < xmax and ww != 0.0) else w[x]
+            kk[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
+        bounds[xx] = (xmin, xmax)
+    return kk, bounds, ksize
+
+
+def _pil_coeffs(in_size: int, out_size: int):
+    """_pil_coeffs_host as device int32 tables kk [out][ksize] and bounds [out][2] (cached per (in, out))."""
     key = (in_size, out_size)
     if key not in _coeff_cache:
-        scale = filterscale = in_size / out_size
-        if filterscale < 1.0:
-            filterscale = 1.0
-        support = 1.0 * filterscale
-        ksize = int(math.ceil(support)) * 2 + 1
-        kk = np.zeros((out_size, ksize), np.int32)
-        bounds = np.zeros((out_size, 2), np.int32)
-        ss = 1.0 / filterscale
-        for xx in range(out_size):
-            center = (xx + 0.5) * scale
-            xmin = max(int(center - support + 0.5), 0)
-            xmax = min(int(center + support + 0.5), in_size) - xmin
-            w = [0.0] * ksize
-            ww = 0.0
-            for x in range(xmax):
-                v = abs((x + xmin - center + 0.5) * ss)
-                w[x] = 1.0 - v if v < 1.0 else 0.0
-                ww += w[x]
-            for x in range(ksize):
-                v = w[x] / ww if (x < xmax and ww != 0.0) else w[x]
-                kk[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
-            bounds[xx] = (xmin, xmax)
+        kk, bounds, ksize = _pil_coeffs_host(in_size, out_size)
         _coeff_cache[key] = (torch.from_numpy(kk).cuda(), torch.from_numpy(bounds).cuda(), ksize)
     return _coeff_cache[key]
 
