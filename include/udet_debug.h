@@ -3,6 +3,7 @@
  * (unsupervised_detection_amd/_devel.py) to pin one convolution kernel family / tile / split-K mode and to ask which one ran. */
 #ifndef UDET_DEBUG_H
 #define UDET_DEBUG_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -24,6 +25,20 @@ void udet_debug_force_wgrad(int nsplit, int dma);
 /* what the most recent filter-gradient launch ran: K slices | variant << 20 (0 register-staged, 1 / 2 LDS-DMA, 3 the Winograd-domain family of
  * conv_wgrad_wino.hip; dma = 3 above forces it where a launch is eligible: 3x3 stride-1, whole 64-channel blocks) */
 int udet_debug_last_wgrad(void);
+/* the reduction behind that launch: lanes per element SL | CW << 8 (channel width of the fused BN reduction; 0: the plain slab reduction) |
+ * rows per block << 16 (fused BN reduction) | 1 << 26 fused BN reduction | 1 << 27 separate BN finalisation (dot + finish launches) |
+ * 1 << 28 operand-swapped view | 1 << 29 class-structured view */
+int udet_debug_last_wgrad_reduce(void);
+/* The filter gradient exactly as the step plan calls it.  x [n,h,w,ldx] and dy [n,oh,ow,ldy] (y_saved like dy; act' on load when given with
+ * act != none) carry the layer's channels at x_coff / y_coff (all four multiples of 4; the float4 groups of a window must lie inside the row).
+ * gamma != null: BN-folded layer y = gamma*bn_c*(conv + b) + beta -- needs w, b, db, dgamma, dbeta.  up: 0 none, 1 NN x2 fused into the
+ * loader (x on the h x w grid, dy on 2h x 2w), 2 the class-structured low-resolution form of the same layer (3x3, BN-folded, dy = dU).
+ * workspace: 64-byte aligned; 64 floats + 1024*cout rounded up to 16 + one (bias, filter) slab per split at the padded tile sizes
+ * (+ 16*cin*cout + 64*cout + 1024 floats for up = 2); the split count is clamped to what fits. */
+int udet_debug_conv2d_backward_filter_ex(const float* x, int ldx, int x_coff, const float* dy, int ldy, int y_coff, const float* y_saved, int act,
+                                         float alpha, const float* w, const float* b, const float* gamma, float bn_c, float* dw, float* db,
+                                         float* dgamma, float* dbeta, int n, int h, int wd, int cin, int cout, int k, int stride, int dilation,
+                                         int up, void* workspace, size_t workspace_bytes, void* stream);
 /* plans created after this call: the recover decoder's backward-data pass takes the low-resolution ("up-conv algebra") form on every
  * level whose source has at least `v` pixels (batch included); v < 0 restores the default of 8192.  Tests use 0 on small plans. */
 void udet_debug_upb_min_pixels(long v);
@@ -35,7 +50,6 @@ void udet_debug_force_pair(int on);
 int udet_debug_last_pair(void);
 /* two forward convolutions (same shape parameters; cin a multiple of 8; batches na / nb; HWIO weights) through the pair launcher;
  * workspace >= (2 * k*k*cin*roundup(cout,4) + 4 Mi + 8192) floats */
-#include <stddef.h>
 int udet_debug_conv2d_pair(const float* xa, const float* xb, const float* wa, const float* wb, const float* ba, const float* bb, float* ya, float* yb,
                            int na, int nb, int h, int w, int cin, int cout, int k, int stride, int dilation, int act, float alpha, void* workspace,
                            size_t workspace_bytes, void* stream);

@@ -206,3 +206,25 @@ def test_latest_checkpoint_accepts_reference_and_tf_files(tmp_path):
     e.mkdir()
     (e / "model.best").write_bytes(b"")
     assert _latest_checkpoint(str(e)) == str(e / "model.best")
+
+
+def test_debug_filter_gradient_entry_checks_its_arguments_before_any_device_call():
+    """udet_debug_conv2d_backward_filter_ex (tests/test_wgrad_gpu.py drives it on the GPU): windows that are not multiples of 4 or leave
+    the row, a BN-folded layer without its outputs, a class-structured call that is not a BN-folded 3x3 layer -- refused on the host."""
+    from unsupervised_detection_amd._devel import dbg
+    from unsupervised_detection_amd._ffi import lib
+    SHAPE, ALIGN, ARG = -1, -2, -5
+    fake = 1 << 20  # never dereferenced: every check comes before the first HIP call
+
+    def call(ldx=8, x_coff=0, ldy=8, y_coff=0, gamma=None, outs=(fake, fake, None, None), up=0, k=3, ws=fake, ws_bytes=1 << 20, x=fake):
+        wb = fake if gamma else None
+        return dbg.udet_debug_conv2d_backward_filter_ex(x, ldx, x_coff, fake, ldy, y_coff, None, 0, 0.0, wb, wb, gamma, 1.0, *outs, 1, 4, 4, 8, 8, k, 1, 1, up,
+                                                        ws, ws_bytes, None)
+    assert call(ldx=10) == ALIGN and b"multiples of 4" in lib.udet_last_error()
+    assert call(ldx=12, x_coff=2) == ALIGN and call(ldy=12, y_coff=6) == ALIGN and call(ldy=9) == ALIGN
+    assert call(ldx=12, x_coff=8) == SHAPE and call(ldy=8, y_coff=4) == SHAPE  # the window leaves the row
+    assert call(gamma=fake) == ARG and b"dgamma" in lib.udet_last_error()
+    assert call(gamma=fake, outs=(fake, fake, fake, None)) == ARG and call(gamma=fake, outs=(fake, None, fake, fake)) == ARG
+    assert call(up=2) == ARG and call(up=2, gamma=fake, outs=(fake,) * 4, k=5) == ARG and call(up=3) == ARG
+    assert call(x=None) == ARG and call(outs=(None, fake, None, None)) == ARG
+    assert call(ws=None) == ARG and call(ws=fake + 4) == ARG and call(ws_bytes=64) == ARG

@@ -32,3 +32,9 @@ dbg.udet_debug_last_pair.restype = ctypes.c_int
 dbg.udet_debug_last_pair.argtypes = []
 dbg.udet_debug_conv2d_pair.restype = ctypes.c_int
 dbg.udet_debug_conv2d_pair.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int] * 10 + [ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+dbg.udet_debug_last_wgrad_reduce.restype = ctypes.c_int
+dbg.udet_debug_last_wgrad_reduce.argtypes = []
+_p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+dbg.udet_debug_conv2d_backward_filter_ex.restype = ctypes.c_int
+dbg.udet_debug_conv2d_backward_filter_ex.argtypes = ([_p, _i, _i, _p, _i, _i, _p, _i, _f, _p, _p, _p, _f, _p, _p, _p, _p] + [_i] * 9
+                                                     + [_p, ctypes.c_size_t, _p])

@@ -260,6 +260,9 @@ struct WgradParams {
   float f16_yscale;
 };
 int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream);
+// the class-structured low-resolution form of an NN x2 + 3x3 BN-folded layer (conv_wgrad.hip): q as launch_wgrad_T takes the layer,
+// X on the H x W grid, dU on 2H x 2W
+int launch_wgrad_up_T(const WgradParams& q, int H, int W, hipStream_t stream);
 int launch_bn_finalize(float* dw, int T, int Cin, int Cout, const float* w, const float* b, const float* gamma, float bn_c, float* pd,
                        float* db, float* dgamma, float* dbeta, hipStream_t stream);
 int launch_wgrad_up_combine(const float* deff, float* dw, int Cin, int Cout, hipStream_t stream);

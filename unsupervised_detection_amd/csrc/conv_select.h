@@ -75,7 +75,7 @@ ConvCfg tune_conv(ConvParams& p, uint64_t key, hipStream_t stream);
 ConvCfg tune_conv_pair(ConvParams& a, ConvParams& b, uint64_t key, hipStream_t stream);
 // filter gradient: run(cfg) launches GEMM + reduction on cfg = split count | variant << 20; what launch_wgrad_T knows about the launch
 // (p: the caller's problem -- log lines, dw / db; g: the view that runs, operands possibly swapped; tiles: output tiles of the GEMM;
-// cap: split capacity of the direct variants; maxs: slices the workspace holds; wsz: floats of dw)
-struct WgradTuneInfo { const WgradParams &p, &g; long tiles; int cap; size_t maxs; bool dma_ok, wino_ok; size_t wsz; };
+// cap: split capacity of the direct variants; maxs: slices the workspace holds; wsz: floats of dw; fused_bn: run() also writes dgamma / dbeta)
+struct WgradTuneInfo { const WgradParams &p, &g; long tiles; int cap; size_t maxs; bool dma_ok, wino_ok; size_t wsz; bool fused_bn; };
 int tune_wgrad(const WgradTuneInfo& t, int heuristic, uint64_t key, const std::function<int(int)>& run, hipStream_t stream);
 }  // namespace udet

@@ -454,18 +454,28 @@ int tune_wgrad(const WgradTuneInfo& t, int h, uint64_t key, const std::function<
           })) best = cfg;
     }
   }
-  // the winner's filter / bias gradient must equal the heuristic configuration's (candidate verification, above)
+  // the winner's filter / bias gradient must equal the heuristic configuration's (candidate verification, above); BN-folded layers whose
+  // reduction also forms dgamma / dbeta (wgrad_reduce_bn_kernel: one instantiation per channel width and split count): those two as
+  // well.  (The separate form computes them behind run(), from a dw that is compared here, with kernels no configuration changes.)
   if (best != h) {
-    float* r0 = tune_scratch(t.wsz + (size_t)p.Cout, 0);
+    const size_t nc = (size_t)p.Cout;
+    const bool bn = p.gamma && t.fused_bn && p.dgamma && p.dbeta;
+    float* r0 = tune_scratch(t.wsz + 3 * nc, 0);
     bool ok = false;
     float diff = 0.f, scale = 0.f;
     if (r0) {
       run(h);
       (void)hipMemcpyAsync(r0, p.dw, t.wsz * sizeof(float), hipMemcpyDeviceToDevice, stream);
-      if (p.db) (void)hipMemcpyAsync(r0 + t.wsz, p.db, (size_t)p.Cout * sizeof(float), hipMemcpyDeviceToDevice, stream);
+      if (p.db) (void)hipMemcpyAsync(r0 + t.wsz, p.db, nc * sizeof(float), hipMemcpyDeviceToDevice, stream);
+      if (bn) {
+        (void)hipMemcpyAsync(r0 + t.wsz + nc, p.dgamma, nc * sizeof(float), hipMemcpyDeviceToDevice, stream);
+        (void)hipMemcpyAsync(r0 + t.wsz + 2 * nc, p.dbeta, nc * sizeof(float), hipMemcpyDeviceToDevice, stream);
+      }
       run(best);
       ok = tune_compare(r0, p.dw, t.wsz, stream, &diff, &scale);
-      if (ok && p.db) ok = tune_compare(r0 + t.wsz, p.db, (size_t)p.Cout, stream, &diff, &scale);
+      if (ok && p.db) ok = tune_compare(r0 + t.wsz, p.db, nc, stream, &diff, &scale);
+      if (ok && bn) ok = tune_compare(r0 + t.wsz + nc, p.dgamma, nc, stream, &diff, &scale);
+      if (ok && bn) ok = tune_compare(r0 + t.wsz + 2 * nc, p.dbeta, nc, stream, &diff, &scale);
     }
     if (!ok) {
       fprintf(stderr, "[udet tune] REJECTED wgrad N=%d %dx%d Cin=%d Cout=%d taps=%d: nsplit=%d dma=%d differs from the heuristic "

@@ -4,6 +4,7 @@
 // Replaces TF-1.13 Conv2DBackpropFilter / BiasAddGrad / FusedBatchNormGrad(inference) reached
 // through optimizer.compute_gradients (models/utils/loss_utils.py:18).
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.h"
 #include "conv_select.h"
@@ -645,7 +646,11 @@ size_t wgrad_partial_floats_needed(int T, int Cin, int Cout) {
 
 static int g_force_wsplit = 0, g_force_wdma = -1;  // test / tool hook (libudet_debug.so): pin the split count / staging variant
 static int g_wlast = 0;                             // configuration of the most recent launch_wgrad_T: split count | variant << 20 (3: Winograd family)
+// reduction behind the most recent launch_wgrad_T (udet_debug_last_wgrad_reduce): lanes per element SL | CW << 8 (0: the plain
+// reduction) | rows per block << 16 | WGRAD_RED_* flags
+static int g_wreduce = 0;
 int wgrad_last_config() { return g_wlast; }
+int wgrad_last_reduce() { return g_wreduce; }
 void wgrad_force(int nsplit, int dma) { g_force_wsplit = nsplit > 0 ? nsplit : 0; g_force_wdma = dma; }
 
 template <int BM, int BN, int WM_, int WN_>
@@ -774,6 +779,7 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
                          // took 30 us instead of 5)
       while ((Mreal + rb - 1) / rb > BNR_MAXBLK) rb *= 2;
       const int nb = (Mreal + rb - 1) / rb;
+      g_wreduce = sl | (cw << 8) | (rb << 16) | WGRAD_RED_FUSED_BN;
 #define UDET_RBN(CW_, SL_) UDET_LAUNCH((wgrad_reduce_bn_kernel<CW_, SL_>), dim3(nb), dim3(256), 0, stream, q, ldn, ns, rb, pd)
       if (cw == 128) { if (sl == 2) UDET_RBN(128, 2); else UDET_RBN(128, 1); }
       else if (cw == 64) { if (sl == 4) UDET_RBN(64, 4); else if (sl == 2) UDET_RBN(64, 2); else UDET_RBN(64, 1); }
@@ -784,6 +790,7 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
       return UDET_OK;
     }
     const int sl = (ns >= 64 && total * 64 <= 262144) ? 64 : ((ns >= 8 && total * 8 <= 262144) ? 8 : 1);
+    g_wreduce = sl | (g.swapped ? WGRAD_RED_SWAPPED : 0) | (p.ycls ? WGRAD_RED_CLASSES : 0);
     const long nbl = (total * sl + 255) / 256;
     const int nb = (int)(nbl > 4096 ? 4096 : nbl);
     if (sl == 64) UDET_LAUNCH(wgrad_reduce_kernel<64>, dim3(nb), dim3(256), 0, stream, q, ldn, ns);
@@ -800,7 +807,7 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
       const int v = cached >> 20, ns = cached & 0xfffff;
       if (v >= 0 && v <= 3 && ns >= 1) nsplit = (v != 3 && ns > cap ? cap : ns) | (v << 20);  // (variant 3 is clamped to its strips / the workspace below)
     } else if (wgrad_tuning_on()) {
-      nsplit = tune_wgrad(WgradTuneInfo{p, g, tiles, cap, maxs, dma_ok, wino_ok, wsz}, nsplit, key, run, stream);
+      nsplit = tune_wgrad(WgradTuneInfo{p, g, tiles, cap, maxs, dma_ok, wino_ok, wsz, fused_bn}, nsplit, key, run, stream);
     }
   }
   if (g_force_wsplit > 0) {
@@ -822,6 +829,7 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
       set_error("wgrad: BN finalisation needs db, dgamma, dbeta, w and b");
       return UDET_ERR_ARG;
     }
+    g_wreduce |= WGRAD_RED_SEPARATE_BN;
     UDET_LAUNCH(bn_dot_kernel, dim3((p.Cout + 63) / 64, BND_SPLIT), dim3(256), 0, stream, p.w, p.dw, T * p.Cin,
                        p.Cout, pd);
     UDET_LAUNCH(bn_finish_kernel, dim3(nbw), dim3(256), 0, stream, p.dw, (long)wsz, p.Cout, p.gamma, p.b, p.bn_c, pd,
@@ -829,6 +837,38 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
     UDET_HIP(hipGetLastError());
   }
   return UDET_OK;
+}
+
+// NN x2 + 3x3 of a BN-folded layer in the class-structured form (gen_deconv; the taps of setup_up_fwd): q describes the layer as
+// launch_wgrad_T would take it (X on the low-resolution H x W grid, dU on 2H x 2W, dw / db / dgamma / dbeta, w / b / gamma, the
+// workspace).  dWeff[class][tap] = sum_q X[q + d]^T dU[2q + p] over the low-resolution pixels (16 instead of 36 tap products each), then
+// dW[ky][kx] = sum over the classes of the effective tap that contains it, then the BN finalisation.  The end of the workspace holds
+// dWeff [16][Cin][Cout] and the BN-dot partials; the GEMM's slabs get what is in front of them.
+int launch_wgrad_up_T(const WgradParams& q, int H, int W, hipStream_t stream) {
+  const size_t reserve = (size_t)16 * q.Cin * q.Cout + 64 * (size_t)q.Cout + 1024;
+  if (q.partial_floats <= reserve) {
+    set_error("wgrad: workspace too small for the class-structured form (%zu <= %zu floats)", q.partial_floats, reserve);
+    return UDET_ERR_ARG;
+  }
+  ConvParams t;
+  memset(&t, 0, sizeof(t));
+  setup_up_fwd(t, q.N, H, W);
+  float* deff = q.partial + (q.partial_floats - reserve);  // [16][Cin][Cout] + BN-dot partials
+  float* pd = deff + (size_t)16 * q.Cin * q.Cout;
+  WgradParams u = q;  // the low-resolution GEMM: effective taps into `deff`, no BN finalisation of its own
+  u.H = H; u.W = W; u.up_shift = 0;
+  u.OH = H; u.OW = W; u.isy = u.isx = 1;
+  u.ycls = 1; u.OHf = 2 * H; u.OWf = 2 * W;
+  u.ntaps = 16;
+  memcpy(u.taps, t.taps, sizeof(t.taps));
+  u.partial_floats = q.partial_floats - reserve;
+  u.dw = deff;  // (u.db = q.db: the kernel's own column sums of dU, four class partials per split)
+  u.w = u.b = u.gamma = nullptr; u.dgamma = u.dbeta = nullptr;
+  int rc = launch_wgrad_T(u, 16, stream);
+  if (rc == UDET_OK) rc = launch_wgrad_up_combine(deff, q.dw, q.Cin, q.Cout, stream);
+  if (rc == UDET_OK) rc = launch_bn_finalize(q.dw, 9, q.Cin, q.Cout, q.w, q.b, q.gamma, q.bn_c, pd, q.db, q.dgamma, q.dbeta, stream);
+  if (rc == UDET_OK) g_wreduce |= WGRAD_RED_SEPARATE_BN;
+  return rc;
 }
 
 }  // namespace udet

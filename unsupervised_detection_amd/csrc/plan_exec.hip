@@ -50,7 +50,7 @@ static inline bool skip_launch(int kind, int net) {
 // the additions.  Tap t of class (py,px): row offset d(py,ty), column offset d(px,tx), weight matrix class*4 + t.
 static inline int up_off(int parity, int t) { return parity == 0 ? (t == 0 ? -1 : 0) : (t == 0 ? 0 : 1); }
 // forward: ncls = 4 launch on the low-resolution grid writing the four output sub-lattices
-static void setup_up_fwd(ConvParams& p, int N, int H, int W) {
+void setup_up_fwd(ConvParams& p, int N, int H, int W) {
   p.N = N; p.H = H; p.W = W;
   p.OH = 2 * H; p.OW = 2 * W; p.OHq = H; p.OWq = W;
   p.osy = p.osx = 2; p.ooy = p.oox = 0; p.isy = p.isx = 1;
@@ -351,28 +351,9 @@ int run_wgrad(Plan* P, const Layer& L, int N, int dy, bool dy_is_du, const float
     q.bn_c = BN_C;
   }
   if (L.up && L.wu_off && L.g_idx >= 0 && dy_is_du) {
-    // NN x2 + 3x3 as four 2x2 convolutions (setup_up_fwd): dWeff[class][tap] = sum_q X[q + d]^T dU[2q + p] over the low-resolution
-    // pixels (16 instead of 36 tap products each), then dW[ky][kx] = sum over the classes of the effective tap that contains it,
-    // then the BN finalisation
-    ConvParams t;
-    memset(&t, 0, sizeof(t));
-    setup_up_fwd(t, N, L.H, L.W);
-    const size_t reserve = (size_t)16 * L.cin * L.cout + 64 * (size_t)L.cout + 1024;
-    float* deff = ws + P->wgrad_off[ln.slot] + (P->wgrad_floats - reserve);  // [16][Cin][Cout] + BN-dot partials
-    float* pd = deff + (size_t)16 * L.cin * L.cout;
-    WgradParams u = q;  // the low-resolution GEMM: effective taps into `deff`, no BN finalisation of its own
-    u.H = L.H; u.W = L.W; u.up_shift = 0;
-    u.OH = L.H; u.OW = L.W; u.isy = u.isx = 1;
-    u.ycls = 1; u.OHf = 2 * L.H; u.OWf = 2 * L.W;
-    u.ntaps = 16;
-    memcpy(u.taps, t.taps, sizeof(t.taps));
-    u.partial_floats = P->wgrad_floats - reserve;
-    u.dw = deff;  // (u.db = q.db: the kernel's own column sums of dU, four class partials per split)
-    u.w = u.b = u.gamma = nullptr; u.dgamma = u.dbeta = nullptr;
+    // NN x2 + 3x3 as four 2x2 convolutions on the low-resolution grid (launch_wgrad_up_T, conv_wgrad.hip)
     prof_begin(P, PROF_CONV_WGRAD, layer_flops(L, N) * 4.0 / 9.0, layer_bytes(L, N), s, L.name.c_str());
-    int rc = launch_wgrad_T(u, 16, s);
-    if (rc == UDET_OK) rc = launch_wgrad_up_combine(deff, q.dw, L.cin, L.cout, s);
-    if (rc == UDET_OK) rc = launch_bn_finalize(q.dw, 9, L.cin, L.cout, q.w, q.b, q.gamma, BN_C, pd, q.db, q.dgamma, q.dbeta, s);
+    const int rc = launch_wgrad_up_T(q, L.H, L.W, s);
     prof_end(P, s);
     return rc;
   }
