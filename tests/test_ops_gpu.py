@@ -295,6 +295,49 @@ def test_conv_kernel_families(ops, force_conv, family, case):
     assert (dx - gx.float()).abs().max() < 2e-4 * max(1.0, float(gx.abs().max()))
 
 
+# every instantiated tile of every implicit-GEMM family (each family's file maps (bm, bn) to its instantiation: a tile wired to another
+# tile's kernel computes on the wrong rows / columns).  One shape, (n,h,w,cin,cout,k,s): M = 560 rows leave a partial M tile for BM = 64,
+# 128 and 256, 100 (forward) / 40 (backward-data) columns a partial N tile for every BN, 40 / 100 channels a narrower last channel block.
+TILE_CASE = (1, 20, 28, 40, 100, 3, 1)
+GEMM_TILES = [(256, 32), (128, 32), (128, 64), (64, 64), (128, 96), (128, 128)]  # CONV_GEMM_TILES (conv_igemm.hip)
+TILE_FAMILIES = {"plain": (1 << 16, 0), "wave_spec": (0, 1), "ring2": (1 << 17, 2), "ring3": (1 << 22, 4), "ring4": (1 << 23, 5)}  # bit, ConvFamily
+TILE_CONFIGS = [(f, bm, bn) for f in TILE_FAMILIES for bm, bn in GEMM_TILES] + [("self_staging", bm, bn) for bm, bn in GEMM_TILES if bn != 96]
+_tile_case_ref = []
+
+
+def _tile_case():
+    """Operands and the float64 results of TILE_CASE, computed once."""
+    if not _tile_case_ref:
+        n, h, w, cin, cout, k, s = TILE_CASE
+        x = rnd(n, h, w, cin, seed=31).double().requires_grad_(True)
+        wt = rnd(k, k, cin, cout, seed=32, scale=(2.0 / (k * k * cin)) ** 0.5).double()
+        b = rnd(cout, seed=33, scale=0.1).double()
+        y = _oracle_conv(x, wt, b, s, 1, "leaky", 0.1, False)
+        lin = O.conv2d_same(x, wt, None, s, 1)
+        dy = rnd(*y.shape, seed=34).double()
+        gx, = torch.autograd.grad((lin * dy).sum(), [x])
+        _tile_case_ref.append((x.detach().float(), wt.float(), b.float(), y.detach().float(), lin.detach().float(), dy.float(), gx.float()))
+    return _tile_case_ref[0]
+
+
+@pytest.mark.parametrize("family,bm,bn", TILE_CONFIGS)
+def test_conv_every_tile_of_every_family(ops, force_conv, family, bm, bn):
+    """Forward and backward-data of the linear layer on one forced (family, tile) against the float64 oracle.  The hook reports the
+    family and bm that ran, which are asserted; it carries no bn: a wrong N tile shows in the result (partial N tiles for every bn)."""
+    n, h, w, cin, cout, k, s = TILE_CASE
+    x, wt, b, y, lin, dy, gx = _tile_case()
+    bit, fam = (1 << 19, 6) if family == "self_staging" else TILE_FAMILIES[family]
+    force_conv.udet_debug_force_conv(bm + bit, bn, 1)
+    got = ops.conv2d(x.cuda(), wt.cuda(), b.cuda(), s, 1, "leaky", 0.1, False).cpu()
+    last = force_conv.udet_debug_last_conv()
+    assert (last & 0xff) == fam and (last >> 8) & 0xfff == bm
+    assert (got - y).abs().max() < 1e-4 * max(1.0, float(y.abs().max()))
+    dx = ops.conv2d_backward_data(dy.cuda(), lin.cuda(), wt.cuda(), (h, w), s, 1, "none", 0.0).cpu()
+    last = force_conv.udet_debug_last_conv()
+    assert (last & 0xff) == fam and (last >> 8) & 0xfff == bm
+    assert (dx - gx).abs().max() < 2e-4 * max(1.0, float(gx.abs().max()))
+
+
 # Winograd F(2x2,3x3) family (conv_wino.hip; bit 25 of the forced tile, low bits = variant: bit 0 64 tiles x 64 channels / 128 x 32,
 # bit 1 the four-wave / the eight-wave kernel; 4: the half-size form -- 32 tiles x 64 channels, two-buffer ring, two workgroups per CU):
 # n, h, w, cin, cout, dilation

@@ -15,7 +15,7 @@ from unsupervised_detection_amd import ops  # noqa: E402
 lib.udet_debug_force_conv.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
 lib.udet_debug_force_conv.restype = None
 lib.udet_debug_last_conv.restype = ctypes.c_int
-TS = 12  # stamps per workgroup (conv_igemm.hip: IGEMM_TS)
+TS = 12  # stamps per workgroup (conv_igemm_ring.hip: IGEMM_TS)
 NAMES = ["tables", "first stage lands", "K loop", "tile store (issue)", "stores acknowledged"]
 # name, n, h, w, cin, cout, k, stride, dil, (bm, bn, ks)
 SHAPES = [

@@ -103,6 +103,26 @@ inline FastDiv make_fastdiv(unsigned d) {
 }
 __device__ __forceinline__ unsigned fdiv(unsigned n, const FastDiv& f) { return f.d == 1 ? n : (__umulhi(n, f.mul) >> f.sh); }
 
+// XCD-aware workgroup order.  The hardware deals consecutive workgroup ids round-robin to the 8 XCDs, each with its own L2.  This maps
+// hardware id `bid` of an nwg-wide grid to a logical id such that every XCD walks ONE contiguous range of logical ids: neighbouring
+// tiles, which share input halos or operand rows, are served by the same L2.
+__host__ __device__ __forceinline__ constexpr int xcd_tile_order(int bid, int nwg) {
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+constexpr bool xcd_tile_order_permutes(int nwg) {  // (nwg <= 64) every logical id of [0, nwg) exactly once
+  unsigned long long seen = 0;
+  for (int b = 0; b < nwg; ++b) {
+    const int l = xcd_tile_order(b, nwg);
+    if (l < 0 || l >= nwg || ((seen >> l) & 1)) return false;
+    seen |= 1ull << l;
+  }
+  return true;
+}
+static_assert(xcd_tile_order_permutes(1) && xcd_tile_order_permutes(7) && xcd_tile_order_permutes(8), "xcd_tile_order");
+static_assert(xcd_tile_order_permutes(9) && xcd_tile_order_permutes(13) && xcd_tile_order_permutes(64), "xcd_tile_order");
+static_assert(xcd_tile_order(1, 13) == 2 && xcd_tile_order(8, 13) == 1 && xcd_tile_order(5, 13) == 10, "xcd 0..4 of 13 hold two tiles, 5..7 one");
+
 // One segment of a segmented launch (ConvParams::nseg): a sub-grid of the output with its own tap list
 struct ConvSeg {
   int oy, ox;   // output pixel of the segment's quotient pixel (0, 0)

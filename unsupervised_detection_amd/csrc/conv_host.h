@@ -22,7 +22,7 @@ size_t conv_wino_floats(int Kc, int cout);
 long conv_wino_workgroups(const ConvParams& p, int variant);
 int conv_wino_max_ksplit(const ConvParams& p, int variant);
 int launch_conv_wino(ConvParams& p, int variant, int ks, hipStream_t stream);
-int launch_splitk_second_pass(const ConvParams& p, hipStream_t stream);  // conv_igemm.hip: sums p.partial's ksplit slabs + epilogue
+int launch_splitk_second_pass(const ConvParams& p, hipStream_t stream);  // conv_splitk.hip: sums p.partial's ksplit slabs + epilogue
 int launch_wino_pack(const float* src, float* dst, int R, int C, int Kc, int np, int k_split, int k_gap, int transposed, hipStream_t stream);
 // U straight from PACKED weights [tap][Kc][ldw] and the launch's own tap table (single-operator launches, tests)
 int launch_wino_from_packed(const ConvParams& p, float* dst, int np, hipStream_t stream);

@@ -1,5 +1,6 @@
 // Internal: what the convolution launchers share -- the kernel families, a launch's configuration, and the interfaces between
-//   conv_igemm.hip   the implicit-GEMM kernels and the code that instantiates them,
+//   conv_igemm.hip   the host side of the implicit GEMM: the tile table, the grid of a launch, launch_conv_gemm / launch_conv_gemm_pair;
+//                    the kernels, one family per file, and their launchers are behind conv_igemm_common.h (its header lists the files),
 //   conv_select.hip  which configuration a launch runs (heuristics, debug forcing, validation; launch_conv / launch_conv_pair),
 //   conv_tune.hip    the autotuner (timing, candidate verification, the three caches and their text form).
 #pragma once
@@ -45,7 +46,7 @@ struct ConvCfg {
 constexpr int CONV_GEMM_NTILES = 6;
 extern const int CONV_GEMM_TILES[CONV_GEMM_NTILES][2];  // the instantiated (bm, bn) tiles, in the order the tuners scan them
 bool conv_gemm_tile(int bm, int bn);                    // is (bm, bn) one of them?
-bool conv_self_staging_tile(int bm, int bn);            // ... and one the self-staging kernel is instantiated for?
+bool conv_self_staging_tile(int bm, int bn);            // ... and one the self-staging kernel is instantiated for? (conv_igemm_self.hip)
 int conv_xblocks(const ConvParams& p, int bm);          // x-blocks of a launch: M tiles of every class / segment
 inline long cfg_tiles(const ConvParams& p, int bm, int bn) { return (long)conv_xblocks(p, bm) * ((p.Cout + bn - 1) / bn); }
 // a prepared launch on a configuration of a GEMM family / two prepared, pair-compatible launches as one grid (c.family: FAM_DMA2 / FAM_DMA3)

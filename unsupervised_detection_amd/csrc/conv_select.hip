@@ -1,6 +1,6 @@
 // Which kernel family and configuration a forward / backward-data convolution launch runs: argument checks, the built-in
 // heuristics, the debug forcing of include/udet_debug.h, the ONE validation of a configuration against a launch (runnable_cfg),
-// and the launchers launch_conv / launch_conv_pair.  The families are listed in conv_select.h; the kernels live in conv_igemm.hip,
+// and the launchers launch_conv / launch_conv_pair.  The families are listed in conv_select.h; the kernels live in conv_igemm_*.hip,
 // conv_tile.hip, conv_thin.hip and conv_wino.hip; the autotuner that fills the caches is conv_tune.hip.
 #include <mutex>
 

@@ -42,9 +42,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p, in
   // 5.4 GB per step for 1.1 GB of operands).  Each XCD now walks whole slices: logical id = slice * tiles + tile.
   int bx, by;
   {
-    const int nx = gridDim.x, nwg = nx * gridDim.y, h = blockIdx.x + nx * blockIdx.y;
-    const int q = nwg >> 3, r = nwg & 7, xcd = h & 7, idx = h >> 3;
-    const int l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int nx = gridDim.x, l = xcd_tile_order(blockIdx.x + nx * blockIdx.y, nx * gridDim.y);
     by = gridDim.y == 1 ? 0 : l / nx;  // (one pixel slice: no run-time division)
     bx = l - by * nx;
   }
@@ -227,9 +225,7 @@ __global__ __launch_bounds__(512, NS == 2 ? 4 : 2) void conv_wgrad_dma_kernel(co
   // 5.4 GB per step for 1.1 GB of operands).  Each XCD now walks whole slices: logical id = slice * tiles + tile.
   int bx, by;
   {
-    const int nx = gridDim.x, nwg = nx * gridDim.y, h = blockIdx.x + nx * blockIdx.y;
-    const int q = nwg >> 3, r = nwg & 7, xcd = h & 7, idx = h >> 3;
-    const int l = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int nx = gridDim.x, l = xcd_tile_order(blockIdx.x + nx * blockIdx.y, nx * gridDim.y);
     by = gridDim.y == 1 ? 0 : l / nx;  // (one pixel slice: no run-time division)
     bx = l - by * nx;
   }

@@ -56,11 +56,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int cib = sub & 1, cob = sub >> 1;
   const int nci = p.Cin / 64, nblk = nci * (p.Cout / 64);
   // the channel-block pairs of one K slice are consecutive workgroups of ONE XCD (they read the same strips): logical id = slice * blocks + block
-  int bid;
-  {
-    const int nwg = gridDim.x, h = blockIdx.x, q = nwg >> 3, r = nwg & 7, xcd = h & 7, idx = h >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
   const int blk = bid % nblk, slice = bid / nblk;
   const int ci0 = (blk % nci) * 64, co0 = (blk / nci) * 64;
   const int s_begin = (int)((long)g.strips * slice / g.slices), s_end = (int)((long)g.strips * (slice + 1) / g.slices);

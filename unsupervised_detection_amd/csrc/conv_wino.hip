@@ -313,11 +313,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int wn = wave % WN, wt = wave / WN, wty = wt / WTX, wtx = wt % WTX;
 
   // XCD-aware block order: consecutive blocks (which share input halos) stay on one XCD's L2
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int bid = xcd_tile_order(blockIdx.x, gridDim.x);
   // the N blocks of one tile block are consecutive workgroups of ONE XCD: they read the same input halo out of that XCD's L2
   // (as blockIdx.y they ran a whole grid apart and the halo came from HBM twice: dc_conv21 338 MB fetched for a 140 MB input)
   const int NB = (p.Cout + BN - 1) / BN;
@@ -544,11 +540,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int li = lane & 31, lh = lane >> 5;
   const int wn = sub % WN, wt = sub / WN, wty = wt / WTX, wtx = wt % WTX;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int bid = xcd_tile_order(blockIdx.x, gridDim.x);
   // the N blocks of one tile block are consecutive workgroups of ONE XCD: they read the same input halo out of that XCD's L2
   // (as blockIdx.y they ran a whole grid apart and the halo came from HBM twice: dc_conv21 338 MB fetched for a 140 MB input)
   const int NB = (p.Cout + BN - 1) / BN;
@@ -772,11 +764,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int role = wave >> 1, wn = wave & 1;
   const int li = lane & 31, lh = lane >> 5;
 
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, idx = bid >> 3;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int bid = xcd_tile_order(blockIdx.x, gridDim.x);
   const int NB = (p.Cout + BN - 1) / BN;
   const int nb = bid % NB;
   bid /= NB;
