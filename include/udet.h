@@ -137,6 +137,38 @@ int udet_restore_masks_ragged(const float* masks, int n, int mh, int mw, const l
                               int max_h, int max_w, unsigned char* data, int* amax, unsigned char* binary, double threshold,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Connected components of the restored masks and the choice of one per sample: the step post_processing/post_processing.py:32-35 names
+ * ("selects the best detection candidate from the set of predicted connected masks, by measuring overlap with the GT mask") and has no
+ * code for; the definition is this project's own.  binary: the packed device uint8 buffer udet_restore_masks_ragged writes (sample i =
+ * H_i x W_i bytes at offsets[i], device int64 [n]; any byte != 0 is foreground); hw: device int32 [n][2] = (H_i, W_i); gt: optional,
+ * packed the same way (!= 0: annotated).  Per sample:
+ *  - a component is a maximal 4- or 8-connected (`connectivity`) set of foreground pixels; its root is the smallest row-major index
+ *    y * W + x among its pixels.  labels (optional device int32, same offsets counted in elements): root + 1 on a foreground pixel, 0 on
+ *    background.  Ranking a sample's roots in ascending order gives scipy.ndimage.label's numbering.
+ *  - area = |C|, inter = |C & gt| (0 without gt), G = |gt| over the sample (0 without gt).
+ *  - mode UDET_COMPONENTS_LABEL: nothing is chosen.  UDET_COMPONENTS_LARGEST: the largest area, ties to the smaller root.
+ *    UDET_COMPONENTS_BEST_GT (needs gt): the largest IoU with the annotation inter / (area + G - inter), compared by 64-bit integer
+ *    cross-multiplication, ties to the larger area, then to the smaller root (no component touches the annotation: the largest one).
+ *  - selected (device uint8, packed like binary; may be NULL in mode LABEL): 1 on the chosen component, 0 elsewhere (all 0 for a
+ *    sample without foreground, and in mode LABEL).  info: device int64 [n][4] = {components, chosen root or -1, its area, its inter}.
+ * Exact integers, identical from run to run.  Five launches whatever n is: union-find in LDS on UDET_COMPONENTS_TILE_H x _TILE_W tiles,
+ * unions across tile edges and corners in global memory (agent-scope atomicMin, the larger root always under the smaller), flatten +
+ * area / inter per root, partial winners per workgroup, the final reduce + selected.  No workgroup waits for another.  max_h / max_w:
+ * the largest H_i / W_i (sizes the grid); total_pixels: the element count of the packed buffers (every offsets[i] + H_i * W_i lies
+ * within it); workspace: udet_components_workspace_bytes(total_pixels, n) bytes, 8-byte aligned.  Only the scalars and pointers are
+ * checked here (UDET_ERR_ARG -- connectivity not 4 / 8, an unknown mode, BEST_GT without gt, a selecting mode without selected, NULL
+ * binary / offsets / hw / info, n outside 1..65535, a short or misaligned workspace; nothing is enqueued on an error): the tables are
+ * device memory (native_results.check_component_tables validates offsets, overlap and H * W < 2^31 on the host before every launch). */
+#define UDET_COMPONENTS_LABEL 0
+#define UDET_COMPONENTS_LARGEST 1
+#define UDET_COMPONENTS_BEST_GT 2
+#define UDET_COMPONENTS_TILE_H 32
+#define UDET_COMPONENTS_TILE_W 64
+size_t udet_components_workspace_bytes(size_t total_pixels, int n);
+int udet_select_components_ragged(const unsigned char* binary, const unsigned char* gt, int n, const long long* offsets, const int* hw,
+                                  int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
+                                  unsigned char* selected, long long* info, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Post-processing stage ("next" row N4; post_processing/generate_soft_score_from_buffer.py, crf_refine.py).  The third-party
  * routines those scripts call are absent from the reference tree; each entry point names the routine it restates and the call
  * site that fixes its arguments.  Frames are small (192x384): one workgroup reductions, double accumulation like numpy float64.

@@ -8,6 +8,7 @@
   python -m unsupervised_detection_amd.cli restore_results --results_dir D --out_dir O --dataset ... --root_dir ...
                                                       [--test_partition val] [--test_temporal_shift 1] [--mask_key pred_mask|mask|soft_mask]
                                                       [--crop 0.9] [--threshold 0.5] [--keep_ends]         (crf_refine.py:84-97)
+                                                      [--component none|largest|best_gt] [--connectivity 4|8]  (post_processing.py:32-35)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
 davis_eval scores a folder of <sequence>/result_<k>.mat files (what test_generator --generate_visualization and the
@@ -15,7 +16,9 @@ post-processing stages write) against their gt_mask key the same way and writes 
 folder back to every frame's own size (the mask is the central --crop of the frame, the strip around it background), scores it there
 against the untouched annotations and writes O/<sequence>/<frame>.png (0 / 255, the DAVIS tools' layout), O/<sequence>/result_<k>.mat
 and O/native_eval.json; test_generator --native_resolution (with --generate_visualization --test_save_dir D) does the same for the
-masks it has just saved, into D/native.
+masks it has just saved, into D/native.  With --component largest / best_gt (both commands; default none) each restored mask is
+reduced to one connected component (--connectivity 4 or 8, default 8) before it is scored and written: the largest one, or the one
+whose IoU with the annotation is largest -- the "best detection candidate" of post_processing/post_processing.py:32-35.
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
 counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
@@ -125,11 +128,20 @@ def parse_restore_results_args(argv):
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--keep_ends", action="store_true", help="score the first and last frame of a sequence too")
+    ap.add_argument("--component", default="none", choices=("none", "largest", "best_gt"),
+                    help="keep one connected component of each restored mask: the largest, or the best IoU with the annotation")
+    ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8))
     a = ap.parse_args(argv)
     flags = default_flags()
     for k, v in vars(a).items():
         setattr(flags, k, v)
     return flags
+
+
+def _component(flags):
+    """--component as restore_results_dir takes it: None for "none"."""
+    c = getattr(flags, "component", "none")
+    return None if c in (None, "none") else c
 
 
 def check_native_flags(flags):
@@ -138,6 +150,8 @@ def check_native_flags(flags):
         raise SystemExit("--native_resolution requires --generate_visualization --test_save_dir D")
     if getattr(flags, "native_resolution", False) and getattr(flags, "synthetic", False):
         raise SystemExit("--native_resolution needs the annotations of a dataset (not --synthetic)")
+    if getattr(flags, "component", "none") not in ("none", "largest", "best_gt") or getattr(flags, "connectivity", 8) not in (4, 8):
+        raise SystemExit("--component is none, largest or best_gt and --connectivity 4 or 8")
 
 
 def main(argv=None):
@@ -149,7 +163,7 @@ def main(argv=None):
         a = parse_restore_results_args(argv[1:])
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
-                            batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends)
+                            batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity)
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -176,7 +190,8 @@ def main(argv=None):
         if flags.native_resolution:
             from .native_results import frame_lists_from_reader, restore_results_dir
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
-                                mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset)
+                                mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
+                                connectivity=flags.connectivity)
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

@@ -31,6 +31,10 @@ _DEFS = [
     # not a reference flag: after test_generator --generate_visualization --test_save_dir D, restore the saved masks to every frame's
     # own size (test_crop pasted into a zero canvas), score them there and export them under D/native (native_results.py)
     ("native_resolution", bool, False),
+    # not reference flags: with --native_resolution, keep one connected component of every restored mask before it is scored and
+    # exported -- none | largest | best_gt (the best IoU with the annotation: post_processing.py:32-35) -- under 4- or 8-connectivity
+    ("component", str, "none"),
+    ("connectivity", int, 8),
 ]
 
 

@@ -132,6 +132,46 @@ int udet_restore_masks_ragged(const float* masks, int n, int mh, int mw, const l
                                      (hipStream_t)stream);
 }
 
+size_t udet_components_workspace_bytes(size_t total_pixels, int n) {
+  return (n < 1 || total_pixels < 1) ? 0 : components_workspace_bytes(total_pixels, n);
+}
+int udet_select_components_ragged(const unsigned char* binary, const unsigned char* gt, int n, const long long* offsets, const int* hw,
+                                  int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
+                                  unsigned char* selected, long long* info, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n < 1 || n > 65535 || max_h < 1 || max_w < 1 || (long)max_h * max_w > 0x7fffffffL || total_pixels < 1 || !binary || !offsets || !hw ||
+      !info) {
+    set_error("select_components_ragged: bad argument (n = %d in 1..65535, largest frame %d x %d below 2^31 pixels, %zu pixels in all, "
+              "non-null binary, offsets, hw and info)", n, max_h, max_w, total_pixels);
+    return UDET_ERR_ARG;
+  }
+  if (connectivity != 4 && connectivity != 8) {
+    set_error("select_components_ragged: connectivity %d is neither 4 nor 8", connectivity);
+    return UDET_ERR_ARG;
+  }
+  if (mode != UDET_COMPONENTS_LABEL && mode != UDET_COMPONENTS_LARGEST && mode != UDET_COMPONENTS_BEST_GT) {
+    set_error("select_components_ragged: mode %d is none of UDET_COMPONENTS_LABEL / _LARGEST / _BEST_GT", mode);
+    return UDET_ERR_ARG;
+  }
+  if (mode == UDET_COMPONENTS_BEST_GT && !gt) {
+    set_error("select_components_ragged: UDET_COMPONENTS_BEST_GT needs the annotation (gt)");
+    return UDET_ERR_ARG;
+  }
+  if ((mode != UDET_COMPONENTS_LABEL && !selected) || (selected && (selected == binary || selected == gt))) {
+    set_error("select_components_ragged: a selecting mode needs `selected`, a buffer of its own");
+    return UDET_ERR_ARG;
+  }
+  if (!workspace || workspace_bytes < components_workspace_bytes(total_pixels, n) || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
+    set_error("select_components_ragged: workspace needs %zu bytes, 8-byte aligned", components_workspace_bytes(total_pixels, n));
+    return UDET_ERR_ARG;
+  }
+  if (reinterpret_cast<uintptr_t>(labels) & 3) {
+    set_error("select_components_ragged: labels must be 4-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_select_components_ragged(binary, gt, n, offsets, hw, max_h, max_w, total_pixels, connectivity, mode, labels, selected, info,
+                                         workspace, (hipStream_t)stream);
+}
+
 size_t udet_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int kh, int kw, int upsample2x) {
   const int kc = round_up(cin > cout ? cin : cout, 8), ldw = round_up(cin > cout ? cin : cout, 4);
   const size_t pix_in = (size_t)n * h * w, pix_out = pix_in * (upsample2x ? 4 : 1);

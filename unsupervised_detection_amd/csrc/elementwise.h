@@ -48,6 +48,11 @@ size_t restore_workspace_bytes(int n);
 int launch_restore_masks_ragged(const float* masks, int n, int mh, int mw, const long long* offsets, const int* tab, const int* coef,
                                 int max_h, int max_w, unsigned char* out, int* amax, unsigned char* binary, double threshold,
                                 void* workspace, hipStream_t s);
+// components.hip: udet_select_components_ragged (arguments already checked)
+size_t components_workspace_bytes(size_t total_pixels, int n);
+int launch_select_components_ragged(const unsigned char* binary, const unsigned char* gt, int n, const long long* offsets, const int* hw,
+                                    int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
+                                    unsigned char* selected, long long* info, void* workspace, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
 int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet

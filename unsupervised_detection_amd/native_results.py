@@ -10,11 +10,15 @@ post_processing/post_processing.py:32-46:
   restore_box(H, W, crop)                       the patch's box (y0, x0, h, w) inside an H x W frame
   build_restore_tables / check_restore_tables   the host tables of udet_restore_masks_ragged and their validation (no GPU needed)
   restore_masks(masks, native_hw, ...)          one call of the ragged kernel (csrc/restore.hip) -> RestoredMasks
-  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore + J / F + <sequence>/<frame>.png, result_<k>.mat, native_eval.json
+  select_components(binary, offsets, hw, gt, mode, ...)   connected components of the restored masks and the choice of one per sample
+                                                (csrc/components.hip, udet_select_components_ragged) -> ComponentSelection
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ component selection] + J / F + <sequence>/<frame>.png,
+                                                result_<k>.mat, native_eval.json
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order
 
-scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  Not here: the full-resolution
-CRF (sxy = 60) and the "best connected candidate" the reference only mentions in a comment."""
+scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  The "best detection candidate from
+the set of predicted connected masks" the reference only mentions in a comment (post_processing.py:32-35) is select_components
+(DESIGN.md 7.3).  Not here: the full-resolution CRF (sxy = 60)."""
 from __future__ import annotations
 
 import ctypes
@@ -30,6 +34,10 @@ lib.udet_restore_workspace_bytes.restype = c_sz
 lib.udet_restore_workspace_bytes.argtypes = [c_i]
 lib.udet_restore_masks_ragged.restype = c_i
 lib.udet_restore_masks_ragged.argtypes = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, c_p, c_sz, c_p]
+lib.udet_components_workspace_bytes.restype = c_sz
+lib.udet_components_workspace_bytes.argtypes = [c_sz, c_i]
+lib.udet_select_components_ragged.restype = c_i
+lib.udet_select_components_ragged.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]
 
 TAB = 12  # int32 per sample: y0 x0 h w H W | hk hb hks | vk vb vks   (include/udet.h)
 
@@ -309,8 +317,111 @@ def _host(x):
     return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Connected components and the choice of one candidate per sample (csrc/components.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+COMPONENT_MODES = {"label": 0, "largest": 1, "best_gt": 2}  # UDET_COMPONENTS_LABEL / _LARGEST / _BEST_GT (include/udet.h)
+COMPONENT_TILE = (32, 64)  # UDET_COMPONENTS_TILE_H / _W: the tile of the LDS union-find
+
+
+def check_component_tables(offsets, hw, numel):
+    """Host validation of the device tables of udet_select_components_ragged, by check_restore_tables' rules: raises ValueError on a
+    sample outside the packed buffer of `numel` elements, overlapping samples or a frame of 2^31 pixels or more.  Returns (offsets
+    int64 [n], hw int32 [n,2]) as the kernels read them."""
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    size = np.asarray(hw, dtype=np.int64).reshape(-1, 2)
+    if len(off) < 1 or len(size) != len(off):
+        raise ValueError("components need at least one sample and one (H, W) per offset")
+    H, W = size[:, 0], size[:, 1]
+    if (H < 1).any() or (W < 1).any() or (H * W > np.iinfo(np.int32).max).any():
+        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
+    if (off < 0).any() or (off + H * W > numel).any():
+        raise ValueError("sample outside the packed buffer (offset + H*W past its end)")
+    order = np.argsort(off, kind="stable")
+    if (off[order][1:] < (off + H * W)[order][:-1]).any():
+        raise ValueError("samples overlap in the packed buffer")
+    return off, np.ascontiguousarray(size.astype(np.int32))
+
+
+class ComponentSelection(object):
+    """Result of select_components: selected (packed uint8 0 / 1, device; None in mode "label"), labels (packed int32, root + 1 /
+    0, or None), info (device int64 [n,4] = components, chosen root or -1, its area, its inter), host offsets [n] / hw [n,2].
+    binary_sample / stack have the contract of RestoredMasks: the scoring and export loops take either."""
+
+    def __init__(self, selected, labels, info, offsets, hw):
+        self.selected, self.labels, self.info, self.offsets, self.hw = selected, labels, info, offsets, hw
+
+    def __len__(self):
+        return len(self.offsets)
+
+    _view = RestoredMasks._view
+
+    def binary_sample(self, i):
+        if self.selected is None:
+            raise ValueError("labelled without a selection: no selected mask")
+        return self._view(self.selected, i)
+
+    def labels_sample(self, i):
+        if self.labels is None:
+            raise ValueError("selected without want_labels: no labels")
+        return self._view(self.labels, i)
+
+    stack = RestoredMasks.stack
+
+
+def select_components(binary, offsets=None, hw=None, gt=None, mode="largest", connectivity=8, want_labels=False) -> ComponentSelection:
+    """Connected components of n packed binary masks and one of them chosen per sample, in one call of
+    udet_select_components_ragged (five launches whatever n is).  binary: a RestoredMasks (its binary masks, offsets and sizes), or a
+    1-D uint8 device tensor with host offsets [n] / hw [n,2]; gt: a GtBatch or a 1-D uint8 device tensor packed like binary, or
+    None.  connectivity 4 or 8.  mode "label": components only; "largest": the largest component, ties to the smaller root (the
+    smallest row-major index of the component); "best_gt": the largest IoU with gt, ties to the larger area, then the smaller root.
+    want_labels: also the int32 labels (root + 1, background 0; the roots in ascending order number as scipy.ndimage.label does).
+    Arguments and tables are validated on the host before the device is touched (ValueError)."""
+    if isinstance(binary, RestoredMasks):
+        if binary.binary is None:
+            raise ValueError("restored without a threshold: no binary mask")
+        binary, offsets, hw = binary.binary, binary.offsets, binary.hw
+    if offsets is None or hw is None:
+        raise ValueError("a packed buffer needs its offsets and sizes")
+    if mode not in COMPONENT_MODES:
+        raise ValueError("mode must be one of {}".format(sorted(COMPONENT_MODES)))
+    if connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    if not isinstance(binary, torch.Tensor) or binary.dtype != torch.uint8 or binary.dim() != 1:
+        raise ValueError("binary must be a 1-D uint8 tensor of packed samples")
+    total = int(binary.numel())
+    off, size = check_component_tables(offsets, hw, total)
+    if isinstance(gt, GtBatch):
+        g_off, g_hw = check_component_tables(gt.offsets, gt.hw, total)
+        if not (np.array_equal(g_off, off) and np.array_equal(g_hw, size)):
+            raise ValueError("the annotations must be packed like the masks (same offsets and sizes)")
+        gt = gt.data
+    if mode == "best_gt" and gt is None:
+        raise ValueError('mode "best_gt" needs the annotations')
+    if gt is not None and not (isinstance(gt, torch.Tensor) and gt.dtype == torch.uint8 and gt.dim() == 1 and gt.numel() == total):
+        raise ValueError("gt must be a 1-D uint8 tensor packed like binary")
+    for buf, name in ((binary, "binary"), (gt, "gt")):
+        if buf is not None and not (buf.is_cuda and buf.is_contiguous()):
+            raise ValueError("{} must be a contiguous CUDA(HIP) tensor".format(name))
+    dev, n = binary.device, len(off)
+    if gt is not None and gt.device != dev:
+        raise ValueError("gt must be on the device of binary")
+    from .data import _upload_tables
+    d_off, d_hw = _upload_tables([off, size], dev)
+    selected = torch.empty(total, dtype=torch.uint8, device=dev) if mode != "label" else None
+    labels = torch.empty(total, dtype=torch.int32, device=dev) if want_labels else None
+    info = torch.empty((n, 4), dtype=torch.int64, device=dev)
+    ws = torch.empty((int(lib.udet_components_workspace_bytes(total, n)) + 7) // 8, dtype=torch.int64, device=dev)
+    check(lib.udet_select_components_ragged(binary.data_ptr(), None if gt is None else gt.data_ptr(), n, d_off.data_ptr(), d_hw.data_ptr(),
+                                            int(size[:, 0].max()), int(size[:, 1].max()), total, int(connectivity), COMPONENT_MODES[mode],
+                                            None if labels is None else labels.data_ptr(), None if selected is None else selected.data_ptr(),
+                                            info.data_ptr(), ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream))
+    return ComponentSelection(selected, labels, info, off, size)
+
+
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
-                        gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True):
+                        gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True,
+                        component=None, connectivity=8, select=select_components):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -320,7 +431,11 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     (evaluation.evaluate_batch_davis, disambiguate=False).  Writes <out_dir>/<category>/<frame stem>.png (8-bit, 0 / 255),
     <out_dir>/<category>/result_<k>.mat (mask uint8 0 / 1, soft_mask float32, gt_mask uint8 0 / 1: `davis_eval --results_dir
     <out_dir> --mask_key mask` reads them unchanged) and <out_dir>/native_eval.json; returns the json's content.
-    restore / load_gt / score are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    component "largest" / "best_gt" (None: off): the restored binary masks of each batch go through one call of select
+    (select_components; "best_gt" together with the batch's annotations), and the selected component is what is scored, written to
+    the .png and stored as `mask`; soft_mask and gt_mask stay as they are, and the json gains "component", "connectivity" and per
+    sequence "components_mean" (the mean number of components per frame).
+    restore / load_gt / score / select are injectable: the host logic runs without a GPU on numpy stand-ins."""
     import json
     import re
     import scipy.io as sio
@@ -329,7 +444,11 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     bound_th = BOUND_TH if bound_th is None else bound_th
     rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
     batch = max(1, int(batch))
-    cat_j, cat_f = {}, {}
+    if component not in (None, "largest", "best_gt"):
+        raise ValueError('component must be None, "largest" or "best_gt"')
+    if component is not None and connectivity not in (4, 8):
+        raise ValueError("connectivity must be 4 or 8")
+    cat_j, cat_f, cat_nc = {}, {}, {}
     for cat, entries in frame_lists.items():
         d = os.path.join(results_dir, cat)
         ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
@@ -337,7 +456,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             raise IOError("category {!r}: {} result_<k>.mat under {!r} for {} listed frames".format(cat, len(ks), d, len(entries)))
         od = os.path.join(out_dir, cat)
         os.makedirs(od, exist_ok=True)
-        j, f = np.empty(len(entries)), np.empty(len(entries))
+        j, f, nc = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries))
         for s in range(0, len(entries), batch):
             rows = entries[s:s + batch]
             masks = []
@@ -350,17 +469,21 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                     raise ValueError("{}: result_{}.mat: masks must be 2-D and of one shape".format(d, k))
             gt = load_gt([a for _, a in rows], rule)
             res = restore(np.stack(masks), gt.hw, crop, threshold)
+            pred = res  # what is scored and exported as the binary mask
+            if component is not None:
+                pred = select(res, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity)
+                nc[s:s + len(rows)] = _host(pred.info)[:, 0]
             shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
             for shape in sorted(set(shapes)):
                 idx = [i for i, sh in enumerate(shapes) if sh == shape]
-                jj, ff = score(gt.stack(idx), res.stack(idx), bound_th)
+                jj, ff = score(gt.stack(idx), pred.stack(idx), bound_th)
                 j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
             for i, (img, _) in enumerate(rows):
-                binm = _host(res.binary_sample(i)).astype(np.uint8)
+                binm = _host(pred.binary_sample(i)).astype(np.uint8)
                 Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, os.path.splitext(os.path.basename(img))[0] + ".png"))
                 sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)),
                             {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32), "gt_mask": _host(gt.sample(i)).astype(np.uint8)})
-        cat_j[cat], cat_f[cat] = j.tolist(), f.tolist()
+        cat_j[cat], cat_f[cat], cat_nc[cat] = j.tolist(), f.tolist(), float(nc.mean()) if len(nc) else 0.0
     if not cat_j:
         raise IOError("no category to restore")
     per, tot = _davis_summary(cat_j, cat_f, skip_ends)
@@ -368,6 +491,10 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     out = {"mask_key": mask_key, "threshold": threshold, "crop": crop, "bound_th": bound_th, "skip_ends": bool(skip_ends),
            "sequences": {c: dict(per[c], frames=len(cat_j[c])) for c in per}, "J": tot["J"], "F": tot["F"], "J&F": tot["J&F"],
            "category_iou": cat_iou, "sequence_iou": _nanmean(list(cat_iou.values()))}
+    if component is not None:
+        out["component"], out["connectivity"] = component, int(connectivity)
+        for c in out["sequences"]:
+            out["sequences"][c]["components_mean"] = cat_nc[c]
     if verbose:
         print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
         _print_davis_table(per, tot)
