@@ -169,6 +169,42 @@ int udet_select_components_ragged(const unsigned char* binary, const unsigned ch
                                   int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
                                   unsigned char* selected, long long* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Dense CRF of a ragged batch at each frame's own size: step 2 of post_processing/crf_refine.py:65-108 run_crf_original_resolution
+ * (DenseCRF2D + setUnaryEnergy + addPairwiseBilateral(sxy, srgb, rgbim, compat) + inference(iters) on the untouched frame).  Packed
+ * layout of the two calls above: sample i = H_i x W_i elements at element offset offsets[i] (device int64 [n]); hw: device int32 [n][2].
+ * image_rgb: device uint8, 3 bytes per element (sample i at byte 3 * offsets[i]); unary: device float32 [2][total_pixels], the energies
+ * of label 0 and of label 1.  Per sample, exactly the definition of udet_post_dense_crf (Kraehenbuehl & Koltun 2011, one bilateral
+ * Potts term, symmetric normalisation; samples do not interact):
+ *   k_ij = exp(-(|dp|^2 / sxy^2 + |dI|^2 / srgb^2) / 2)  for |dy|, |dx| <= radius, j != i, j inside the frame (a square window)
+ *   n_i = 1 / sqrt(sum_j k_ij + 1e-20);  Q <- softmax(-unary);  iters times: Q <- softmax(-unary + compat * n * K (n * Q))
+ * iters = 0 returns softmax(-unary).  q1 (optional, device float32, packed): the marginal of label 1 (Q0 = 1 - Q1).  labels (optional,
+ * device uint8, packed like `binary` above, so it feeds udet_select_components_ragged and the scoring kernels unchanged): 1 where
+ * Q1 > Q0 strictly (np.argmax: ties to 0).  At least one of the two.  Elements of q1 / labels between the samples are not written.
+ * iters + 2 launches of one kernel whatever n is (K 1 -> n; K n with the first softmax; one launch per iteration whose epilogue does
+ * the softmax update and writes n * Q1 into the other of two field buffers): 64-column tiles of each frame, the window walked in
+ * strips staged in LDS (16 KiB whatever the radius; zeros outside the frame, so the inner loop has no bounds checks), several targets
+ * per thread, the exponent as FMAs + one v_exp_f32, the tap j = i excluded by construction.  No atomics, no workgroup waits for
+ * another, a fixed summation order per pixel: bit-identical from run to run and between a sample alone and inside a batch.
+ * max_h / max_w: the largest H_i / W_i (sizes the grid); workspace: udet_dense_crf_workspace_bytes(total_pixels, n) bytes, 16-byte
+ * aligned.  Only the scalars and pointers are checked here (UDET_ERR_ARG -- n outside 1..65535, iters < 0, radius < 1, sxy or
+ * srgb <= 0, NULL unary / image_rgb / offsets / hw, both outputs NULL, a short or misaligned workspace; nothing is enqueued on an
+ * error): the tables are device memory (native_results.check_crf_tables validates offsets, overlap and H * W < 2^31 on the host before
+ * every launch).
+ * udet_dense_crf_rows_per_thread: the rows of a tile each thread of that call holds (tiles are 64 columns x 4 times that many rows): the one
+ * of 1, 2, 4 with the smallest estimated time max(2, ceil(workgroups of the grid of (max_h, max_w, n) / 256)) x cost per workgroup
+ * (52, 66, 120), ties to the larger -- small batches get short tiles, large ones the packed forms; 0 for a bad argument.  The results do not depend on
+ * it, bit for bit (tests/test_crf_native_gpu.py runs all three on the same samples).
+ * udet_crf_unary_lookup: unary[l][offsets[i] + k] = table[i][l][data[offsets[i] + k]] -- the unary of crf_refine.py:113-121 from the
+ * restored bytes of udet_restore_masks_ragged (`data`); table: device float32 [n][2][256], built by the host in float64
+ * (post_processing.unary_table). */
+size_t udet_dense_crf_workspace_bytes(size_t total_pixels, int n);
+int udet_dense_crf_rows_per_thread(int n, int max_h, int max_w);
+int udet_dense_crf_ragged(const float* unary, const unsigned char* image_rgb, int n, const long long* offsets, const int* hw, int max_h,
+                          int max_w, size_t total_pixels, float sxy, float srgb, float compat, int iters, int radius, float* q1,
+                          unsigned char* labels, void* workspace, size_t workspace_bytes, void* stream);
+int udet_crf_unary_lookup(const unsigned char* data, const float* table, int n, const long long* offsets, const int* hw, int max_h,
+                          int max_w, size_t total_pixels, float* unary, void* stream);
+
 /* Post-processing stage ("next" row N4; post_processing/generate_soft_score_from_buffer.py, crf_refine.py).  The third-party
  * routines those scripts call are absent from the reference tree; each entry point names the routine it restates and the call
  * site that fixes its arguments.  Frames are small (192x384): one workgroup reductions, double accumulation like numpy float64.

@@ -9,6 +9,8 @@
                                                       [--test_partition val] [--test_temporal_shift 1] [--mask_key pred_mask|mask|soft_mask]
                                                       [--crop 0.9] [--threshold 0.5] [--keep_ends]         (crf_refine.py:84-97)
                                                       [--component none|largest|best_gt] [--connectivity 4|8]  (post_processing.py:32-35)
+                                                      [--crf] [--sxy 60] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_iters 50]
+                                                      [--crf_radius R]                                      (crf_refine.py:65-108)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
 davis_eval scores a folder of <sequence>/result_<k>.mat files (what test_generator --generate_visualization and the
@@ -18,7 +20,11 @@ against the untouched annotations and writes O/<sequence>/<frame>.png (0 / 255, 
 and O/native_eval.json; test_generator --native_resolution (with --generate_visualization --test_save_dir D) does the same for the
 masks it has just saved, into D/native.  With --component largest / best_gt (both commands; default none) each restored mask is
 reduced to one connected component (--connectivity 4 or 8, default 8) before it is scored and written: the largest one, or the one
-whose IoU with the annotation is largest -- the "best detection candidate" of post_processing/post_processing.py:32-35.
+whose IoU with the annotation is largest -- the "best detection candidate" of post_processing/post_processing.py:32-35.  With --crf
+(both commands) the restored soft mask of every frame is first refined by the dense CRF on the untouched frame at its own size
+(crf_refine.run_crf_original_resolution; --sxy / --srgb / --scomp / --gauss_k default to post_processing.py:24-28,40, --crf_radius to
+ceil(3 sxy)), and the CRF's labels are what is selected from, scored and written.  The reference's whole benchmark pass is run_crf
+followed by `restore_results --mask_key soft_mask --crf --component best_gt`.
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
 counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
@@ -131,6 +137,13 @@ def parse_restore_results_args(argv):
     ap.add_argument("--component", default="none", choices=("none", "largest", "best_gt"),
                     help="keep one connected component of each restored mask: the largest, or the best IoU with the annotation")
     ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8))
+    ap.add_argument("--crf", action="store_true", help="refine every restored mask by the dense CRF on the frame at its own size")
+    ap.add_argument("--sxy", type=float, default=60.0)
+    ap.add_argument("--srgb", type=float, default=5.0)
+    ap.add_argument("--scomp", type=float, default=5.0)
+    ap.add_argument("--gauss_k", type=float, default=0.1)
+    ap.add_argument("--crf_iters", type=int, default=50)
+    ap.add_argument("--crf_radius", type=int, default=0, help="window radius of the CRF's kernel; 0: ceil(3 sxy)")
     a = ap.parse_args(argv)
     flags = default_flags()
     for k, v in vars(a).items():
@@ -142,6 +155,14 @@ def _component(flags):
     """--component as restore_results_dir takes it: None for "none"."""
     c = getattr(flags, "component", "none")
     return None if c in (None, "none") else c
+
+
+def _crf(flags):
+    """--crf and its parameters as restore_results_dir takes them: None without --crf."""
+    if not getattr(flags, "crf", False):
+        return None
+    return {"sxy": flags.sxy, "srgb": flags.srgb, "compat": flags.scomp, "gauss_k": flags.gauss_k, "iters": flags.crf_iters,
+            "radius": flags.crf_radius if flags.crf_radius > 0 else None}
 
 
 def check_native_flags(flags):
@@ -163,7 +184,8 @@ def main(argv=None):
         a = parse_restore_results_args(argv[1:])
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
-                            batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity)
+                            batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
+                            crf=_crf(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -191,7 +213,7 @@ def main(argv=None):
             from .native_results import frame_lists_from_reader, restore_results_dir
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
-                                connectivity=flags.connectivity)
+                                connectivity=flags.connectivity, crf=_crf(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

@@ -35,6 +35,16 @@ _DEFS = [
     # exported -- none | largest | best_gt (the best IoU with the annotation: post_processing.py:32-35) -- under 4- or 8-connectivity
     ("component", str, "none"),
     ("connectivity", int, 8),
+    # not reference flags: with --native_resolution, --crf runs the reference's full-resolution pass on the restored masks
+    # (crf_refine.run_crf_original_resolution; defaults of post_processing.py:24-28,40): the dense CRF on every frame at its own size;
+    # crf_radius 0 = ceil(3 sxy)
+    ("crf", bool, False),
+    ("sxy", float, 60.0),
+    ("srgb", float, 5.0),
+    ("scomp", float, 5.0),
+    ("gauss_k", float, 0.1),
+    ("crf_iters", int, 50),
+    ("crf_radius", int, 0),
 ]
 
 

@@ -12,13 +12,16 @@ post_processing/post_processing.py:32-46:
   restore_masks(masks, native_hw, ...)          one call of the ragged kernel (csrc/restore.hip) -> RestoredMasks
   select_components(binary, offsets, hw, gt, mode, ...)   connected components of the restored masks and the choice of one per sample
                                                 (csrc/components.hip, udet_select_components_ragged) -> ComponentSelection
-  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ component selection] + J / F + <sequence>/<frame>.png,
-                                                result_<k>.mat, native_eval.json
+  check_crf_tables / load_images_device / crf_refine_restored   the full-resolution dense CRF of run_crf_original_resolution on the
+                                                restored batch: unary from the restored bytes, the frames read at their own size,
+                                                one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] + J / F +
+                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order
 
 scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  The "best detection candidate from
 the set of predicted connected masks" the reference only mentions in a comment (post_processing.py:32-35) is select_components
-(DESIGN.md 7.3).  Not here: the full-resolution CRF (sxy = 60)."""
+(DESIGN.md 7.3).  The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...})."""
 from __future__ import annotations
 
 import ctypes
@@ -419,9 +422,65 @@ def select_components(binary, offsets=None, hw=None, gt=None, mode="largest", co
     return ComponentSelection(selected, labels, info, off, size)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The dense CRF at native resolution (csrc/crf.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+CRF_KEYS = ("sxy", "srgb", "compat", "gauss_k", "iters", "radius")
+
+
+def check_crf_tables(offsets, hw, numel):
+    """Host validation of the device tables of udet_dense_crf_ragged / udet_crf_unary_lookup, by check_component_tables' rules:
+    raises ValueError on a sample outside the packed buffers of `numel` elements, overlapping samples or a frame of 2^31 pixels or
+    more.  Returns (offsets int64 [n], hw int32 [n,2]) as the kernels read them."""
+    if len(np.asarray(offsets).reshape(-1)) > 65535:
+        raise ValueError("at most 65535 samples per call")
+    return check_component_tables(offsets, hw, numel)
+
+
+def crf_params(crf):
+    """The `crf` dict of restore_results_dir with its defaults filled in (iters 50, radius ceil(3 sxy)) and checked (ValueError)."""
+    from .post_processing import default_radius
+    if not isinstance(crf, dict) or not {"sxy", "srgb", "compat", "gauss_k"} <= set(crf) or not set(crf) <= set(CRF_KEYS):
+        raise ValueError("crf must be a dict with sxy, srgb, compat, gauss_k and optionally iters, radius")
+    p = {k: float(crf[k]) for k in ("sxy", "srgb", "compat", "gauss_k")}
+    p["iters"] = 50 if crf.get("iters") is None else int(crf["iters"])
+    p["radius"] = default_radius(p["sxy"]) if crf.get("radius") is None else int(crf["radius"])
+    if not (p["sxy"] > 0 and p["srgb"] > 0 and p["gauss_k"] >= 0 and p["iters"] >= 0 and p["radius"] >= 1):
+        raise ValueError("crf: sxy, srgb > 0, gauss_k >= 0, iters >= 0 and radius >= 1 are required")
+    return p
+
+
+def load_images_device(paths):
+    """The frames of a batch at their own size through data.RaggedLoader (mixed sizes: one pinned buffer, one copy) -> RaggedBatch
+    (data: packed rgb bytes on the device, offsets in bytes)."""
+    global _ragged_loader
+    from . import data
+    if _ragged_loader is None:
+        _ragged_loader = data.RaggedLoader()
+    return _ragged_loader.load(list(paths), 3)
+
+
+def crf_refine_restored(res, images, crf) -> RestoredMasks:
+    """refine (crf_refine.py:110-130) of a restored batch at native size: the unary from the restored bytes
+    (post_processing.unary_from_restored), the dense CRF on the frames `images` (a RaggedBatch of rgb frames in the order and of the
+    sizes of res; they stay on the device) in one call of post_processing.dense_crf_ragged.  Returns res with the CRF's labels in
+    the place of the thresholded binary masks."""
+    from .post_processing import dense_crf_ragged, unary_from_restored
+    p = crf_params(crf)
+    if not np.array_equal(np.asarray(images.hw, np.int64), np.asarray(res.hw, np.int64)):
+        raise ValueError("the frames and their annotations differ in size")
+    if not np.array_equal(np.asarray(images.offsets, np.int64), 3 * np.asarray(res.offsets, np.int64)) or images.data.numel() != 3 * res.data.numel():
+        raise ValueError("the frames must be packed like the restored masks")
+    unary = unary_from_restored(res.data, res.offsets, res.hw, res.amax, p["gauss_k"])
+    _, labels = dense_crf_ragged(unary, images.data, res.offsets, res.hw, p["sxy"], p["srgb"], p["compat"], p["iters"], p["radius"],
+                                 want_q=False, want_labels=True)
+    return RestoredMasks(res.data, labels, res.offsets, res.hw, res.amax)
+
+
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
                         gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True,
-                        component=None, connectivity=8, select=select_components):
+                        component=None, connectivity=8, select=select_components, crf=None, load_images=load_images_device,
+                        refine=crf_refine_restored):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -435,7 +494,13 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     (select_components; "best_gt" together with the batch's annotations), and the selected component is what is scored, written to
     the .png and stored as `mask`; soft_mask and gt_mask stay as they are, and the json gains "component", "connectivity" and per
     sequence "components_mean" (the mean number of components per frame).
-    restore / load_gt / score / select are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    crf (None: off): a dict with sxy, srgb, compat, gauss_k and optionally iters (50), radius (ceil(3 sxy)) -- the full-resolution
+    pass of crf_refine.run_crf_original_resolution.  The batch's frames are read at their own size (load_images(paths), in the list's
+    order) and refine(restored, frames, crf) (crf_refine_restored: unary from the restored bytes + one dense-CRF call for the batch)
+    returns the restored batch with the CRF's labels as its binary masks; they take the place of the thresholded masks for
+    everything downstream (component selection, J / F, the .png, `mask`); soft_mask stays the restored soft mask and the json gains
+    "crf" with the parameters used.
+    restore / load_gt / score / select / load_images / refine are injectable: the host logic runs without a GPU on numpy stand-ins."""
     import json
     import re
     import scipy.io as sio
@@ -448,6 +513,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         raise ValueError('component must be None, "largest" or "best_gt"')
     if component is not None and connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8")
+    crf = None if crf is None else crf_params(crf)
     cat_j, cat_f, cat_nc = {}, {}, {}
     for cat, entries in frame_lists.items():
         d = os.path.join(results_dir, cat)
@@ -470,8 +536,10 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             gt = load_gt([a for _, a in rows], rule)
             res = restore(np.stack(masks), gt.hw, crop, threshold)
             pred = res  # what is scored and exported as the binary mask
+            if crf is not None:
+                pred = refine(res, load_images([img for img, _ in rows]), crf)
             if component is not None:
-                pred = select(res, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity)
+                pred = select(pred, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity)
                 nc[s:s + len(rows)] = _host(pred.info)[:, 0]
             shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
             for shape in sorted(set(shapes)):
@@ -495,6 +563,8 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         out["component"], out["connectivity"] = component, int(connectivity)
         for c in out["sequences"]:
             out["sequences"][c]["components_mean"] = cat_nc[c]
+    if crf is not None:
+        out["crf"] = crf
     if verbose:
         print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
         _print_davis_table(per, tot)

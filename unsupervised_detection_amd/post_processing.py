@@ -6,6 +6,8 @@ meaning as post_processing/generate_soft_score_from_buffer.py and post_processin
   propagate(...)    flow-guided moving average of the masks       :127-231 (pyflow.so -> the path's own PWC-Net flow; cv2.remap -> udet_post_remap)
   refine(...) / select_candidate(...)                             crf_refine.py:110-138, :40-50
   buffer_to_soft_score(buffer_path, out_path, ...) / run_crf(...)  the file-level drivers over the .mat buffers the ensemble run writes
+  dense_crf_ragged(...) / unary_from_restored(...) / run_crf_original_resolution(...)   crf_refine.py:65-108: the CRF on every frame at
+                    its own size, a ragged batch per call (csrc/crf.hip)
 
 The kernels of the stage -- border statistics, bytescale, Pillow's 8-bit resampler, canvas placement, min-max / max
 normalisations, remap, blending, the separable Gaussian and the dense-CRF mean field -- run in libudet.so (csrc/postproc.hip); torch
@@ -37,6 +39,15 @@ for _n, _a in (("udet_post_border_mean", [c_p, c_i, c_i, c_i, c_p, c_p]),
     getattr(lib, _n).argtypes = _a
 lib.udet_post_crf_workspace_bytes.restype = c_sz
 lib.udet_post_crf_workspace_bytes.argtypes = [c_i, c_i]
+# the dense CRF of a ragged batch at native resolution (csrc/crf.hip)
+lib.udet_dense_crf_workspace_bytes.restype = c_sz
+lib.udet_dense_crf_workspace_bytes.argtypes = [c_sz, c_i]
+lib.udet_dense_crf_ragged.restype = c_i
+lib.udet_dense_crf_ragged.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]
+lib.udet_dense_crf_rows_per_thread.restype = c_i
+lib.udet_dense_crf_rows_per_thread.argtypes = [c_i, c_i, c_i]
+lib.udet_crf_unary_lookup.restype = c_i
+lib.udet_crf_unary_lookup.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p]
 
 
 def _stream():
@@ -281,6 +292,106 @@ def refine(mask, image, gk, sxy, srgb, compat, gtmask, iters=50, radius=None):
     new_mask = (Q[1] > Q[0]).float().cpu().numpy()  # np.argmax(Q, axis=0): label 1 only where strictly larger
     gt, bm = np.asarray(gtmask) > 0.1, new_mask > 0.1
     return new_mask, np.float32(np.sum(gt & bm)) / np.float32(np.sum(gt | bm))
+
+
+# ------------------------------------------------------------------------------------- CRF at native resolution ----
+def default_radius(sxy):
+    """The window radius of the truncated Gaussian: ceil(3 sxy)."""
+    return int(math.ceil(3.0 * float(sxy)))
+
+
+def unary_table(amax):
+    """crf_refine.py:93-97,113-121 with the reference's gauss_k = 0.1 (a Gaussian of radius int(4 gauss_k + 0.5) = 0: the identity) as
+    a function of the restored byte: the soft value is byte / (amax + 1e-8), its maximum amax / (amax + 1e-8), so
+    U = soft / (max + 1e-8), clipped to [1e-6, 1 - 1e-6], and the energies -log(1 - U), -log(U).  amax: int [n] (the largest byte of
+    each sample) -> float32 [n,2,256], computed in float64 with numpy like oracle_post.unary_from_mask.  amax = 0 (a constant mask):
+    U = 1e-6 everywhere."""
+    a = np.asarray(amax, dtype=np.float64).reshape(-1, 1)
+    soft = np.arange(256, dtype=np.float64)[None, :] / (a + 1e-8)
+    U = soft / (a / (a + 1e-8) + 1e-8)
+    U = np.clip(U, 1e-6, 1.0 - 1e-6)
+    return np.ascontiguousarray(np.float32(-np.log(np.stack([1.0 - U, U], 1))))
+
+
+def _crf_tables(offsets, hw, total, device):
+    from .data import _upload_tables
+    from .native_results import check_crf_tables
+    off, size = check_crf_tables(offsets, hw, total)  # before the device is touched
+    d_off, d_hw = _upload_tables([off, size], device)
+    return off, size, d_off, d_hw
+
+
+def unary_from_restored(data, offsets, hw, amax, gauss_k=0.1):
+    """The unary energies of refine (crf_refine.py:113-121) for the packed restored bytes `data` (1-D uint8 device tensor, sample i
+    = hw[i] bytes at offsets[i]; amax [n]: each sample's largest byte, device or host) -> device float32 [2,total], packed the same
+    way (elements between samples are 0).  A Gaussian of radius 0 (int(4 gauss_k + 0.5) == 0, the reference's 0.1): a 256-entry table
+    per sample (unary_table) and one lookup launch for the batch, bit-equal to oracle_post.unary_from_mask of the float64 soft mask.
+    A wider Gaussian goes through gaussian_filter per sample (slow, correct, not what the reference uses)."""
+    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
+        raise ValueError("data must be a contiguous 1-D uint8 CUDA(HIP) tensor of packed samples")
+    total, dev = int(data.numel()), data.device
+    off, size, d_off, d_hw = _crf_tables(offsets, hw, total, dev)
+    am = (amax.cpu().numpy() if isinstance(amax, torch.Tensor) else np.asarray(amax)).reshape(-1).astype(np.int64)
+    if len(am) != len(off) or (am < 0).any() or (am > 255).any():
+        raise ValueError("one amax in 0..255 per sample")
+    unary = torch.zeros((2, total), dtype=torch.float32, device=dev)
+    if int(4.0 * float(gauss_k) + 0.5) == 0:
+        table = torch.from_numpy(unary_table(am)).to(dev)
+        check(lib.udet_crf_unary_lookup(data.data_ptr(), table.data_ptr(), len(off), d_off.data_ptr(), d_hw.data_ptr(), int(size[:, 0].max()),
+                                        int(size[:, 1].max()), total, unary.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return unary
+    for i, (o, (H, W)) in enumerate(zip(off, size)):
+        o, H, W = int(o), int(H), int(W)
+        soft = data[o:o + H * W].view(H, W).double() / (float(am[i]) + 1e-8)
+        U = gaussian_filter(soft, gauss_k)
+        U = torch.clamp(U / (U.max() + 1e-8), 1e-6, 1.0 - 1e-6)
+        unary[:, o:o + H * W] = (-torch.log(torch.stack([1.0 - U, U], 0))).float().view(2, -1)
+    return unary
+
+
+def dense_crf_ragged(unary, images, offsets, hw, sxy, srgb, compat, iters=50, radius=None, want_q=True, want_labels=True, q_out=None,
+                     labels_out=None):
+    """The dense CRF of dense_crf on n frames of their own sizes in one call of udet_dense_crf_ragged (iters + 2 launches whatever
+    n is).  unary: device float32 [2,total] (the energies of label 0 / 1), images: device uint8 [3 * total] (rgb), both packed:
+    sample i = hw[i] = (H_i, W_i) elements at element offset offsets[i] (host arrays [n] / [n,2]).  radius None: ceil(3 sxy).
+    Returns (q1, labels): the marginal of label 1 (device float32 [total]) and the label (device uint8 [total], 1 where Q1 > Q0), each
+    None when not wanted; elements between the samples are not written (q_out / labels_out: caller-owned buffers of `total`
+    elements, else fresh zeroed ones).  The tables are validated on the host before anything is launched (ValueError)."""
+    if not (isinstance(unary, torch.Tensor) and unary.is_cuda and unary.dtype == torch.float32 and unary.dim() == 2 and
+            unary.shape[0] == 2 and unary.is_contiguous()):
+        raise ValueError("unary must be a contiguous float32 CUDA(HIP) tensor [2,total]")
+    total, dev = int(unary.shape[1]), unary.device
+    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.is_contiguous() and images.numel() == 3 * total and
+            images.device == dev):
+        raise ValueError("images must be a contiguous uint8 tensor of 3 * total bytes on the device of unary")
+    if not (want_q or want_labels):
+        raise ValueError("at least one of want_q and want_labels")
+    for buf, dt, name in ((q_out, torch.float32, "q_out"), (labels_out, torch.uint8, "labels_out")):
+        if buf is not None and not (buf.dtype == dt and buf.dim() == 1 and buf.numel() == total and buf.is_contiguous() and buf.device == dev):
+            raise ValueError("{} must be a contiguous 1-D tensor of total elements on the device of unary".format(name))
+    off, size, d_off, d_hw = _crf_tables(offsets, hw, total, dev)
+    R = default_radius(sxy) if radius is None else int(radius)
+    q1 = (torch.zeros(total, dtype=torch.float32, device=dev) if q_out is None else q_out) if want_q else None
+    labels = (torch.zeros(total, dtype=torch.uint8, device=dev) if labels_out is None else labels_out) if want_labels else None
+    ws = torch.empty((int(lib.udet_dense_crf_workspace_bytes(total, len(off))) + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    check(lib.udet_dense_crf_ragged(unary.data_ptr(), images.data_ptr(), len(off), d_off.data_ptr(), d_hw.data_ptr(), int(size[:, 0].max()),
+                                    int(size[:, 1].max()), total, float(sxy), float(srgb), float(compat), int(iters), R,
+                                    None if q1 is None else q1.data_ptr(), None if labels is None else labels.data_ptr(), ws.data_ptr(),
+                                    ws.numel() * 4, torch.cuda.current_stream(dev).cuda_stream))
+    return q1, labels
+
+
+def run_crf_original_resolution(path_soft, frame_lists, sxy, srgb, scomp, gauss_k, out_path="./post_processed_davis_original", **kwargs):
+    """crf_refine.run_crf_original_resolution (:65-108) over the folder run_crf wrote: soft_mask of every result_<k>.mat restored to
+    its frame's own size, refined there by the dense CRF on the untouched frame, scored and exported.  frame_lists ({category:
+    [(image, annotation), ...]}, native_results.frame_lists_from_reader) stands for the reference's path_img / path_gt.  A thin call
+    of native_results.restore_results_dir (its other arguments -- component, batch, gt_rule, ... -- ride along in kwargs; crf_iters /
+    crf_radius: the iterations (50) and the window radius (ceil(3 sxy))); returns what it returns, native_eval.json's content."""
+    from .native_results import restore_results_dir
+    crf = {"sxy": sxy, "srgb": srgb, "compat": scomp, "gauss_k": gauss_k, "iters": kwargs.pop("crf_iters", 50),
+           "radius": kwargs.pop("crf_radius", None)}
+    kwargs.setdefault("mask_key", "soft_mask")
+    return restore_results_dir(path_soft, frame_lists, out_path, crf=crf, **kwargs)
 
 
 # ----------------------------------------------------------------------------------------------------- file drivers ----
