@@ -235,6 +235,40 @@ size_t udet_post_crf_workspace_bytes(int h, int w);
 int udet_post_dense_crf(const float* unary, const unsigned char* image_rgb, int h, int w, float sxy, float srgb, float compat, int iters,
                         int radius, float* q, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The sequence stage of the same pass, batched (csrc/sequence.hip).
+ * udet_post_propagate_sequences: generate_soft_score_from_buffer.py propagate :127-231 for n_seq sequences and both directions, given the
+ * flows.  The frames of all sequences lie in one array of total_frames frames; sequence s is frames seq_first[s] .. seq_first[s] +
+ * seq_len[s] - 1 (device int32 [n_seq]; lengths >= 1, ranges inside the array and disjoint -- device memory, so validated by the host
+ * caller before anything is launched: post_processing.check_sequence_tables).  masks [total][h][w]; flow_prev / flow_next [total][h][w][2]
+ * = (u, v) from frame k to frame k - 1 / k + 1 (the entry of a sequence's first / last frame is not read); avg_f / avg_b [total][h][w].
+ * Per sequence: avg_f[first] = mask[first], then for k = first + 1 ..: with s2 = remap(mask[k-1], flow_prev[k]) and ra = remap(avg_f[k-1],
+ * flow_prev[k]) (udet_post_remap), avg_f[k] = r / den(max r), r = w_s * (s2 / den(max s2)) + w_r * (ra / den(max ra)), den(m) =
+ * (float)((double)m + 1e-8) -- operation for operation what udet_post_remap x 2 + udet_post_blend x 2 compute per step (one set of
+ * device functions, csrc/post_remap.h): bit-identical to that chain.  avg_b likewise from the last frame down along flow_next.  w_s and
+ * w_r are the two float32 weights as udet_post_blend takes them (the reference: float32(1 - 0.85) and float32(0.85); 1 - w_r is rounded
+ * from the caller's double, so it cannot be derived from the float32 w_r here).
+ * Two launches whatever the batch: (a) max s2 of every step, which does not depend on the recurrence -- workgroups (slice, sequence,
+ * direction), 32 partial maxima per step into the workspace, no atomics; (b) one workgroup of 1024 threads per (sequence, direction)
+ * that walks the frames: avg[k] is the state (a step gathers from avg[k -+ 1]), barriers of the workgroup only, no workgroup waits for
+ * another.  max is exact in any order and everything else is per element: bit-identical from run to run and between a sequence alone
+ * and inside a batch.  workspace: udet_post_propagate_workspace_bytes(total_frames, n_seq) bytes (256 per frame; no per-pixel
+ * intermediate), 16-byte aligned.  UDET_ERR_ARG, nothing enqueued: n_seq outside 1..65535, h, w or total_frames < 1, h * w >= 2^31, a NULL
+ * pointer, a flow array that is not 8-byte aligned, masks / avg_f / avg_b not three different buffers, a short or misaligned workspace.
+ * udet_post_select_unary: crf_refine.py:40-52 and :113-121 for n frames of hw pixels each (pred, avg_f, avg_b, gt: [n][hw]).  Launch 1,
+ * a workgroup per (frame, candidate): scores[n][3] = sum(p * gt) / (sum(p) + 1e-8), the product in float32, the sums in double in a
+ * fixed order.  Launch 2, a workgroup per frame: choice[n] by the reference's rule on (m, f, b) = scores[i] (m >= f and m >= b: 0; else
+ * f >= m and f >= b: 1; else 2), soft[n][hw] = the chosen candidate, U = clamp((double)p / (max p + 1e-8), 1e-6, 1 - 1e-6), unary[0] =
+ * (float)-log(1 - U), unary[1] = (float)-log(U) in double, unary [2][n * hw] with frame i at element i * hw of each half -- the packed
+ * layout of udet_dense_crf_ragged with offsets[i] = i * hw.  The Gaussian of crf_refine.py:113 is the identity here (radius int(4 *
+ * gauss_k + 0.5) = 0, the reference's 0.1).  UDET_ERR_ARG, nothing enqueued: n outside 1..65535, hw < 1, a NULL pointer, scores not
+ * 8-byte aligned. */
+size_t udet_post_propagate_workspace_bytes(int total_frames, int n_seq);
+int udet_post_propagate_sequences(const float* masks, const float* flow_prev, const float* flow_next, int n_seq, const int* seq_first,
+                                  const int* seq_len, int total_frames, int h, int w, float w_s, float w_r, float* avg_f, float* avg_b,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int udet_post_select_unary(const float* pred, const float* avg_f, const float* avg_b, const float* gt, int n, int hw, int* choice,
+                           double* scores, float* soft, float* unary, void* stream);
+
 /* Visualisation and training summaries (models/utils/flow_utils.py:14-100, models/adversarial_learner.py:260-298,
  * test_generator.py:93-117): the images and gradient histograms of a run, from buffers that already sit on the device.
  *  - udet_flow_to_image: flow_to_image + compute_color (flow_utils.py:46-100) with the arithmetic the reference has on a float32

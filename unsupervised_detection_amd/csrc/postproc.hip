@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "post_remap.h"
 
 namespace udet {
 
@@ -115,23 +116,12 @@ __global__ __launch_bounds__(1024) void post_minmax_norm_kernel(const double* __
 }
 
 // cv2.remap(src, flow + grid, None, INTER_LINEAR), BORDER_CONSTANT 0 (OpenCV imgwarp.cpp remapBilinear): coordinates rounded
-// to 1/32 pixel (round half to even), float weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx, taps outside the image read 0
+// to 1/32 pixel (round half to even), float weights (1-fy)(1-fx), (1-fy)fx, fy(1-fx), fy fx, taps outside the image read 0 (post_remap.h)
 __global__ __launch_bounds__(256) void post_remap_kernel(const float* __restrict__ src, const float* __restrict__ flow_uv,
                                                          float* __restrict__ dst, int H, int W) {
   for (int i = blockIdx.x * 256 + threadIdx.x; i < H * W; i += gridDim.x * 256) {
     const int y = i / W, x = i - y * W;
-    const float mxf = (float)((double)flow_uv[2 * i] + (double)x), myf = (float)((double)flow_uv[2 * i + 1] + (double)y);
-    long sx = (long)rint((double)mxf * 32.0), sy = (long)rint((double)myf * 32.0);
-    long ix = sx >> 5, iy = sy >> 5;
-    const float fx = (float)(sx & 31) / 32.f, fy = (float)(sy & 31) / 32.f;
-    ix = ix < -32768 ? -32768 : (ix > 32767 ? 32767 : ix);
-    iy = iy < -32768 ? -32768 : (iy > 32767 ? 32767 : iy);
-    auto tap = [&](long yy, long xx) { return (yy >= 0 && yy < H && xx >= 0 && xx < W) ? src[yy * W + xx] : 0.f; };
-    float o = tap(iy, ix) * ((1.f - fy) * (1.f - fx));
-    o = o + tap(iy, ix + 1) * ((1.f - fy) * fx);
-    o = o + tap(iy + 1, ix) * (fy * (1.f - fx));
-    o = o + tap(iy + 1, ix + 1) * (fy * fx);
-    dst[i] = o;
+    dst[i] = remap_gather(src, remap_taps(flow_uv[2 * i], flow_uv[2 * i + 1], x, y), H, W);
   }
 }
 
@@ -142,17 +132,17 @@ __global__ __launch_bounds__(1024) void post_blend_kernel(const float* __restric
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < n; i += 1024) mx = fmaxf(mx, x[i]);
   mx = block_reduce(mx, sm, [](float p, float q) { return fmaxf(p, q); });
-  const float den = (float)((double)mx + 1e-8);
+  const float den = max_denominator(mx);
   float my = -INFINITY;
   for (int i = threadIdx.x; i < n; i += 1024) {
     const float v = x[i] / den;
-    const float r = b == 0.f ? a * v : a * v + b * y[i];
+    const float r = b == 0.f ? a * v : blend_pair(a, v, b, y[i]);
     y[i] = r;
     my = fmaxf(my, r);
   }
   if (!renorm) return;
   my = block_reduce(my, sm, [](float p, float q) { return fmaxf(p, q); });
-  const float den2 = (float)((double)my + 1e-8);
+  const float den2 = max_denominator(my);
   __syncthreads();
   for (int i = threadIdx.x; i < n; i += 1024) y[i] = y[i] / den2;
 }

@@ -8,6 +8,9 @@ meaning as post_processing/generate_soft_score_from_buffer.py and post_processin
   buffer_to_soft_score(buffer_path, out_path, ...) / run_crf(...)  the file-level drivers over the .mat buffers the ensemble run writes
   dense_crf_ragged(...) / unary_from_restored(...) / run_crf_original_resolution(...)   crf_refine.py:65-108: the CRF on every frame at
                     its own size, a ragged batch per call (csrc/crf.hip)
+  propagate_sequences(...) / PWCFlow.batch(...) / select_unary_batch(...)   the sequence stage batched (csrc/sequence.hip):
+                    propagate(flow_batch=), buffer_to_soft_score(flow_batch=) and run_crf(batch=) reach them; the defaults (None) keep the
+                    per-frame paths
 
 The kernels of the stage -- border statistics, bytescale, Pillow's 8-bit resampler, canvas placement, min-max / max
 normalisations, remap, blending, the separable Gaussian and the dense-CRF mean field -- run in libudet.so (csrc/postproc.hip); torch
@@ -48,6 +51,13 @@ lib.udet_dense_crf_rows_per_thread.restype = c_i
 lib.udet_dense_crf_rows_per_thread.argtypes = [c_i, c_i, c_i]
 lib.udet_crf_unary_lookup.restype = c_i
 lib.udet_crf_unary_lookup.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p]
+# the sequence stage, batched (csrc/sequence.hip)
+lib.udet_post_propagate_workspace_bytes.restype = c_sz
+lib.udet_post_propagate_workspace_bytes.argtypes = [c_i, c_i]
+lib.udet_post_propagate_sequences.restype = c_i
+lib.udet_post_propagate_sequences.argtypes = [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]
+lib.udet_post_select_unary.restype = c_i
+lib.udet_post_select_unary.argtypes = [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
 
 
 def _stream():
@@ -216,11 +226,121 @@ class PWCFlow(object):
         # the order pyflow returns and cv2.remap's map expects (:162-165)
         return self.model.predict_from_img_pairs(a.unsqueeze(0).contiguous(), b.unsqueeze(0).contiguous())[0].contiguous()
 
+    def batch(self, imgs_from, imgs_to, batch=8):
+        """The flows of many pairs, `batch` pairs per network call: imgs_from / imgs_to are equally long lists of [H,W,3] uint8 frames ->
+        device float32 [n,H,W,2], row i = self(imgs_from[i], imgs_to[i])'s field.  Every call has `batch` pairs (the last chunk is
+        padded by repeating its last pair, flow_chunks), so one engine shape is built whatever n is."""
+        if len(imgs_from) != len(imgs_to) or not len(imgs_from):
+            raise ValueError("as many frames to start from as to go to, and at least one pair")
+        out = None
+        for idx, keep in flow_chunks(len(imgs_from), batch):
+            a = torch.stack([_dev(imgs_from[i], torch.float32) for i in idx], 0) / 255.0 - 0.5
+            b = torch.stack([_dev(imgs_to[i], torch.float32) for i in idx], 0) / 255.0 - 0.5
+            f = self.model.predict_from_img_pairs(a.contiguous(), b.contiguous())
+            if out is None:
+                out = torch.empty((len(imgs_from),) + tuple(f.shape[1:]), dtype=torch.float32, device=f.device)
+            out[idx[0]:idx[0] + keep] = f[:keep]
+        return out
 
-def propagate(pred_masks, images_u8, flow_fn, w_r=0.85):
+
+def flow_chunks(n, batch):
+    """The chunking of PWCFlow.batch: n pairs in calls of exactly `batch` -> [(indices [batch], keep), ...]; the indices of a chunk are
+    consecutive, its first `keep` results are used, and the last chunk is padded with its last pair's index."""
+    n, batch = int(n), int(batch)
+    if n < 1 or batch < 1:
+        raise ValueError("flow_chunks: n and batch must be at least 1")
+    out = []
+    for lo in range(0, n, batch):
+        keep = min(batch, n - lo)
+        out.append((list(range(lo, lo + keep)) + [lo + keep - 1] * (batch - keep), keep))
+    return out
+
+
+def check_sequence_tables(seq_first, seq_len, total):
+    """Host validation of the device tables of udet_post_propagate_sequences, before the device is touched: raises ValueError unless
+    every sequence has at least one frame, lies inside the array of `total` frames and shares no frame with another one (any order, gaps
+    allowed); at most 65535 sequences.  Returns (seq_first, seq_len) as int32 arrays [n_seq], as the kernels read them."""
+    first, length = np.asarray(seq_first, dtype=np.int64).reshape(-1), np.asarray(seq_len, dtype=np.int64).reshape(-1)
+    if len(first) != len(length) or not 1 <= len(first) <= 65535:
+        raise ValueError("one first frame and one length per sequence, 1..65535 sequences")
+    if int(total) < 1 or int(total) > 0x7fffffff:
+        raise ValueError("total frames must be in 1..2^31-1")
+    if (length < 1).any():
+        raise ValueError("a sequence has a length below 1")
+    if (first < 0).any() or (first + length > int(total)).any():
+        raise ValueError("a sequence lies outside the {} frames".format(int(total)))
+    order = np.argsort(first, kind="stable")
+    if (first[order][1:] < (first + length)[order][:-1]).any():
+        raise ValueError("sequences overlap")
+    return first.astype(np.int32), length.astype(np.int32)
+
+
+def propagate_sequences(masks, flow_prev, flow_next, seq_lens, w_r=0.85):
+    """propagate() for many sequences in one call of udet_post_propagate_sequences (two launches whatever the batch), given the flows.
+    masks: device float32 [total,H,W], the sequences one after the other (seq_lens: their lengths, host integers summing to total);
+    flow_prev / flow_next: device float32 [total,H,W,2], (u, v) from frame k to k - 1 / k + 1 (the entry of a sequence's first / last frame
+    is not read).  Returns (avg_f, avg_b), device float32 [total,H,W]: bit-identical to propagate()'s lists with the same flows."""
+    for t, nd, name in ((masks, 3, "masks"), (flow_prev, 4, "flow_prev"), (flow_next, 4, "flow_next")):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == nd and t.is_contiguous()):
+            raise ValueError("{} must be a contiguous float32 CUDA(HIP) tensor of {} dimensions".format(name, nd))
+    total, H, W = (int(v) for v in masks.shape)
+    if tuple(flow_prev.shape) != (total, H, W, 2) or tuple(flow_next.shape) != (total, H, W, 2):
+        raise ValueError("flow_prev and flow_next must be [total,H,W,2] like masks [total,H,W]")
+    lens = np.asarray(seq_lens, dtype=np.int64).reshape(-1)
+    if lens.sum() != total:
+        raise ValueError("seq_lens must sum to the {} frames of masks".format(total))
+    first, length = check_sequence_tables(np.concatenate([[0], np.cumsum(lens)[:-1]]), lens, total)  # before the device is touched
+    from .data import _upload_tables
+    d_first, d_len = _upload_tables([first, length], masks.device)
+    avg_f, avg_b = torch.empty_like(masks), torch.empty_like(masks)
+    ws = torch.empty((int(lib.udet_post_propagate_workspace_bytes(total, len(first))) + 15) // 16 * 4, dtype=torch.float32, device=masks.device)
+    check(lib.udet_post_propagate_sequences(masks.data_ptr(), flow_prev.data_ptr(), flow_next.data_ptr(), len(first), d_first.data_ptr(),
+                                            d_len.data_ptr(), total, H, W, float(np.float32(1 - w_r)), float(np.float32(w_r)),
+                                            avg_f.data_ptr(), avg_b.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                            torch.cuda.current_stream(masks.device).cuda_stream))
+    return avg_f, avg_b
+
+
+def _propagate_batched(seq_masks, seq_images, flow_fn, w_r, flow_batch):
+    """propagate(flow_batch=...) for a list of sequences: every flow of every sequence through flow_fn.batch (2 (n - 1) pairs per
+    sequence of n frames), then one propagate_sequences call.  Returns [(running_avg_f, running_avg_b), ...], one pair of lists per
+    sequence."""
+    if not hasattr(flow_fn, "batch"):
+        raise ValueError("flow_batch needs a flow_fn with a batch(imgs_from, imgs_to, batch) method (PWCFlow)")
+    masks = [_dev(np.squeeze(m) if not isinstance(m, torch.Tensor) else m.squeeze(), torch.float32) for ms in seq_masks for m in ms]
+    lens = [len(ms) for ms in seq_masks]
+    if any(len(ms) != len(im) or not len(ms) for ms, im in zip(seq_masks, seq_images)):
+        raise ValueError("one frame per mask, and at least one mask per sequence")
+    masks = torch.stack(masks, 0).contiguous()
+    total, H, W = masks.shape
+    a, b, slot = [], [], []  # pair i: flow from a[i] to b[i], stored at (direction, frame) = slot[i]
+    base = 0
+    for im in seq_images:
+        n = len(im)
+        for k in range(1, n):
+            a.append(im[k]), b.append(im[k - 1]), slot.append(base + k)
+        for k in range(n - 1):
+            a.append(im[k]), b.append(im[k + 1]), slot.append(total + base + k)
+        base += n
+    flows = torch.zeros((2 * total, H, W, 2), dtype=torch.float32, device=masks.device)
+    if slot:
+        flows[torch.as_tensor(slot, device=masks.device)] = flow_fn.batch(a, b, int(flow_batch))
+    avg_f, avg_b = propagate_sequences(masks, flows[:total], flows[total:], lens, w_r)
+    out, base = [], 0
+    for n in lens:
+        out.append((list(avg_f[base:base + n]), list(avg_b[base:base + n])))
+        base += n
+    return out
+
+
+def propagate(pred_masks, images_u8, flow_fn, w_r=0.85, flow_batch=None):
     """Moving average of a sequence's masks along the optical flow, forward and backward (:127-231).  pred_masks: list of [H,W]
     soft masks, images_u8: list of [H,W,3] uint8 frames, flow_fn(I_a, I_b) -> (u, v) field used as in the reference's calls
-    (forward pass: flow_fn(I_k, I_{k-1}); backward pass: flow_fn(I_k, I_{k+1})).  Returns (running_avg_f, running_avg_b) lists."""
+    (forward pass: flow_fn(I_k, I_{k-1}); backward pass: flow_fn(I_k, I_{k+1})).  Returns (running_avg_f, running_avg_b) lists.
+    flow_batch None: one flow_fn call and four launches per frame and direction.  An integer: all flows through flow_fn.batch, that
+    many pairs per network call, then one propagate_sequences call."""
+    if flow_batch is not None:
+        return _propagate_batched([pred_masks], [images_u8], flow_fn, w_r, flow_batch)[0]
     n = len(pred_masks)
     masks = [_dev(np.squeeze(m) if not isinstance(m, torch.Tensor) else m.squeeze(), torch.float32) for m in pred_masks]
     fwd, bwd = [None] * n, [None] * n
@@ -251,6 +371,29 @@ def select_candidate(pred_mask, pred_f, pred_b, gt_mask):
     if f >= m and f >= b:
         return pred_f, 1
     return pred_b, 2
+
+
+def select_unary_batch(pred, avg_f, avg_b, gt, gauss_k=0.1):
+    """select_candidate and the unary of refine (crf_refine.py:40-52, :113-121) for n same-size frames in one call of
+    udet_post_select_unary (two launches, no host round trip).  pred, avg_f, avg_b, gt: device float32 [n,H,W].  Returns (choice int32 [n],
+    scores float64 [n,3] = the object scores of (pred, avg_f, avg_b), soft float32 [n,H,W] = the chosen candidate, unary float32
+    [2, n*H*W] with frame i at element i*H*W: what dense_crf_ragged takes with offsets i*H*W), all on the device.  Only the identity
+    Gaussian (int(4 gauss_k + 0.5) == 0, the reference's 0.1): ValueError otherwise -- run_crf then keeps the per-frame path."""
+    if int(4.0 * float(gauss_k) + 0.5) != 0:
+        raise ValueError("select_unary_batch covers gauss_k with int(4 gauss_k + 0.5) == 0 only")
+    for t in (pred, avg_f, avg_b, gt):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and
+                t.shape == pred.shape):
+            raise ValueError("pred, avg_f, avg_b and gt must be contiguous float32 CUDA(HIP) tensors of one shape [n,H,W]")
+    n, H, W = (int(v) for v in pred.shape)
+    dev = pred.device
+    choice = torch.empty(n, dtype=torch.int32, device=dev)
+    scores = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    soft = torch.empty_like(pred)
+    unary = torch.empty((2, n * H * W), dtype=torch.float32, device=dev)
+    check(lib.udet_post_select_unary(pred.data_ptr(), avg_f.data_ptr(), avg_b.data_ptr(), gt.data_ptr(), n, H * W, choice.data_ptr(),
+                                     scores.data_ptr(), soft.data_ptr(), unary.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return choice, scores, soft, unary
 
 
 def gaussian_filter(x, sigma, truncate=4.0):
@@ -395,12 +538,15 @@ def run_crf_original_resolution(path_soft, frame_lists, sxy, srgb, scomp, gauss_
 
 
 # ----------------------------------------------------------------------------------------------------- file drivers ----
-def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2, base_crop=90.0, dprefix="davis_shift", flow_fn=None):
+def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2, base_crop=90.0, dprefix="davis_shift", flow_fn=None,
+                         flow_batch=None):
     """generate_soft_score_from_buffer.buffer_to_soft_score over the result_<k>.mat buffers test_generator_ensemble writes
     (evaluation.evaluate_ensemble), followed by propagate(); writes result_<k>.mat with pred_mask / img1 / gt_mask /
-    running_avg_f / running_avg_b like the reference (:91-93, :148, :184, :199, :229)."""
+    running_avg_f / running_avg_b like the reference (:91-93, :148, :184, :199, :229).  flow_batch (None: propagate() per sequence as
+    it is read): an integer computes the soft scores of the whole folder first and propagates all its sequences in one call."""
     import scipy.io as sio
     crops = list(range(85, 101, 5))
+    held = []  # flow_batch: (out_dir, masks, imgs, gts) of every sequence until the one propagation
     for name, num in zip(seq_names, seq_num):
         out_dir = os.path.join(out_path, name)
         os.makedirs(out_dir, exist_ok=True)
@@ -418,30 +564,87 @@ def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2,
             masks.append(soft_score(pb, pf, crops, base_crop))
             imgs.append(((r_f1["img_1_%03d" % int(base_crop)] + 0.5) * 255).astype("uint8"))
             gts.append(r_f1["gt_mask_%03d" % int(base_crop)])
+        if flow_batch is not None:
+            held.append((out_dir, masks, imgs, gts))
+            continue
         fwd, bwd = propagate(masks, imgs, flow_fn or PWCFlow())
         for k in range(num):
             sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
                         {"pred_mask": masks[k].cpu().numpy(), "img1": imgs[k], "gt_mask": gts[k],
                          "running_avg_f": fwd[k].cpu().numpy(), "running_avg_b": bwd[k].cpu().numpy()})
+    if held:
+        avgs = _propagate_batched([h[1] for h in held], [h[2] for h in held], flow_fn or PWCFlow(), 0.85, flow_batch)
+        for (out_dir, masks, imgs, gts), (fwd, bwd) in zip(held, avgs):
+            for k in range(len(masks)):
+                sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
+                            {"pred_mask": masks[k].cpu().numpy(), "img1": imgs[k], "gt_mask": gts[k],
+                             "running_avg_f": fwd[k].cpu().numpy(), "running_avg_b": bwd[k].cpu().numpy()})
 
 
-def run_crf(path_soft, sxy, srgb, scomp, gauss_k, out_path="./post_processed_davis"):
-    """crf_refine.run_crf (:9-59) over the soft-score folder; returns the average IoU."""
+def _run_crf_group(frames, sxy, srgb, scomp, gauss_k, iters, radius):
+    """The device part of run_crf(batch=...) for a group of same-size frames [(pred_mask, running_avg_f, running_avg_b, gt_mask float32
+    [H,W], img1 uint8 [H,W,3]), ...]: one upload, select_unary_batch, one dense_crf_ragged call, the IoU's integer counts on the
+    device, one copy back -> (soft float32 [n,H,W], labels uint8 [n,H,W], intersection int64 [n], union int64 [n]) on the host."""
+    n, (H, W) = len(frames), frames[0][0].shape
+    hw = H * W
+    buf = np.empty(16 * n * hw + 3 * n * hw, np.uint8)
+    fl = buf[:16 * n * hw].view(np.float32).reshape(4, n, hw)
+    im = buf[16 * n * hw:].reshape(n, hw * 3)
+    for i, fr in enumerate(frames):
+        for c in range(4):
+            fl[c, i] = fr[c].reshape(-1)
+        im[i] = np.asarray(fr[4], np.uint8).reshape(-1)
+    d = torch.from_numpy(buf).cuda()
+    dfl = d[:16 * n * hw].view(torch.float32).view(4, n, H, W)
+    choice, _, soft, unary = select_unary_batch(dfl[0], dfl[1], dfl[2], dfl[3], gauss_k)
+    _, labels = dense_crf_ragged(unary, d[16 * n * hw:], np.arange(n, dtype=np.int64) * hw, np.full((n, 2), (H, W), np.int64), sxy, srgb, scomp,
+                                 iters, radius, want_q=False)
+    gt, bm = dfl[3].reshape(n, hw) > 0.1, labels.view(n, hw) > 0
+    counts = torch.stack([(gt & bm).sum(1), (gt | bm).sum(1)], 0)  # int64 [2,n]: exact
+    back = torch.cat([soft.reshape(-1).view(torch.uint8), counts.reshape(-1).view(torch.uint8), labels]).cpu().numpy()
+    soft_h = back[:4 * n * hw].view(np.float32).reshape(n, H, W)
+    cnt = back[4 * n * hw:4 * n * hw + 16 * n].view(np.int64).reshape(2, n)
+    return soft_h, back[4 * n * hw + 16 * n:].reshape(n, H, W), cnt[0], cnt[1]
+
+
+def run_crf(path_soft, sxy, srgb, scomp, gauss_k, out_path="./post_processed_davis", batch=None, crf_iters=50, crf_radius=None):
+    """crf_refine.run_crf (:9-59) over the soft-score folder; returns the average IoU.  crf_iters / crf_radius: the mean-field
+    iterations and the window radius of the kernel (None: ceil(3 sxy)).  batch None: a frame at a time (select_candidate + refine).  An
+    integer: the frames of a sequence in groups of that many -- one upload, select_unary_batch, one dense_crf_ragged call and one copy back
+    per group (_run_crf_group); the same files, keys and dtypes, the same return value.  A Gaussian wider than the identity (int(4 gauss_k
+    + 0.5) > 0, not what the reference uses) keeps the per-frame path."""
     import scipy.io as sio
     sum_iou, total = 0.0, 0.0
+    if batch is not None and int(batch) < 1:
+        raise ValueError("run_crf: batch must be None or at least 1")
+    if batch is not None and int(4.0 * float(gauss_k) + 0.5) != 0:
+        batch = None
+
+    def load(seq_path, k):
+        result = sio.loadmat(os.path.join(seq_path, "result_%d.mat" % (k + 1)))
+        return tuple(np.float32(np.squeeze(result[n])) for n in ("pred_mask", "running_avg_f", "running_avg_b", "gt_mask")) + (result["img1"],)
     for seq in os.listdir(path_soft):
         seq_path = os.path.join(path_soft, seq)
         seq_len = len([n for n in os.listdir(seq_path) if n.endswith(".mat")])
         out_dir = os.path.join(out_path, seq)
         os.makedirs(out_dir, exist_ok=True)
         print(out_dir)
+        if batch is not None:
+            for k0 in range(0, seq_len, int(batch)):
+                ks = range(k0, min(seq_len, k0 + int(batch)))
+                frames = [load(seq_path, k) for k in ks]
+                soft, labels, inter, union = _run_crf_group(frames, sxy, srgb, scomp, gauss_k, crf_iters, crf_radius)
+                for i, k in enumerate(ks):
+                    total += 1.0
+                    sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
+                                {"gt_mask": frames[i][3], "soft_mask": soft[i], "mask": labels[i].astype(np.float32)})
+                    sum_iou += np.float32(inter[i]) / np.float32(union[i])
+            continue
         for k in range(seq_len):
-            result = sio.loadmat(os.path.join(seq_path, "result_%d.mat" % (k + 1)))
+            pm, pf, pb, gt, img = load(seq_path, k)
             total += 1.0
-            pm, pf, pb = (np.float32(np.squeeze(result[n])) for n in ("pred_mask", "running_avg_f", "running_avg_b"))
-            gt = np.float32(np.squeeze(result["gt_mask"]))
             mask, _ = select_candidate(pm, pf, pb, gt)
-            new_mask, iou = refine(mask, result["img1"], gauss_k, sxy, srgb, scomp, gt)
+            new_mask, iou = refine(mask, img, gauss_k, sxy, srgb, scomp, gt, crf_iters, crf_radius)
             sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)), {"gt_mask": gt, "soft_mask": mask, "mask": new_mask})
             sum_iou += iou
     return sum_iou / total
