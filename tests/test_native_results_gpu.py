@@ -171,3 +171,102 @@ def test_restore_results_dir_end_to_end(gpu, tmp_path, mixed):
     assert ev["J"] == got["J"] and ev["F"] == got["F"] and ev["J&F"] == got["J&F"]
     for seq in SEQS:
         assert ev["sequences"][seq] == got["sequences"][seq]
+
+
+RAGGED3 = [(30, 53), (13, 26), (9, 70)]  # the shapes of tests/test_ragged.py
+
+
+def _count_table_uploads(monkeypatch):
+    """Counts the uploads of a layout's own (offsets int64 [n], hw int32 [n,2]) pair; the restore tables' tab / coef upload is separate."""
+    from unsupervised_detection_amd import ragged
+    calls, real = [], ragged.upload_tables
+
+    def counting(arrays, device):
+        if len(arrays) == 2 and arrays[0].dtype == np.int64 and arrays[1].dtype == np.int32 and arrays[1].shape == (len(arrays[0]), 2):
+            calls.append(arrays)
+        return real(arrays, device)
+    monkeypatch.setattr(ragged, "upload_tables", counting)
+    return calls
+
+
+def test_chain_by_layout_equals_chain_by_raw_tables(gpu, monkeypatch):
+    """restore -> unary -> dense CRF -> select on three ragged samples with gaps and guard bytes, once handing the restored batch's
+    layout along and once passing raw offsets / hw to every call: the same bytes everywhere, the guards untouched, and in the first form
+    one upload of the layout's tables for the whole chain."""
+    from test_crf_native import COMPAT, scene
+    from unsupervised_detection_amd import native_results
+    from unsupervised_detection_amd.native_results import RestoredMasks, restore_masks, select_components
+    monkeypatch.setattr(native_results, "_restore_tables", {})  # the counts below start from a cold restore cache
+    from unsupervised_detection_amd.post_processing import dense_crf_ragged, unary_from_restored
+    masks = np.stack([scene(12, 24, 500 + k)[1] for k in range(3)])
+    masks[1] = 0.25  # constant: restores to zeros, amax = 0
+    areas = [h * w for h, w in RAGGED3]
+    offsets = [40, 40 + areas[0] + 72, 40 + areas[0] + 72 + areas[1]]  # a gap in front, one between samples 0 and 1, a tail
+    numel = offsets[2] + areas[2] + 24
+    guard = np.ones(numel, bool)
+    for o, a in zip(offsets, areas):
+        guard[o:o + a] = False
+    rgb = np.zeros(3 * numel, np.uint8)
+    for (H, W), o in zip(RAGGED3, offsets):
+        rgb[3 * o:3 * (o + H * W)] = scene(H, W, H * W)[0].reshape(-1)
+    images, dev = torch.from_numpy(rgb).cuda(), torch.from_numpy(masks).cuda()
+    uploads = _count_table_uploads(monkeypatch)
+
+    def chain(by_layout):
+        out, binary, labels = (torch.full((numel,), 0xA5, dtype=torch.uint8, device="cuda") for _ in range(3))
+        q = torch.full((numel,), -7.0, dtype=torch.float32, device="cuda")
+        res = restore_masks(dev, RAGGED3, 0.9, 0.5, offsets=offsets, out=out, binary_out=binary)
+        tables = (res.layout, None) if by_layout else (offsets, RAGGED3)
+        unary = unary_from_restored(res.data, tables[0], tables[1], res.amax, 0.1)
+        q1, lab = dense_crf_ragged(unary, images, tables[0], tables[1], 3, 5, COMPAT, iters=2, radius=5, q_out=q, labels_out=labels)
+        if by_layout:
+            sel = select_components(RestoredMasks(res.data, lab, res.layout, None, res.amax), mode="largest")
+        else:
+            sel = select_components(lab, offsets, RAGGED3, mode="largest")
+        torch.cuda.synchronize()
+        return res, unary, q1, lab, sel
+    first = chain(True)
+    assert len(uploads) == 1 and uploads[0][0] is first[0].layout.offsets and uploads[0][1] is first[0].layout.hw
+    assert first[4].layout is first[0].layout
+    second = chain(False)
+    assert len(uploads) == 4  # the restore tables are cached with their layout; unary, CRF and selection each upload their raw tables
+    (res, unary, q1, lab, sel), (res2, unary2, q2, lab2, sel2) = first, second
+    assert torch.equal(res.data, res2.data) and torch.equal(res.binary, res2.binary) and torch.equal(res.amax, res2.amax)
+    assert torch.equal(unary, unary2) and torch.equal(q1, q2) and torch.equal(lab, lab2) and torch.equal(sel.info, sel2.info)
+    assert res.amax.cpu().tolist()[1] == 0 and lab.sum() > 0
+    for i in range(3):
+        assert torch.equal(sel.binary_sample(i), sel2.binary_sample(i)), i
+        assert not (sel.binary_sample(i).bool() & ~res.layout.view(lab, i).bool()).any()
+    for buf in (res.data, res.binary, lab, res2.data, res2.binary, lab2):
+        assert (buf.cpu().numpy()[guard] == 0xA5).all()
+    for buf in (q1, q2):
+        assert (buf.cpu().numpy()[guard] == -7.0).all() and (buf.cpu().numpy()[~guard] >= 0).all()
+    assert not unary.cpu().numpy()[:, guard].any()
+
+
+def test_loader_batch_uploads_no_tables(gpu, tmp_path, monkeypatch):
+    """A RaggedLoader batch's layout hands out the device tables that travelled with the pixels: nothing is uploaded for them."""
+    from PIL import Image
+    from unsupervised_detection_amd import data
+    from unsupervised_detection_amd.native_results import GtBatch, select_components
+    rng = np.random.default_rng(3)
+    arrs = [(rng.random((h, w)) > 0.5).astype(np.uint8) * 255 for h, w in RAGGED3]
+    paths = []
+    for k, a in enumerate(arrs):
+        paths.append(str(tmp_path / ("%d.png" % k)))
+        Image.fromarray(a, "L").save(paths[-1])
+    uploads = _count_table_uploads(monkeypatch)
+    rb = data.RaggedLoader().load(paths, 1)
+    d_off, d_hw = rb.layout.device_tables(rb.data.device)
+    assert d_off is rb.dev_offsets and d_hw is rb.dev_hw
+    assert d_off.data_ptr() + 16 * len(paths) == rb.data.data_ptr() and d_hw.data_ptr() == d_off.data_ptr() + 8 * len(paths)
+    assert d_off.cpu().tolist() == rb.offsets.tolist() and d_hw.cpu().view(-1, 2).tolist() == rb.hw.tolist() == [list(s) for s in RAGGED3]
+    got = rb.resize(12, 24, None, True, 255.0, 0.0)  # the input stage's launch reads them
+    for i, a in enumerate(arrs):
+        one = data.crop_flip_resize(torch.from_numpy(a[None, :, :, None].copy()).cuda(), 12, 24, None, True, 255.0, 0.0)
+        assert torch.equal(got[i:i + 1], one), i
+    gt = GtBatch((rb.data > 127).to(torch.uint8), rb.layout)  # and so does whatever the annotations' layout is handed to
+    sel = select_components(gt.data, gt.layout, mode="label", want_labels=True)
+    assert sel.layout is rb.layout and int(sel.info[:, 0].min()) >= 1
+    torch.cuda.synchronize()
+    assert uploads == []

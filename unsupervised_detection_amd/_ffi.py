@@ -33,50 +33,51 @@ lib.udet_version.restype = c_i
 lib.udet_last_error.restype = ctypes.c_char_p
 
 
-def _sig(name, restype, *argtypes):
+def sig(name, restype, *argtypes):
+    """Declare the C signature of lib.<name>; returns the function."""
     fn = getattr(lib, name)
     fn.restype = restype
     fn.argtypes = list(argtypes)
     return fn
 
 
-_sig("udet_warp", c_i, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_warp_debug", c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_cost_volume", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_resize_bilinear_legacy_fwd", c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_resize_bilinear_legacy_bwd", c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_conv2d_workspace_bytes", c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i)
-_sig("udet_conv2d", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_sz, c_p)
-_sig("udet_conv2d_backward_data", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p,
+sig("udet_warp", c_i, c_p, c_p, c_f, c_p, c_i, c_i, c_i, c_i, c_p)
+sig("udet_warp_debug", c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
+sig("udet_cost_volume", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
+sig("udet_resize_bilinear_legacy_fwd", c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p)
+sig("udet_resize_bilinear_legacy_bwd", c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p)
+sig("udet_conv2d_workspace_bytes", c_sz, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i)
+sig("udet_conv2d", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_sz, c_p)
+sig("udet_conv2d_backward_data", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p,
      c_sz, c_p)
-_sig("udet_conv2d_backward_filter", c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+sig("udet_conv2d_backward_filter", c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
      c_f, c_p, c_sz, c_p)
-_sig("udet_conv2d_transpose4x4s2", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p)
+sig("udet_conv2d_transpose4x4s2", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_sz, c_p)
 
 
-_sig("udet_warp_cost_volume", c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
-_sig("udet_stage_workspace_bytes", c_sz, c_i)
-_sig("udet_flow_normalize", c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p)
-_sig("udet_charbonnier_loss", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_sz, c_p)
-_sig("udet_losses_forward", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p)
-_sig("udet_losses_backward", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p)
-_sig("udet_clip_or_noise", c_i, c_p, c_sz, c_f, c_p, ctypes.c_ulonglong, ctypes.c_long, c_p)
-_sig("udet_adam_step", c_i, c_p, c_p, c_p, c_p, c_sz, c_f, c_f, c_f, c_f, ctypes.c_long, c_p)
-_sig("udet_generator_layers", c_i, c_p, c_p, c_p)
-_sig("udet_generator_backward", c_i, c_p, c_p, c_p, c_p, c_p)
-_sig("udet_recover_backward", c_i, c_p, c_p, c_p, c_p, c_p)
-_sig("udet_grad_absmean", c_i, c_p, c_i, c_p, c_p, c_p, c_p)
-_sig("udet_stream_wait_grads", c_i, c_p, c_i, c_p)
-_sig("udet_tune_rejected", c_i)
-_sig("udet_tune_save", c_i, ctypes.c_char_p)
-_sig("udet_tune_load", c_i, ctypes.c_char_p)
+sig("udet_warp_cost_volume", c_i, c_p, c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_p)
+sig("udet_stage_workspace_bytes", c_sz, c_i)
+sig("udet_flow_normalize", c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p)
+sig("udet_charbonnier_loss", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_sz, c_p)
+sig("udet_losses_forward", c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_losses_backward", c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p)
+sig("udet_clip_or_noise", c_i, c_p, c_sz, c_f, c_p, ctypes.c_ulonglong, ctypes.c_long, c_p)
+sig("udet_adam_step", c_i, c_p, c_p, c_p, c_p, c_sz, c_f, c_f, c_f, c_f, ctypes.c_long, c_p)
+sig("udet_generator_layers", c_i, c_p, c_p, c_p)
+sig("udet_generator_backward", c_i, c_p, c_p, c_p, c_p, c_p)
+sig("udet_recover_backward", c_i, c_p, c_p, c_p, c_p, c_p)
+sig("udet_grad_absmean", c_i, c_p, c_i, c_p, c_p, c_p, c_p)
+sig("udet_stream_wait_grads", c_i, c_p, c_i, c_p)
+sig("udet_tune_rejected", c_i)
+sig("udet_tune_save", c_i, ctypes.c_char_p)
+sig("udet_tune_load", c_i, ctypes.c_char_p)
 # visualisation and training summaries (visualize.py)
-_sig("udet_flow_to_image_workspace_bytes", c_sz, c_i)
-_sig("udet_flow_to_image", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_sz, c_p)
-_sig("udet_overlay_mask", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p)
-_sig("udet_histogram_limits", c_i, c_p, c_i)
-_sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
-_sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_flow_to_image_workspace_bytes", c_sz, c_i)
+sig("udet_flow_to_image", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_sz, c_p)
+sig("udet_overlay_mask", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p)
+sig("udet_histogram_limits", c_i, c_p, c_i)
+sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
+sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)
 
 
 class UdetError(RuntimeError):

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "conv_host.h"
 #include "elementwise.h"
+#include "host_checks.h"
 
 namespace udet {
 static thread_local char g_err[512] = "";
@@ -114,20 +115,16 @@ size_t udet_restore_workspace_bytes(int n) { return n < 1 ? 0 : restore_workspac
 int udet_restore_masks_ragged(const float* masks, int n, int mh, int mw, const long long* offsets, const int* tables12, const int* coef,
                               int max_h, int max_w, unsigned char* data, int* amax, unsigned char* binary, double threshold,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (n < 1 || n > 65535 || mh < 1 || mw < 1 || (long)mh * mw > 0x7fffffffL || max_h < 1 || max_w < 1 || !masks || !offsets || !tables12 ||
-      !coef || !data || !amax) {
-    set_error("restore_masks_ragged: bad argument (n = %d in 1..65535, mask %d x %d, largest frame %d x %d, non-null masks, tables, data and amax)",
-              n, mh, mw, max_h, max_w);
+  if (bad_batch("restore_masks_ragged", n, max_h, max_w, 1)) return UDET_ERR_ARG;
+  if (mh < 1 || mw < 1 || (long)mh * mw > 0x7fffffffL || !masks || !offsets || !tables12 || !coef || !data || !amax) {
+    set_error("restore_masks_ragged: bad argument (mask %d x %d, non-null masks, tables, data and amax)", mh, mw);
     return UDET_ERR_ARG;
   }
   if (binary && (!(threshold >= 0.0) || isinf(threshold) || binary == data)) {
     set_error("restore_masks_ragged: the binary mask needs a finite threshold >= 0 and a buffer of its own");
     return UDET_ERR_ARG;
   }
-  if (!workspace || workspace_bytes < restore_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 3)) {
-    set_error("restore_masks_ragged: workspace needs %zu bytes, 4-byte aligned", restore_workspace_bytes(n));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("restore_masks_ragged", workspace, workspace_bytes, restore_workspace_bytes(n), 4)) return UDET_ERR_ARG;
   return launch_restore_masks_ragged(masks, n, mh, mw, offsets, tables12, coef, max_h, max_w, data, amax, binary, threshold, workspace,
                                      (hipStream_t)stream);
 }
@@ -138,10 +135,9 @@ size_t udet_components_workspace_bytes(size_t total_pixels, int n) {
 int udet_select_components_ragged(const unsigned char* binary, const unsigned char* gt, int n, const long long* offsets, const int* hw,
                                   int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
                                   unsigned char* selected, long long* info, void* workspace, size_t workspace_bytes, void* stream) {
-  if (n < 1 || n > 65535 || max_h < 1 || max_w < 1 || (long)max_h * max_w > 0x7fffffffL || total_pixels < 1 || !binary || !offsets || !hw ||
-      !info) {
-    set_error("select_components_ragged: bad argument (n = %d in 1..65535, largest frame %d x %d below 2^31 pixels, %zu pixels in all, "
-              "non-null binary, offsets, hw and info)", n, max_h, max_w, total_pixels);
+  if (bad_batch("select_components_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!binary || !offsets || !hw || !info) {
+    set_error("select_components_ragged: bad argument (non-null binary, offsets, hw and info)");
     return UDET_ERR_ARG;
   }
   if (connectivity != 4 && connectivity != 8) {
@@ -160,10 +156,7 @@ int udet_select_components_ragged(const unsigned char* binary, const unsigned ch
     set_error("select_components_ragged: a selecting mode needs `selected`, a buffer of its own");
     return UDET_ERR_ARG;
   }
-  if (!workspace || workspace_bytes < components_workspace_bytes(total_pixels, n) || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
-    set_error("select_components_ragged: workspace needs %zu bytes, 8-byte aligned", components_workspace_bytes(total_pixels, n));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("select_components_ragged", workspace, workspace_bytes, components_workspace_bytes(total_pixels, n), 8)) return UDET_ERR_ARG;
   if (reinterpret_cast<uintptr_t>(labels) & 3) {
     set_error("select_components_ragged: labels must be 4-byte aligned");
     return UDET_ERR_ARG;
@@ -370,10 +363,7 @@ int udet_conv2d_backward_filter(const float* x, const float* dy, const float* y_
 /* ---- per-stage entry points of the loss / optimizer tail (SURVEY 8b minimum export list) ---------------------------- */
 int udet_flow_normalize(const float* flow, float* out, int n, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
   if (!flow || !out || n < 1 || h < 1 || w < 1) { set_error("flow_normalize: bad argument"); return UDET_ERR_ARG; }
-  if (!workspace || workspace_bytes < flow_stats_doubles(n) * sizeof(double) || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
-    set_error("flow_normalize: workspace needs %zu bytes, 8-byte aligned", flow_stats_doubles(n) * sizeof(double));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("flow_normalize", workspace, workspace_bytes, flow_stats_doubles(n) * sizeof(double), 8)) return UDET_ERR_ARG;
   return launch_flow_normalize(flow, (double*)workspace, out, n, (long)h * w, (hipStream_t)stream);
 }
 size_t udet_stage_workspace_bytes(int n) {

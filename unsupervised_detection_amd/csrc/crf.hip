@@ -31,6 +31,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_checks.h"
 
 namespace udet {
 
@@ -284,10 +285,9 @@ int udet_dense_crf_rows_per_thread(int n, int max_h, int max_w) {
 int udet_dense_crf_ragged(const float* unary, const unsigned char* image_rgb, int n, const long long* offsets, const int* hw, int max_h,
                           int max_w, size_t total_pixels, float sxy, float srgb, float compat, int iters, int radius, float* q1,
                           unsigned char* labels, void* workspace, size_t workspace_bytes, void* stream) {
-  if (n < 1 || n > 65535 || max_h < 1 || max_w < 1 || (long)max_h * max_w > 0x7fffffffL || total_pixels < 1 || !unary || !image_rgb ||
-      !offsets || !hw) {
-    set_error("dense_crf_ragged: bad argument (n = %d in 1..65535, largest frame %d x %d below 2^31 pixels, %zu pixels in all, non-null "
-              "unary, image_rgb, offsets and hw)", n, max_h, max_w, total_pixels);
+  if (bad_batch("dense_crf_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!unary || !image_rgb || !offsets || !hw) {
+    set_error("dense_crf_ragged: bad argument (non-null unary, image_rgb, offsets and hw)");
     return UDET_ERR_ARG;
   }
   if (iters < 0 || radius < 1 || !(sxy > 0.f) || !(srgb > 0.f) || isinf(sxy) || isinf(srgb)) {
@@ -302,10 +302,7 @@ int udet_dense_crf_ragged(const float* unary, const unsigned char* image_rgb, in
     set_error("dense_crf_ragged: q1 must be 4-byte aligned");
     return UDET_ERR_ARG;
   }
-  if (!workspace || workspace_bytes < udet_dense_crf_workspace_bytes(total_pixels, n) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-    set_error("dense_crf_ragged: workspace needs %zu bytes, 16-byte aligned", udet_dense_crf_workspace_bytes(total_pixels, n));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("dense_crf_ragged", workspace, workspace_bytes, udet_dense_crf_workspace_bytes(total_pixels, n), 16)) return UDET_ERR_ARG;
   if (max_h > (1 << 29) || max_w > (1 << 29)) {  // tile and window coordinates are 32-bit
     set_error("dense_crf_ragged: a frame side above 2^29 is not supported");
     return UDET_ERR_SHAPE;
@@ -338,10 +335,9 @@ int udet_dense_crf_ragged(const float* unary, const unsigned char* image_rgb, in
 
 int udet_crf_unary_lookup(const unsigned char* data, const float* table, int n, const long long* offsets, const int* hw, int max_h,
                           int max_w, size_t total_pixels, float* unary, void* stream) {
-  if (n < 1 || n > 65535 || max_h < 1 || max_w < 1 || (long)max_h * max_w > 0x7fffffffL || total_pixels < 1 || !data || !table || !offsets ||
-      !hw || !unary || (reinterpret_cast<uintptr_t>(unary) & 3) || (reinterpret_cast<uintptr_t>(table) & 3)) {
-    set_error("crf_unary_lookup: bad argument (n = %d in 1..65535, largest frame %d x %d below 2^31 pixels, %zu pixels in all, non-null "
-              "data, table, offsets, hw and unary)", n, max_h, max_w, total_pixels);
+  if (bad_batch("crf_unary_lookup", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!data || !table || !offsets || !hw || !unary || (reinterpret_cast<uintptr_t>(unary) & 3) || (reinterpret_cast<uintptr_t>(table) & 3)) {
+    set_error("crf_unary_lookup: bad argument (non-null data, offsets and hw, non-null 4-byte aligned table and unary)");
     return UDET_ERR_ARG;
   }
   const long nb = ((long)max_h * max_w + 2047) / 2048;

@@ -9,6 +9,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_checks.h"
 #include "post_remap.h"
 
 namespace udet {
@@ -282,10 +283,7 @@ int udet_post_dense_crf(const float* unary, const unsigned char* image_rgb, int 
   hipStream_t s = (hipStream_t)stream_;
   const int n = h * w;
   if (!unary || !image_rgb || !q || h < 1 || w < 1 || iters < 0 || radius < 1 || sxy <= 0.f || srgb <= 0.f) { set_error("post_dense_crf: bad argument"); return UDET_ERR_ARG; }
-  if (!workspace || workspace_bytes < udet_post_crf_workspace_bytes(h, w) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-    set_error("post_dense_crf: workspace needs %zu bytes, 16-byte aligned", udet_post_crf_workspace_bytes(h, w));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("post_dense_crf", workspace, workspace_bytes, udet_post_crf_workspace_bytes(h, w), 16)) return UDET_ERR_ARG;
   float4* feat = (float4*)workspace;
   float* norm = (float*)(feat + n);
   float* kn = norm + n;

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_checks.h"
 #include "post_remap.h"
 
 namespace udet {
@@ -193,10 +194,9 @@ size_t udet_post_propagate_workspace_bytes(int total_frames, int n_seq) {
 int udet_post_propagate_sequences(const float* masks, const float* flow_prev, const float* flow_next, int n_seq, const int* seq_first,
                                   const int* seq_len, int total_frames, int h, int w, float w_s, float w_r, float* avg_f, float* avg_b,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (n_seq < 1 || n_seq > 65535 || h < 1 || w < 1 || total_frames < 1 || (long)h * w > 0x7fffffffL || !masks || !flow_prev || !flow_next ||
-      !seq_first || !seq_len || !avg_f || !avg_b) {
-    set_error("post_propagate_sequences: bad argument (n_seq = %d in 1..65535, %d frames of %d x %d below 2^31 pixels, non-null masks, "
-              "flow_prev, flow_next, seq_first, seq_len, avg_f and avg_b)", n_seq, total_frames, h, w);
+  if (bad_batch("post_propagate_sequences", n_seq, h, w, total_frames < 1 ? 0 : (size_t)total_frames)) return UDET_ERR_ARG;
+  if (!masks || !flow_prev || !flow_next || !seq_first || !seq_len || !avg_f || !avg_b) {
+    set_error("post_propagate_sequences: bad argument (non-null masks, flow_prev, flow_next, seq_first, seq_len, avg_f and avg_b)");
     return UDET_ERR_ARG;
   }
   if ((reinterpret_cast<uintptr_t>(flow_prev) | reinterpret_cast<uintptr_t>(flow_next)) & 7) {  // a pixel's (u, v) is one 8-byte load
@@ -207,10 +207,8 @@ int udet_post_propagate_sequences(const float* masks, const float* flow_prev, co
     set_error("post_propagate_sequences: masks, avg_f and avg_b must be three different buffers");
     return UDET_ERR_ARG;
   }
-  if (!workspace || workspace_bytes < udet_post_propagate_workspace_bytes(total_frames, n_seq) || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
-    set_error("post_propagate_sequences: workspace needs %zu bytes, 16-byte aligned", udet_post_propagate_workspace_bytes(total_frames, n_seq));
+  if (bad_workspace("post_propagate_sequences", workspace, workspace_bytes, udet_post_propagate_workspace_bytes(total_frames, n_seq), 16))
     return UDET_ERR_ARG;
-  }
   SeqArgs a;
   a.masks = masks; a.flow[0] = flow_prev; a.flow[1] = flow_next;
   a.seq_first = seq_first; a.seq_len = seq_len;

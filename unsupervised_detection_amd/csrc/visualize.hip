@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "host_checks.h"
 
 namespace udet {
 
@@ -269,10 +270,7 @@ int udet_flow_to_image(const float* flow, const float* mask, const double* stats
     set_error("flow_to_image: bad argument (mask and stats8 go together)");
     return UDET_ERR_ARG;
   }
-  if (!workspace || workspace_bytes < udet_flow_to_image_workspace_bytes(n) || (reinterpret_cast<uintptr_t>(workspace) & 3)) {
-    set_error("flow_to_image: workspace needs %zu bytes, 4-byte aligned", udet_flow_to_image_workspace_bytes(n));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("flow_to_image", workspace, workspace_bytes, udet_flow_to_image_workspace_bytes(n), 4)) return UDET_ERR_ARG;
   const long HW = (long)h * w;
   float* part = (float*)workspace;
   hipLaunchKernelGGL(flow_maxrad_kernel, dim3(FI_SPLIT, n), dim3(256), 0, (hipStream_t)stream, flow, HW, part);
@@ -308,10 +306,7 @@ int udet_grad_histogram(const float* g, const long long* seg_offsets, int nseg, 
                         size_t workspace_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   if (!g || !seg_offsets || !stats || !counts || nseg < 1 || nseg > 65535) { set_error("grad_histogram: bad argument"); return UDET_ERR_ARG; }
-  if (!workspace || workspace_bytes < udet_grad_histogram_workspace_bytes(nseg) || (reinterpret_cast<uintptr_t>(workspace) & 7)) {
-    set_error("grad_histogram: workspace needs %zu bytes, 8-byte aligned", udet_grad_histogram_workspace_bytes(nseg));
-    return UDET_ERR_ARG;
-  }
+  if (bad_workspace("grad_histogram", workspace, workspace_bytes, udet_grad_histogram_workspace_bytes(nseg), 8)) return UDET_ERR_ARG;
   double* limits = (double*)workspace;
   double* part = (double*)((char*)workspace + kLimitBytes);
   UDET_HIP(hipMemcpyAsync(limits, histogram_limits(), GH_BUCKETS * sizeof(double), hipMemcpyHostToDevice, s));

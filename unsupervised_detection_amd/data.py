@@ -9,6 +9,9 @@ uint8 -> /255 - 0.5, flips, the crop window and the TF-1.13 legacy resize.  Same
   Davis2016Reader.random_crop_image_pair / central_cropping / augment_pair   :101-146, random_flip_images aug_flips.py:35-45
   Davis2016Reader.image_inputs / test_inputs / augmented_inputs              :180-354  (pair tables + batching)
 
+Frames of different sizes (FBMS-59, SegTrackV2) travel as one packed batch (ragged.py): RaggedLoader / RaggedBatch /
+crop_flip_resize_ragged at the end of this file.
+
 JPEG / PNG decoding stays on the host (Pillow); batches are dicts {"img1","img2","gt_mask","fname"} of device tensors, the
 form AdversarialLearner consumes (config.data_source)."""
 from __future__ import annotations
@@ -18,10 +21,12 @@ import os
 import numpy as np
 import torch
 
-from ._ffi import c_f, c_i, c_p, check, lib
+from ._ffi import c_f, c_i, c_p, check, lib, sig
+from .ragged import PackedLayout, PackedSamples, as_layout, check_packed_tables, require_tensor, upload_tables
 
-lib.udet_crop_flip_resize.restype = c_i
-lib.udet_crop_flip_resize.argtypes = [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p]
+sig("udet_crop_flip_resize", c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_p)
+sig("udet_crop_flip_resize_ragged", c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p)
+_upload_tables = upload_tables  # the name tools know
 
 READER_H, READER_W = 384, 640
 
@@ -29,9 +34,7 @@ READER_H, READER_W = 384, 640
 def crop_flip_resize(src: torch.Tensor, out_h: int, out_w: int, params=None, nearest: bool = False, div: float = 1.0,
                      add: float = 0.0) -> torch.Tensor:
     """src [N,H,W,C] uint8 or float32 on the GPU; params int array [N,6] = (y0, x0, crop_h, crop_w, flip_lr, flip_td)."""
-    if not (src.is_cuda and src.is_contiguous() and src.dtype in (torch.uint8, torch.float32) and src.dim() == 4):
-        raise ValueError("src must be a contiguous [N,H,W,C] uint8/float32 CUDA(HIP) tensor")
-    n, h, w, c = src.shape
+    n, h, w, c = require_tensor(src, "src [N,H,W,C]", (torch.uint8, torch.float32), 4).shape
     prm = None
     if params is not None:
         pa = np.ascontiguousarray(np.asarray(params, dtype=np.int32).reshape(n, 6))
@@ -283,64 +286,46 @@ def synthetic_davis_pairs(batch: int, seed: int, h: int = 480, w: int = 854, max
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Ragged input stage: frames of different sizes in one batch (FBMS-59, SegTrackV2; datasets.py).  One pinned staging buffer and one
-# H2D copy per batch, one udet_crop_flip_resize_ragged launch per resize; per sample bit-identical to crop_flip_resize.
+# Ragged input stage: frames of different sizes in one batch (FBMS-59, SegTrackV2; datasets.py), in the packed layout of ragged.py.  One
+# pinned staging buffer and one H2D copy per batch, one udet_crop_flip_resize_ragged launch per resize; per sample bit-identical to
+# crop_flip_resize.
 # ---------------------------------------------------------------------------------------------------------------------------------
-lib.udet_crop_flip_resize_ragged.restype = c_i
-lib.udet_crop_flip_resize_ragged.argtypes = [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p]
+def _check_crop_params(params, size):
+    """params [n,6] = (y0, x0, crop_h, crop_w, flip_lr, flip_td) against the samples' own sizes [n,2] -> int32 [n,6], or None."""
+    if params is None:
+        return None
+    pa = np.ascontiguousarray(np.asarray(params, dtype=np.int32).reshape(len(size), 6))
+    if (pa[:, 0] < 0).any() or (pa[:, 1] < 0).any() or (pa[:, 2] < 1).any() or (pa[:, 3] < 1).any() or \
+            (pa[:, 0] + pa[:, 2] > size[:, 0]).any() or (pa[:, 1] + pa[:, 3] > size[:, 1]).any():
+        raise ValueError("crop window outside its own image")
+    if not np.isin(pa[:, 4:], (0, 1)).all():
+        raise ValueError("flip_lr / flip_td must be 0 or 1")
+    return pa
 
 
 def check_ragged_tables(offsets, hw, c, numel, params=None):
-    """Host validation of the tables of udet_crop_flip_resize_ragged (the C entry point does not read device tables).  Returns
-    (offsets int64 [n], hw int32 [n,2], params int32 [n,6] or None); raises ValueError on a sample outside the packed buffer of
-    `numel` elements, a crop window outside its own image or a flip flag other than 0 / 1."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
-    n = len(off)
-    if n < 1 or c < 1:
-        raise ValueError("ragged batch needs at least one sample and one channel")
-    size = np.asarray(hw, dtype=np.int64).reshape(n, 2)
-    if (size < 1).any() or (size > np.iinfo(np.int32).max).any():
-        raise ValueError("sample sizes must be at least 1x1")
-    if (off < 0).any() or (off + size[:, 0] * size[:, 1] * c > numel).any():
-        raise ValueError("sample outside the packed buffer (offset + h*w*c past its end)")
-    pa = None
-    if params is not None:
-        pa = np.ascontiguousarray(np.asarray(params, dtype=np.int32).reshape(n, 6))
-        if (pa[:, 0] < 0).any() or (pa[:, 1] < 0).any() or (pa[:, 2] < 1).any() or (pa[:, 3] < 1).any() or \
-                (pa[:, 0] + pa[:, 2] > size[:, 0]).any() or (pa[:, 1] + pa[:, 3] > size[:, 1]).any():
-            raise ValueError("crop window outside its own image")
-        if not np.isin(pa[:, 4:], (0, 1)).all():
-            raise ValueError("flip_lr / flip_td must be 0 or 1")
-    return off, np.ascontiguousarray(size.astype(np.int32)), pa
-
-
-def _upload_tables(arrays, device):
-    """Host int arrays -> one pinned buffer -> one non-blocking copy on the current stream; device views in the same order.
-    (A pinned block of torch's host allocator is not handed out again before the copy that read it has finished.)"""
-    raw = [np.ascontiguousarray(a).view(np.uint8).reshape(-1) for a in arrays]
-    pos = np.cumsum([0] + [len(r) for r in raw])
-    host = torch.from_numpy(np.concatenate(raw)).pin_memory()
-    dev = host.to(device, non_blocking=True)
-    return [dev[int(pos[i]):int(pos[i + 1])].view(torch.int64 if a.dtype == np.int64 else torch.int32) for i, a in enumerate(arrays)]
+    """Host validation of the tables of udet_crop_flip_resize_ragged: ragged.check_packed_tables (samples may overlap: the buffer is
+    only read) plus, per sample, a crop window inside its own image and flip flags of 0 / 1.  Returns (offsets int64 [n], hw int32
+    [n,2], params int32 [n,6] or None); raises ValueError."""
+    off, size = check_packed_tables(offsets, hw, numel, c, overlap_ok=True)
+    return off, size, _check_crop_params(params, size)
 
 
 def crop_flip_resize_ragged(src: torch.Tensor, offsets, hw, c: int, out_h: int, out_w: int, params=None, nearest: bool = False,
                             div: float = 1.0, add: float = 0.0, device_tables=None) -> torch.Tensor:
-    """crop_flip_resize over n samples of different sizes, one launch.  src: 1-D contiguous uint8 / float32 GPU tensor, sample i
-    = [hw[i,0], hw[i,1], c] at element offsets[i]; offsets [n] and hw [n,2] host arrays; params [n,6] = (y0, x0, crop_h, crop_w,
-    flip_lr, flip_td) relative to each sample's own size, or None.  device_tables = (offsets, hw) already on the device (the
-    RaggedLoader's copy of these same host tables), else they are uploaded here.  Returns float32 [n,out_h,out_w,c]; row i is
-    bit-identical to crop_flip_resize of sample i alone.  The tables are validated on the host before anything is launched."""
-    off, size, pa = check_ragged_tables(offsets, hw, c, src.numel(), params)
-    if not (src.is_cuda and src.is_contiguous() and src.dtype in (torch.uint8, torch.float32) and src.dim() == 1):
-        raise ValueError("src must be a contiguous 1-D uint8/float32 CUDA(HIP) tensor of packed samples")
-    n = len(off)
-    if device_tables is None:
-        device_tables = _upload_tables([off, size], src.device)
-    d_off, d_hw = device_tables
+    """crop_flip_resize over n samples of different sizes, one launch.  src: 1-D contiguous uint8 / float32 GPU tensor packed by
+    offsets [n] / hw [n,2] with c channels (host arrays, validated here before anything is launched; or a PackedLayout as offsets with
+    hw=None, taken as it is); params [n,6] = (y0, x0, crop_h, crop_w, flip_lr, flip_td) relative to each sample's own size, or None.
+    device_tables = (offsets, hw) already on the device, else the layout's own copies are used (uploaded once).  Returns float32
+    [n,out_h,out_w,c]; row i is bit-identical to crop_flip_resize of sample i alone."""
+    layout = as_layout(offsets, hw, src.numel(), c, overlap_ok=True)
+    pa = _check_crop_params(params, layout.hw)
+    require_tensor(src, "src (packed samples)", (torch.uint8, torch.float32), 1)
+    n = layout.n
+    d_off, d_hw = layout.device_tables(src.device) if device_tables is None else device_tables
     if d_off.numel() != n or d_hw.numel() != 2 * n or d_off.dtype != torch.int64 or d_hw.dtype != torch.int32:
         raise ValueError("device tables do not match the host tables")
-    prm = _upload_tables([pa], src.device)[0] if pa is not None else None
+    prm = upload_tables([pa], src.device)[0] if pa is not None else None
     out = torch.empty((n, out_h, out_w, c), dtype=torch.float32, device=src.device)
     check(lib.udet_crop_flip_resize_ragged(src.data_ptr(), int(src.dtype == torch.uint8), int(nearest), n, c, d_off.data_ptr(),
                                            d_hw.data_ptr(), prm.data_ptr() if prm is not None else None, out.data_ptr(), out_h,
@@ -348,20 +333,17 @@ def crop_flip_resize_ragged(src: torch.Tensor, offsets, hw, c: int, out_h: int, 
     return out
 
 
-class RaggedBatch(object):
-    """Decoded frames of different sizes packed on the device: data (1-D uint8), host tables offsets [n] / hw [n,2], their device
-    copies, c channels."""
+class RaggedBatch(PackedSamples):
+    """Decoded frames of different sizes packed on the device: data (1-D uint8) in `layout` (host tables offsets [n] / hw [n,2] with
+    the device copies dev_offsets / dev_hw handed in; offsets may be the PackedLayout itself, hw=None), c channels."""
 
     def __init__(self, data, offsets, hw, c, dev_offsets, dev_hw):
-        self.data, self.offsets, self.hw, self.c = data, offsets, hw, c
-        self.dev_offsets, self.dev_hw = dev_offsets, dev_hw
-
-    def __len__(self):
-        return len(self.offsets)
+        PackedSamples.__init__(self, as_layout(offsets, hw, data.numel(), c, overlap_ok=True), data.device)  # read-only: samples may share bytes
+        self.layout.adopt_device_tables(dev_offsets, dev_hw)
+        self.data, self.c = data, c
 
     def resize(self, out_h, out_w, params=None, nearest=False, div=1.0, add=0.0):
-        return crop_flip_resize_ragged(self.data, self.offsets, self.hw, self.c, out_h, out_w, params, nearest, div, add,
-                                       (self.dev_offsets, self.dev_hw))
+        return crop_flip_resize_ragged(self.data, self.layout, None, self.c, out_h, out_w, params, nearest, div, add)
 
     def preprocess_image(self):
         """preprocess_image of every frame (uint8 -> /255 - 0.5, legacy bilinear to READER_H x READER_W)."""
@@ -394,12 +376,11 @@ class RaggedLoader(object):
         for p, a in zip(paths, arrs):
             if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != channels:
                 raise ValueError("%s: decoded to %s %s, expected uint8 [H,W,%d]" % (p, a.dtype, a.shape, channels))
-        hw = np.array([a.shape[:2] for a in arrs], dtype=np.int32).reshape(n, 2)
+        layout = PackedLayout.packed([a.shape[:2] for a in arrs], channels)
+        off, hw = layout.offsets, layout.hw
         sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * channels
-        off = np.zeros(n, np.int64)
-        off[1:] = np.cumsum(sizes)[:-1]
         head = 16 * n  # int64 offsets [n] + int32 sizes [n,2], then the pixels
-        total = head + int(sizes.sum())
+        total = head + layout.numel
         k = self._next
         self._next = (k + 1) % len(self._slots)
         if self._events[k] is not None:
@@ -419,4 +400,4 @@ class RaggedLoader(object):
         ev = torch.cuda.Event()
         ev.record(stream)
         self._events[k] = ev
-        return RaggedBatch(dev[head:], off, hw, channels, dev[:8 * n].view(torch.int64), dev[8 * n:head].view(torch.int32))
+        return RaggedBatch(dev[head:], layout, None, channels, dev[:8 * n].view(torch.int64), dev[8 * n:head].view(torch.int32))

@@ -12,6 +12,8 @@ post_processing/post_processing.py:32-46:
   restore_masks(masks, native_hw, ...)          one call of the ragged kernel (csrc/restore.hip) -> RestoredMasks
   select_components(binary, offsets, hw, gt, mode, ...)   connected components of the restored masks and the choice of one per sample
                                                 (csrc/components.hip, udet_select_components_ragged) -> ComponentSelection
+  RestoredMasks / GtBatch / ComponentSelection  buffers of one batch in one ragged.PackedLayout (the packed layout): the
+                                                annotations' layout is built once per batch and handed from call to call
   check_crf_tables / load_images_device / crf_refine_restored   the full-resolution dense CRF of run_crf_original_resolution on the
                                                 restored batch: unary from the restored bytes, the frames read at their own size,
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
@@ -30,17 +32,15 @@ import os
 import numpy as np
 import torch
 
-from ._ffi import c_i, c_p, c_sz, check, lib
-from .post_processing import _pil_coeffs_host
+from . import ragged
+from ._ffi import c_i, c_p, c_sz, check, lib, sig
+from .post_processing import CRF_MAX_SAMPLES, _pil_coeffs_host, default_radius, dense_crf_ragged, unary_from_restored
+from .ragged import PackedLayout, PackedSamples, as_layout, check_packed_tables, require_tensor, workspace
 
-lib.udet_restore_workspace_bytes.restype = c_sz
-lib.udet_restore_workspace_bytes.argtypes = [c_i]
-lib.udet_restore_masks_ragged.restype = c_i
-lib.udet_restore_masks_ragged.argtypes = [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, c_p, c_sz, c_p]
-lib.udet_components_workspace_bytes.restype = c_sz
-lib.udet_components_workspace_bytes.argtypes = [c_sz, c_i]
-lib.udet_select_components_ragged.restype = c_i
-lib.udet_select_components_ragged.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]
+sig("udet_restore_workspace_bytes", c_sz, c_i)
+sig("udet_restore_masks_ragged", c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, c_p, c_sz, c_p)
+sig("udet_components_workspace_bytes", c_sz, c_sz, c_i)
+sig("udet_select_components_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p)
 
 TAB = 12  # int32 per sample: y0 x0 h w H W | hk hb hks | vk vb vks   (include/udet.h)
 
@@ -78,11 +78,8 @@ def build_restore_tables(native_hw, mh, mw, crop=0.9, offsets=None):
     n = len(hw)
     if n < 1:
         raise ValueError("restore needs at least one sample")
-    if (hw < 1).any() or (hw[:, 0] * hw[:, 1] > np.iinfo(np.int32).max).any():
-        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
     if offsets is None:
-        off = np.zeros(n, np.int64)
-        off[1:] = np.cumsum(hw[:, 0] * hw[:, 1])[:-1]
+        off = PackedLayout.packed(hw).offsets
     else:
         off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
         if len(off) != n:
@@ -110,23 +107,16 @@ def build_restore_tables(native_hw, mh, mw, crop=0.9, offsets=None):
 
 def check_restore_tables(offsets, tab, coef, numel, mh, mw):
     """Host validation of the device tables of udet_restore_masks_ragged (its C entry point does not read device memory): raises
-    ValueError on a sample outside the output buffer of `numel` bytes, overlapping samples, a box outside its own frame, a
+    ValueError on tables ragged.check_packed_tables refuses for an output buffer of `numel` bytes, a box outside its own frame, a
     coefficient window outside coef, or a tap outside the mask.  Returns the three arrays in the dtypes the kernel reads."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
     tab = np.ascontiguousarray(np.asarray(tab, dtype=np.int32).reshape(-1, TAB))
     coef = np.ascontiguousarray(np.asarray(coef, dtype=np.int32).reshape(-1))
-    n = len(off)
-    if n < 1 or len(tab) != n or mh < 1 or mw < 1:
-        raise ValueError("restore needs at least one sample, one table row per sample and a mask of at least 1x1")
+    if mh < 1 or mw < 1:
+        raise ValueError("restore needs a mask of at least 1x1")
     t = tab.astype(np.int64)
     y0, x0, h, w, H, W = (t[:, k] for k in range(6))
-    if (H < 1).any() or (W < 1).any() or (H * W > np.iinfo(np.int32).max).any():
-        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
-    if (off < 0).any() or (off + H * W > numel).any():
-        raise ValueError("sample outside the output buffer (offset + H*W past its end)")
-    order = np.argsort(off, kind="stable")
-    if (off[order][1:] < (off + H * W)[order][:-1]).any():
-        raise ValueError("samples overlap in the output buffer")
+    off, _ = check_packed_tables(offsets, t[:, 4:6], numel, buffer="output buffer")
+    n = len(off)
     if (y0 < 0).any() or (x0 < 0).any() or (h < 1).any() or (w < 1).any() or (y0 + h > H).any() or (x0 + w > W).any():
         raise ValueError("box outside its own frame")
     seen = set()
@@ -152,20 +142,13 @@ def check_restore_tables(offsets, tab, coef, numel, mh, mw):
     return off, tab, coef
 
 
-class RestoredMasks(object):
-    """Result of restore_masks: data (packed uint8, device), binary (same layout, 0 / 1, or None), host offsets [n] / hw [n,2],
-    amax (device int32 [n])."""
+class RestoredMasks(PackedSamples):
+    """Result of restore_masks: data (packed uint8, device), binary (same layout, 0 / 1, or None), amax (device int32 [n]); their
+    `layout` is given as host offsets [n] / hw [n,2], or as the PackedLayout itself (hw=None)."""
 
     def __init__(self, data, binary, offsets, hw, amax):
-        self.data, self.binary, self.offsets, self.hw, self.amax = data, binary, offsets, hw, amax
-
-    def __len__(self):
-        return len(self.offsets)
-
-    def _view(self, buf, i):
-        H, W = (int(v) for v in self.hw[i])
-        o = int(self.offsets[i])
-        return buf[o:o + H * W].view(H, W)
+        PackedSamples.__init__(self, as_layout(offsets, hw, data.numel()), data.device)
+        self.data, self.binary, self.amax = data, binary, amax
 
     def sample(self, i):
         """[H_i, W_i] uint8 view of sample i."""
@@ -180,32 +163,10 @@ class RestoredMasks(object):
         """float64 [H_i, W_i] = byte / (amax + 1e-8): the mask run_crf_original_resolution hands to its CRF (crf_refine.py:94)."""
         return self.sample(i).double() / (self.amax[i].double() + 1e-8)
 
-    def stack(self, idx):
-        """[k,H,W,1] float32 0 / 1 tensor of the binary masks of samples idx (all of one size): what the metrics kernels take."""
-        idx = list(idx)
-        if len({tuple(int(v) for v in self.hw[i]) for i in idx}) != 1:
-            raise ValueError("stack: the samples must be of one size")
-        return torch.stack([self.binary_sample(i) for i in idx]).to(torch.float32).unsqueeze(-1).contiguous()
 
-
-_checked, _table_cache = set(), {}
-
-
-def _table_key(off, tab, coef, numel, mh, mw):
-    """Everything check_restore_tables reads: a batch with the tables of an earlier one (every DAVIS batch) is validated and
-    uploaded once."""
-    return (off.tobytes(), tab.tobytes(), coef.tobytes(), int(numel), int(mh), int(mw))
-
-
-def _device_tables(key, off, tab, coef, device):
-    from .data import _upload_tables
-    key = key + (str(device),)
-    if key not in _table_cache:
-        if len(_table_cache) >= 16:
-            _table_cache.clear()
-        _table_cache[key] = _upload_tables([off, tab, coef], device)
-        torch.cuda.current_stream(device).synchronize()  # once per table set: a later call may run on another stream
-    return _table_cache[key]
+# Everything the restore tables are built from -> [the layout of a call that gave none, off, tab, coef, {device: (tab, coef) there}]: a
+# batch with the sizes of an earlier one (every DAVIS batch) has its tables built, validated and uploaded once.
+_restore_tables = {}
 
 
 def restore_masks(masks, native_hw, crop=0.9, threshold=None, offsets=None, out=None, binary_out=None) -> RestoredMasks:
@@ -213,7 +174,8 @@ def restore_masks(masks, native_hw, crop=0.9, threshold=None, offsets=None, out=
     bytescale over the whole mask, Pillow's 8-bit bilinear resize to restore_box(H_i, W_i, crop), pasted into zeros; amax[i] = the
     patch's largest byte; threshold (float, optional): also the binary mask byte / (amax + 1e-8) > threshold (float64).  One call
     of udet_restore_masks_ragged: at most three launches for the whole batch.  offsets / out / binary_out: a caller-owned packed
-    uint8 buffer and the byte offset of every sample in it (default: a fresh buffer, samples back to back).  The tables are
+    uint8 buffer and the byte offset of every sample in it (default: a fresh buffer, samples back to back).  native_hw may be the
+    PackedLayout of the output (the annotations' own: its sizes, offsets and device tables are used as they are).  The tables are
     validated on the host before anything is launched (ValueError)."""
     m = masks if isinstance(masks, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(masks, dtype=np.float32))
     if m.dim() == 4 and m.shape[-1] == 1:
@@ -221,37 +183,46 @@ def restore_masks(masks, native_hw, crop=0.9, threshold=None, offsets=None, out=
     if m.dim() != 3:
         raise ValueError("masks must be [n,mh,mw] or [n,mh,mw,1]")
     n, mh, mw = (int(v) for v in m.shape)
+    given = native_hw if isinstance(native_hw, PackedLayout) else None
     hw = np.asarray(native_hw, dtype=np.int64).reshape(-1, 2)
-    if len(hw) != n:
-        raise ValueError("one native size per mask")
-    off, tab, coef = build_restore_tables(hw, mh, mw, crop, offsets)
-    total = int((hw[:, 0] * hw[:, 1]).sum()) if out is None else int(out.numel())
+    if len(hw) != n or (given is not None and offsets is not None):
+        raise ValueError("one native size per mask (a PackedLayout brings its own offsets)")
+    if given is not None:
+        offsets = given.offsets
+    total = int(out.numel()) if out is not None else (int((hw[:, 0] * hw[:, 1]).sum()) if given is None else given.numel)
     if threshold is not None and not (0.0 <= float(threshold) < float("inf")):
         raise ValueError("threshold must be finite and >= 0")
-    key = _table_key(off, tab, coef, total, mh, mw)
-    if key not in _checked:  # before the device is touched
-        off, tab, coef = check_restore_tables(off, tab, coef, total, mh, mw)
-        if len(_checked) >= 64:
-            _checked.clear()
-        _checked.add(key)
+    key = (hw.tobytes(), None if offsets is None else np.asarray(offsets, dtype=np.int64).tobytes(), total, mh, mw, float(crop))
+    if key not in _restore_tables:  # before the device is touched
+        off, tab, coef = check_restore_tables(*build_restore_tables(hw, mh, mw, crop, offsets), total, mh, mw)
+        if len(_restore_tables) >= 16:
+            _restore_tables.clear()
+        _restore_tables[key] = [None, off, tab, coef, {}]
+    entry = _restore_tables[key]
+    if given is None and entry[0] is None:
+        entry[0] = PackedLayout(entry[1], hw, total, buffer="output buffer")
+    layout = entry[0] if given is None else as_layout(given, None, total, buffer="output buffer")
+    tab, coef, on_device = entry[2:]
     m = m.to("cuda", torch.float32).contiguous()
     dev = m.device
     for buf, name in ((out, "out"), (binary_out, "binary_out")):
-        if buf is not None and not (buf.is_cuda and buf.dtype == torch.uint8 and buf.dim() == 1 and buf.is_contiguous() and
-                                    buf.numel() == total):
-            raise ValueError("{} must be a contiguous 1-D uint8 CUDA(HIP) tensor of the output buffer's size".format(name))
+        if buf is not None:
+            require_tensor(buf, name + " (the output buffer)", torch.uint8, 1, total)
     data = torch.empty(total, dtype=torch.uint8, device=dev) if out is None else out
     binary = None
     if threshold is not None:
         binary = torch.empty(total, dtype=torch.uint8, device=dev) if binary_out is None else binary_out
-    d_off, d_tab, d_coef = _device_tables(key, off, tab, coef, dev)
+    if dev not in on_device:
+        on_device[dev] = ragged.upload_tables([tab, coef], dev)
+        torch.cuda.current_stream(dev).synchronize()  # once per table set: a later call may run on another stream
+    (d_tab, d_coef), (d_off, _) = on_device[dev], layout.device_tables(dev)
     amax = torch.empty(n, dtype=torch.int32, device=dev)  # zeroed by the call
-    ws = torch.empty(max(int(lib.udet_restore_workspace_bytes(n)), 4), dtype=torch.uint8, device=dev)
+    ws = workspace(lib.udet_restore_workspace_bytes(n), 4, dev)
     check(lib.udet_restore_masks_ragged(m.data_ptr(), n, mh, mw, d_off.data_ptr(), d_tab.data_ptr(), d_coef.data_ptr(),
-                                        int(hw[:, 0].max()), int(hw[:, 1].max()), data.data_ptr(), amax.data_ptr(),
+                                        layout.max_h, layout.max_w, data.data_ptr(), amax.data_ptr(),
                                         None if binary is None else binary.data_ptr(), 0.0 if threshold is None else float(threshold),
                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
-    return RestoredMasks(data, binary, off, hw.astype(np.int32), amax)
+    return RestoredMasks(data, binary, layout, None, amax)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -281,19 +252,18 @@ def _segtrack_loader(path, channels):
 GT_RULES = {"DAVIS2016": GtRule(None, 0.1), "SEGTRACK": GtRule(_segtrack_loader, 0.1), "FBMS": GtRule(_fbms_loader, 0.5)}
 
 
-class GtBatch(object):
-    """Annotations of one batch, binarised at native size: data (packed uint8 0 / 1), host offsets / hw."""
+class GtBatch(PackedSamples):
+    """Annotations of one batch, binarised at native size: data (packed uint8 0 / 1) in the layout given as host offsets / hw, or as
+    the PackedLayout itself (hw=None)."""
 
-    def __init__(self, data, offsets, hw):
-        self.data, self.offsets, self.hw = data, offsets, hw
+    def __init__(self, data, offsets, hw=None):
+        PackedSamples.__init__(self, as_layout(offsets, hw, data.numel()), data.device)
+        self.data = data
 
     def sample(self, i):
-        H, W = (int(v) for v in self.hw[i])
-        o = int(self.offsets[i])
-        return self.data[o:o + H * W].reshape(H, W)
+        return self._view(self.data, i)
 
-    def stack(self, idx):
-        return torch.stack([self.sample(i) for i in idx]).to(torch.float32).unsqueeze(-1).contiguous()
+    binary_sample = sample
 
 
 _ragged_loader = None
@@ -306,7 +276,7 @@ def load_gt_device(paths, rule):
     if _ragged_loader is None:
         _ragged_loader = data.RaggedLoader()
     rb = _ragged_loader.load(list(paths), 1, loader=rule.loader)
-    return GtBatch((rb.data.double() / 255.0 > rule.threshold).to(torch.uint8), rb.offsets, rb.hw)
+    return GtBatch((rb.data.double() / 255.0 > rule.threshold).to(torch.uint8), rb.layout)
 
 
 def score_device(gt_stack, pred_stack, bound_th):
@@ -328,36 +298,24 @@ COMPONENT_TILE = (32, 64)  # UDET_COMPONENTS_TILE_H / _W: the tile of the LDS un
 
 
 def check_component_tables(offsets, hw, numel):
-    """Host validation of the device tables of udet_select_components_ragged, by check_restore_tables' rules: raises ValueError on a
-    sample outside the packed buffer of `numel` elements, overlapping samples or a frame of 2^31 pixels or more.  Returns (offsets
-    int64 [n], hw int32 [n,2]) as the kernels read them."""
-    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
-    size = np.asarray(hw, dtype=np.int64).reshape(-1, 2)
-    if len(off) < 1 or len(size) != len(off):
-        raise ValueError("components need at least one sample and one (H, W) per offset")
-    H, W = size[:, 0], size[:, 1]
-    if (H < 1).any() or (W < 1).any() or (H * W > np.iinfo(np.int32).max).any():
-        raise ValueError("native sizes must be at least 1x1 (and below 2^31 pixels)")
-    if (off < 0).any() or (off + H * W > numel).any():
-        raise ValueError("sample outside the packed buffer (offset + H*W past its end)")
-    order = np.argsort(off, kind="stable")
-    if (off[order][1:] < (off + H * W)[order][:-1]).any():
-        raise ValueError("samples overlap in the packed buffer")
-    return off, np.ascontiguousarray(size.astype(np.int32))
+    """Host validation of the device tables of udet_select_components_ragged: ragged.check_packed_tables for a packed buffer of
+    `numel` elements.  Returns (offsets int64 [n], hw int32 [n,2]) as the kernels read them."""
+    return check_packed_tables(offsets, hw, numel)
 
 
-class ComponentSelection(object):
+class ComponentSelection(PackedSamples):
     """Result of select_components: selected (packed uint8 0 / 1, device; None in mode "label"), labels (packed int32, root + 1 /
-    0, or None), info (device int64 [n,4] = components, chosen root or -1, its area, its inter), host offsets [n] / hw [n,2].
-    binary_sample / stack have the contract of RestoredMasks: the scoring and export loops take either."""
+    0, or None), info (device int64 [n,4] = components, chosen root or -1, its area, its inter); their `layout` is given as host
+    offsets [n] / hw [n,2], or as the PackedLayout itself (hw=None).  binary_sample / stack have the contract of RestoredMasks: the
+    scoring and export loops take either."""
 
     def __init__(self, selected, labels, info, offsets, hw):
-        self.selected, self.labels, self.info, self.offsets, self.hw = selected, labels, info, offsets, hw
-
-    def __len__(self):
-        return len(self.offsets)
-
-    _view = RestoredMasks._view
+        if isinstance(offsets, PackedLayout) or selected is not None or labels is not None:
+            numel = offsets.numel if isinstance(offsets, PackedLayout) else (labels if selected is None else selected).numel()
+        else:  # no packed buffer to measure: the tables' own extent
+            numel = int((np.asarray(offsets, np.int64).reshape(-1) + np.asarray(hw, np.int64).reshape(-1, 2).prod(1)).max())
+        PackedSamples.__init__(self, as_layout(offsets, hw, numel), info.device)
+        self.selected, self.labels, self.info = selected, labels, info
 
     def binary_sample(self, i):
         if self.selected is None:
@@ -369,57 +327,47 @@ class ComponentSelection(object):
             raise ValueError("selected without want_labels: no labels")
         return self._view(self.labels, i)
 
-    stack = RestoredMasks.stack
-
 
 def select_components(binary, offsets=None, hw=None, gt=None, mode="largest", connectivity=8, want_labels=False) -> ComponentSelection:
     """Connected components of n packed binary masks and one of them chosen per sample, in one call of
-    udet_select_components_ragged (five launches whatever n is).  binary: a RestoredMasks (its binary masks, offsets and sizes), or a
-    1-D uint8 device tensor with host offsets [n] / hw [n,2]; gt: a GtBatch or a 1-D uint8 device tensor packed like binary, or
-    None.  connectivity 4 or 8.  mode "label": components only; "largest": the largest component, ties to the smaller root (the
+    udet_select_components_ragged (five launches whatever n is).  binary: a RestoredMasks (its binary masks and layout), or a 1-D
+    uint8 device tensor with host offsets [n] / hw [n,2] (or a PackedLayout as offsets, hw=None: taken as it is); gt: a GtBatch or a
+    1-D uint8 device tensor packed like binary, or None.  connectivity 4 or 8.  mode "label": components only; "largest": the largest component, ties to the smaller root (the
     smallest row-major index of the component); "best_gt": the largest IoU with gt, ties to the larger area, then the smaller root.
     want_labels: also the int32 labels (root + 1, background 0; the roots in ascending order number as scipy.ndimage.label does).
     Arguments and tables are validated on the host before the device is touched (ValueError)."""
     if isinstance(binary, RestoredMasks):
         if binary.binary is None:
             raise ValueError("restored without a threshold: no binary mask")
-        binary, offsets, hw = binary.binary, binary.offsets, binary.hw
-    if offsets is None or hw is None:
+        binary, offsets, hw = binary.binary, binary.layout, None
+    if offsets is None or (hw is None and not isinstance(offsets, PackedLayout)):
         raise ValueError("a packed buffer needs its offsets and sizes")
     if mode not in COMPONENT_MODES:
         raise ValueError("mode must be one of {}".format(sorted(COMPONENT_MODES)))
     if connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8")
-    if not isinstance(binary, torch.Tensor) or binary.dtype != torch.uint8 or binary.dim() != 1:
-        raise ValueError("binary must be a 1-D uint8 tensor of packed samples")
-    total = int(binary.numel())
-    off, size = check_component_tables(offsets, hw, total)
+    total = int(require_tensor(binary, "binary (packed samples)", torch.uint8, 1, cuda=False).numel())
+    layout = as_layout(offsets, hw, total)  # raw tables: validated before the device is touched
     if isinstance(gt, GtBatch):
-        g_off, g_hw = check_component_tables(gt.offsets, gt.hw, total)
-        if not (np.array_equal(g_off, off) and np.array_equal(g_hw, size)):
+        if not gt.layout.same_as(layout):
             raise ValueError("the annotations must be packed like the masks (same offsets and sizes)")
         gt = gt.data
     if mode == "best_gt" and gt is None:
         raise ValueError('mode "best_gt" needs the annotations')
-    if gt is not None and not (isinstance(gt, torch.Tensor) and gt.dtype == torch.uint8 and gt.dim() == 1 and gt.numel() == total):
-        raise ValueError("gt must be a 1-D uint8 tensor packed like binary")
-    for buf, name in ((binary, "binary"), (gt, "gt")):
-        if buf is not None and not (buf.is_cuda and buf.is_contiguous()):
-            raise ValueError("{} must be a contiguous CUDA(HIP) tensor".format(name))
-    dev, n = binary.device, len(off)
-    if gt is not None and gt.device != dev:
-        raise ValueError("gt must be on the device of binary")
-    from .data import _upload_tables
-    d_off, d_hw = _upload_tables([off, size], dev)
+    dev, n = binary.device, layout.n
+    if gt is not None:
+        require_tensor(gt, "gt (packed like binary)", torch.uint8, 1, total, dev)
+    require_tensor(binary, "binary (packed samples)", torch.uint8, 1)
+    d_off, d_hw = layout.device_tables(dev)
     selected = torch.empty(total, dtype=torch.uint8, device=dev) if mode != "label" else None
     labels = torch.empty(total, dtype=torch.int32, device=dev) if want_labels else None
     info = torch.empty((n, 4), dtype=torch.int64, device=dev)
-    ws = torch.empty((int(lib.udet_components_workspace_bytes(total, n)) + 7) // 8, dtype=torch.int64, device=dev)
+    ws = workspace(lib.udet_components_workspace_bytes(total, n), 8, dev)
     check(lib.udet_select_components_ragged(binary.data_ptr(), None if gt is None else gt.data_ptr(), n, d_off.data_ptr(), d_hw.data_ptr(),
-                                            int(size[:, 0].max()), int(size[:, 1].max()), total, int(connectivity), COMPONENT_MODES[mode],
+                                            layout.max_h, layout.max_w, total, int(connectivity), COMPONENT_MODES[mode],
                                             None if labels is None else labels.data_ptr(), None if selected is None else selected.data_ptr(),
-                                            info.data_ptr(), ws.data_ptr(), ws.numel() * 8, torch.cuda.current_stream(dev).cuda_stream))
-    return ComponentSelection(selected, labels, info, off, size)
+                                            info.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return ComponentSelection(selected, labels, info, layout, None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -429,17 +377,13 @@ CRF_KEYS = ("sxy", "srgb", "compat", "gauss_k", "iters", "radius")
 
 
 def check_crf_tables(offsets, hw, numel):
-    """Host validation of the device tables of udet_dense_crf_ragged / udet_crf_unary_lookup, by check_component_tables' rules:
-    raises ValueError on a sample outside the packed buffers of `numel` elements, overlapping samples or a frame of 2^31 pixels or
-    more.  Returns (offsets int64 [n], hw int32 [n,2]) as the kernels read them."""
-    if len(np.asarray(offsets).reshape(-1)) > 65535:
-        raise ValueError("at most 65535 samples per call")
-    return check_component_tables(offsets, hw, numel)
+    """Host validation of the device tables of udet_dense_crf_ragged / udet_crf_unary_lookup: ragged.check_packed_tables for packed
+    buffers of `numel` elements and at most 65535 samples.  Returns (offsets int64 [n], hw int32 [n,2]) as the kernels read them."""
+    return check_packed_tables(offsets, hw, numel, max_samples=CRF_MAX_SAMPLES)
 
 
 def crf_params(crf):
     """The `crf` dict of restore_results_dir with its defaults filled in (iters 50, radius ceil(3 sxy)) and checked (ValueError)."""
-    from .post_processing import default_radius
     if not isinstance(crf, dict) or not {"sxy", "srgb", "compat", "gauss_k"} <= set(crf) or not set(crf) <= set(CRF_KEYS):
         raise ValueError("crf must be a dict with sxy, srgb, compat, gauss_k and optionally iters, radius")
     p = {k: float(crf[k]) for k in ("sxy", "srgb", "compat", "gauss_k")}
@@ -463,18 +407,16 @@ def load_images_device(paths):
 def crf_refine_restored(res, images, crf) -> RestoredMasks:
     """refine (crf_refine.py:110-130) of a restored batch at native size: the unary from the restored bytes
     (post_processing.unary_from_restored), the dense CRF on the frames `images` (a RaggedBatch of rgb frames in the order and of the
-    sizes of res; they stay on the device) in one call of post_processing.dense_crf_ragged.  Returns res with the CRF's labels in
-    the place of the thresholded binary masks."""
-    from .post_processing import dense_crf_ragged, unary_from_restored
+    sizes of res -- or anything with its data / offsets / hw; they stay on the device) in one call of post_processing.dense_crf_ragged,
+    both on res's own layout.  Returns res with the CRF's labels in the place of the thresholded binary masks."""
     p = crf_params(crf)
-    if not np.array_equal(np.asarray(images.hw, np.int64), np.asarray(res.hw, np.int64)):
-        raise ValueError("the frames and their annotations differ in size")
-    if not np.array_equal(np.asarray(images.offsets, np.int64), 3 * np.asarray(res.offsets, np.int64)) or images.data.numel() != 3 * res.data.numel():
-        raise ValueError("the frames must be packed like the restored masks")
-    unary = unary_from_restored(res.data, res.offsets, res.hw, res.amax, p["gauss_k"])
-    _, labels = dense_crf_ragged(unary, images.data, res.offsets, res.hw, p["sxy"], p["srgb"], p["compat"], p["iters"], p["radius"],
+    frames = images.layout if hasattr(images, "layout") else PackedLayout(images.offsets, images.hw, images.data.numel(), 3)
+    if not frames.same_as(res.layout, scale=3):
+        raise ValueError("the frames must be packed like the restored masks (their sizes, three times their offsets)")
+    unary = unary_from_restored(res.data, res.layout, None, res.amax, p["gauss_k"])
+    _, labels = dense_crf_ragged(unary, images.data, res.layout, None, p["sxy"], p["srgb"], p["compat"], p["iters"], p["radius"],
                                  want_q=False, want_labels=True)
-    return RestoredMasks(res.data, labels, res.offsets, res.hw, res.amax)
+    return RestoredMasks(res.data, labels, res.layout, None, res.amax)
 
 
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
@@ -534,7 +476,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                 if masks[-1].ndim != 2 or masks[-1].shape != masks[0].shape:
                     raise ValueError("{}: result_{}.mat: masks must be 2-D and of one shape".format(d, k))
             gt = load_gt([a for _, a in rows], rule)
-            res = restore(np.stack(masks), gt.hw, crop, threshold)
+            res = restore(np.stack(masks), getattr(gt, "layout", gt.hw), crop, threshold)  # the annotations' layout is the batch's
             pred = res  # what is scored and exported as the binary mask
             if crf is not None:
                 pred = refine(res, load_images([img for img, _ in rows]), crf)

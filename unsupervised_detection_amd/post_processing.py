@@ -7,7 +7,8 @@ meaning as post_processing/generate_soft_score_from_buffer.py and post_processin
   refine(...) / select_candidate(...)                             crf_refine.py:110-138, :40-50
   buffer_to_soft_score(buffer_path, out_path, ...) / run_crf(...)  the file-level drivers over the .mat buffers the ensemble run writes
   dense_crf_ragged(...) / unary_from_restored(...) / run_crf_original_resolution(...)   crf_refine.py:65-108: the CRF on every frame at
-                    its own size, a ragged batch per call (csrc/crf.hip)
+                    its own size, a ragged batch per call (csrc/crf.hip) in the packed layout of ragged.py:
+                    both take host offsets / hw, or the batch's PackedLayout and then neither validate nor upload
   propagate_sequences(...) / PWCFlow.batch(...) / select_unary_batch(...)   the sequence stage batched (csrc/sequence.hip):
                     propagate(flow_batch=), buffer_to_soft_score(flow_batch=) and run_crf(batch=) reach them; the defaults (None) keep the
                     per-frame paths
@@ -20,14 +21,14 @@ published algorithms -- see oracle/oracle_post.py for the restatement the kernel
 not be pinned to the original libraries."""
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 
 import numpy as np
 import torch
 
-from ._ffi import c_f, c_i, c_p, c_sz, check, lib
+from ._ffi import c_f, c_i, c_p, c_sz, check, lib, sig
+from .ragged import PackedLayout, as_layout, check_ranges, require_tensor, upload_tables, workspace
 
 for _n, _a in (("udet_post_border_mean", [c_p, c_i, c_i, c_i, c_p, c_p]),
                ("udet_post_bytescale", [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
@@ -37,27 +38,18 @@ for _n, _a in (("udet_post_border_mean", [c_p, c_i, c_i, c_i, c_p, c_p]),
                ("udet_post_remap", [c_p, c_p, c_p, c_i, c_i, c_p]),
                ("udet_post_blend", [c_p, c_f, c_p, c_f, c_i, c_i, c_p]),
                ("udet_post_gauss1d", [c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p]),
-               ("udet_post_dense_crf", [c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_sz, c_p])):
-    getattr(lib, _n).restype = c_i
-    getattr(lib, _n).argtypes = _a
-lib.udet_post_crf_workspace_bytes.restype = c_sz
-lib.udet_post_crf_workspace_bytes.argtypes = [c_i, c_i]
-# the dense CRF of a ragged batch at native resolution (csrc/crf.hip)
-lib.udet_dense_crf_workspace_bytes.restype = c_sz
-lib.udet_dense_crf_workspace_bytes.argtypes = [c_sz, c_i]
-lib.udet_dense_crf_ragged.restype = c_i
-lib.udet_dense_crf_ragged.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]
-lib.udet_dense_crf_rows_per_thread.restype = c_i
-lib.udet_dense_crf_rows_per_thread.argtypes = [c_i, c_i, c_i]
-lib.udet_crf_unary_lookup.restype = c_i
-lib.udet_crf_unary_lookup.argtypes = [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p]
-# the sequence stage, batched (csrc/sequence.hip)
-lib.udet_post_propagate_workspace_bytes.restype = c_sz
-lib.udet_post_propagate_workspace_bytes.argtypes = [c_i, c_i]
-lib.udet_post_propagate_sequences.restype = c_i
-lib.udet_post_propagate_sequences.argtypes = [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]
-lib.udet_post_select_unary.restype = c_i
-lib.udet_post_select_unary.argtypes = [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]
+               ("udet_post_dense_crf", [c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_sz, c_p]),
+               # the dense CRF of a ragged batch at native resolution (csrc/crf.hip)
+               ("udet_dense_crf_ragged", [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_f, c_f, c_f, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
+               ("udet_dense_crf_rows_per_thread", [c_i, c_i, c_i]),
+               ("udet_crf_unary_lookup", [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p]),
+               # the sequence stage, batched (csrc/sequence.hip)
+               ("udet_post_propagate_sequences", [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
+               ("udet_post_select_unary", [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p])):
+    sig(_n, c_i, *_a)
+sig("udet_post_crf_workspace_bytes", c_sz, c_i, c_i)
+sig("udet_dense_crf_workspace_bytes", c_sz, c_sz, c_i)
+sig("udet_post_propagate_workspace_bytes", c_sz, c_i, c_i)
 
 
 def _stream():
@@ -67,6 +59,11 @@ def _stream():
 def _dev(x, dtype):
     t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
     return t.to("cuda", dtype).contiguous()
+
+
+def _as_mask(m):
+    """A soft mask as the stage takes it: its singleton dimensions dropped, device float32."""
+    return _dev(m.squeeze() if isinstance(m, torch.Tensor) else np.squeeze(m), torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------- Pillow coefficients ----
@@ -164,8 +161,7 @@ def soft_score(preds_b, preds_f, crops=(85, 90, 95, 100), base_crop=90.0, base_h
     tensors or arrays) of the backward (-shift) / forward (+shift) ensemble runs -> pred_mask, device float64 [H,W]."""
     H, W = base_hw
     ns, nc = len(preds_b), len(crops)
-    allm = torch.stack([_dev(np.squeeze(m) if not isinstance(m, torch.Tensor) else m.squeeze(), torch.float32)
-                        for grp in (preds_b, preds_f) for row in grp for m in row], 0)
+    allm = torch.stack([_as_mask(m) for grp in (preds_b, preds_f) for row in grp for m in row], 0)
     sani = sanity_check(allm).reshape(2, ns, nc)  # one launch for every mask of the frame
     score = None
     for si in range(ns):
@@ -267,11 +263,7 @@ def check_sequence_tables(seq_first, seq_len, total):
         raise ValueError("total frames must be in 1..2^31-1")
     if (length < 1).any():
         raise ValueError("a sequence has a length below 1")
-    if (first < 0).any() or (first + length > int(total)).any():
-        raise ValueError("a sequence lies outside the {} frames".format(int(total)))
-    order = np.argsort(first, kind="stable")
-    if (first[order][1:] < (first + length)[order][:-1]).any():
-        raise ValueError("sequences overlap")
+    check_ranges(first, length, int(total), "sequence", "array of {} frames".format(int(total)))
     return first.astype(np.int32), length.astype(np.int32)
 
 
@@ -281,8 +273,7 @@ def propagate_sequences(masks, flow_prev, flow_next, seq_lens, w_r=0.85):
     flow_prev / flow_next: device float32 [total,H,W,2], (u, v) from frame k to k - 1 / k + 1 (the entry of a sequence's first / last frame
     is not read).  Returns (avg_f, avg_b), device float32 [total,H,W]: bit-identical to propagate()'s lists with the same flows."""
     for t, nd, name in ((masks, 3, "masks"), (flow_prev, 4, "flow_prev"), (flow_next, 4, "flow_next")):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == nd and t.is_contiguous()):
-            raise ValueError("{} must be a contiguous float32 CUDA(HIP) tensor of {} dimensions".format(name, nd))
+        require_tensor(t, name, torch.float32, nd)
     total, H, W = (int(v) for v in masks.shape)
     if tuple(flow_prev.shape) != (total, H, W, 2) or tuple(flow_next.shape) != (total, H, W, 2):
         raise ValueError("flow_prev and flow_next must be [total,H,W,2] like masks [total,H,W]")
@@ -290,13 +281,12 @@ def propagate_sequences(masks, flow_prev, flow_next, seq_lens, w_r=0.85):
     if lens.sum() != total:
         raise ValueError("seq_lens must sum to the {} frames of masks".format(total))
     first, length = check_sequence_tables(np.concatenate([[0], np.cumsum(lens)[:-1]]), lens, total)  # before the device is touched
-    from .data import _upload_tables
-    d_first, d_len = _upload_tables([first, length], masks.device)
+    d_first, d_len = upload_tables([first, length], masks.device)
     avg_f, avg_b = torch.empty_like(masks), torch.empty_like(masks)
-    ws = torch.empty((int(lib.udet_post_propagate_workspace_bytes(total, len(first))) + 15) // 16 * 4, dtype=torch.float32, device=masks.device)
+    ws = workspace(lib.udet_post_propagate_workspace_bytes(total, len(first)), 16, masks.device)
     check(lib.udet_post_propagate_sequences(masks.data_ptr(), flow_prev.data_ptr(), flow_next.data_ptr(), len(first), d_first.data_ptr(),
                                             d_len.data_ptr(), total, H, W, float(np.float32(1 - w_r)), float(np.float32(w_r)),
-                                            avg_f.data_ptr(), avg_b.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                                            avg_f.data_ptr(), avg_b.data_ptr(), ws.data_ptr(), ws.numel(),
                                             torch.cuda.current_stream(masks.device).cuda_stream))
     return avg_f, avg_b
 
@@ -307,7 +297,7 @@ def _propagate_batched(seq_masks, seq_images, flow_fn, w_r, flow_batch):
     sequence."""
     if not hasattr(flow_fn, "batch"):
         raise ValueError("flow_batch needs a flow_fn with a batch(imgs_from, imgs_to, batch) method (PWCFlow)")
-    masks = [_dev(np.squeeze(m) if not isinstance(m, torch.Tensor) else m.squeeze(), torch.float32) for ms in seq_masks for m in ms]
+    masks = [_as_mask(m) for ms in seq_masks for m in ms]
     lens = [len(ms) for ms in seq_masks]
     if any(len(ms) != len(im) or not len(ms) for ms, im in zip(seq_masks, seq_images)):
         raise ValueError("one frame per mask, and at least one mask per sequence")
@@ -342,7 +332,7 @@ def propagate(pred_masks, images_u8, flow_fn, w_r=0.85, flow_batch=None):
     if flow_batch is not None:
         return _propagate_batched([pred_masks], [images_u8], flow_fn, w_r, flow_batch)[0]
     n = len(pred_masks)
-    masks = [_dev(np.squeeze(m) if not isinstance(m, torch.Tensor) else m.squeeze(), torch.float32) for m in pred_masks]
+    masks = [_as_mask(m) for m in pred_masks]
     fwd, bwd = [None] * n, [None] * n
     ra = masks[0]
     fwd[0] = ra
@@ -381,10 +371,9 @@ def select_unary_batch(pred, avg_f, avg_b, gt, gauss_k=0.1):
     Gaussian (int(4 gauss_k + 0.5) == 0, the reference's 0.1): ValueError otherwise -- run_crf then keeps the per-frame path."""
     if int(4.0 * float(gauss_k) + 0.5) != 0:
         raise ValueError("select_unary_batch covers gauss_k with int(4 gauss_k + 0.5) == 0 only")
-    for t in (pred, avg_f, avg_b, gt):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3 and t.is_contiguous() and
-                t.shape == pred.shape):
-            raise ValueError("pred, avg_f, avg_b and gt must be contiguous float32 CUDA(HIP) tensors of one shape [n,H,W]")
+    for t, name in ((pred, "pred"), (avg_f, "avg_f"), (avg_b, "avg_b"), (gt, "gt")):
+        if require_tensor(t, name + " [n,H,W]", torch.float32, 3).shape != pred.shape:
+            raise ValueError("pred, avg_f, avg_b and gt must be of one shape [n,H,W]")
     n, H, W = (int(v) for v in pred.shape)
     dev = pred.device
     choice = torch.empty(n, dtype=torch.int32, device=dev)
@@ -419,7 +408,7 @@ def dense_crf(unary, image_u8, sxy, srgb, compat, iters=50, radius=None):
     _, H, W = un.shape
     R = int(math.ceil(3.0 * sxy)) if radius is None else int(radius)
     q = torch.empty_like(un)
-    ws = torch.empty(int(lib.udet_post_crf_workspace_bytes(H, W)), dtype=torch.uint8, device=un.device)
+    ws = workspace(lib.udet_post_crf_workspace_bytes(H, W), 16, un.device)
     check(lib.udet_post_dense_crf(un.data_ptr(), img.data_ptr(), H, W, sxy, srgb, compat, iters, R, q.data_ptr(), ws.data_ptr(), ws.numel(),
                                   _stream()))
     return q
@@ -456,71 +445,64 @@ def unary_table(amax):
     return np.ascontiguousarray(np.float32(-np.log(np.stack([1.0 - U, U], 1))))
 
 
-def _crf_tables(offsets, hw, total, device):
-    from .data import _upload_tables
-    from .native_results import check_crf_tables
-    off, size = check_crf_tables(offsets, hw, total)  # before the device is touched
-    d_off, d_hw = _upload_tables([off, size], device)
-    return off, size, d_off, d_hw
+CRF_MAX_SAMPLES = 65535  # a grid dimension of udet_dense_crf_ragged / udet_crf_unary_lookup
 
 
 def unary_from_restored(data, offsets, hw, amax, gauss_k=0.1):
-    """The unary energies of refine (crf_refine.py:113-121) for the packed restored bytes `data` (1-D uint8 device tensor, sample i
-    = hw[i] bytes at offsets[i]; amax [n]: each sample's largest byte, device or host) -> device float32 [2,total], packed the same
-    way (elements between samples are 0).  A Gaussian of radius 0 (int(4 gauss_k + 0.5) == 0, the reference's 0.1): a 256-entry table
+    """The unary energies of refine (crf_refine.py:113-121) for the packed restored bytes `data` (1-D uint8 device tensor in the layout
+    offsets / hw -- host arrays, or a PackedLayout with hw=None; amax [n]: each sample's largest byte, device or host) -> device
+    float32 [2,total], packed the same way (elements between samples are 0).
+    A Gaussian of radius 0 (int(4 gauss_k + 0.5) == 0, the reference's 0.1): a 256-entry table
     per sample (unary_table) and one lookup launch for the batch, bit-equal to oracle_post.unary_from_mask of the float64 soft mask.
     A wider Gaussian goes through gaussian_filter per sample (slow, correct, not what the reference uses)."""
-    if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
-        raise ValueError("data must be a contiguous 1-D uint8 CUDA(HIP) tensor of packed samples")
+    require_tensor(data, "data (packed samples)", torch.uint8, 1)
     total, dev = int(data.numel()), data.device
-    off, size, d_off, d_hw = _crf_tables(offsets, hw, total, dev)
+    layout = as_layout(offsets, hw, total, max_samples=CRF_MAX_SAMPLES)  # raw tables: validated before the device is touched
     am = (amax.cpu().numpy() if isinstance(amax, torch.Tensor) else np.asarray(amax)).reshape(-1).astype(np.int64)
-    if len(am) != len(off) or (am < 0).any() or (am > 255).any():
+    if len(am) != layout.n or (am < 0).any() or (am > 255).any():
         raise ValueError("one amax in 0..255 per sample")
     unary = torch.zeros((2, total), dtype=torch.float32, device=dev)
     if int(4.0 * float(gauss_k) + 0.5) == 0:
         table = torch.from_numpy(unary_table(am)).to(dev)
-        check(lib.udet_crf_unary_lookup(data.data_ptr(), table.data_ptr(), len(off), d_off.data_ptr(), d_hw.data_ptr(), int(size[:, 0].max()),
-                                        int(size[:, 1].max()), total, unary.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        d_off, d_hw = layout.device_tables(dev)
+        check(lib.udet_crf_unary_lookup(data.data_ptr(), table.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.max_h,
+                                        layout.max_w, total, unary.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
         return unary
-    for i, (o, (H, W)) in enumerate(zip(off, size)):
-        o, H, W = int(o), int(H), int(W)
-        soft = data[o:o + H * W].view(H, W).double() / (float(am[i]) + 1e-8)
-        U = gaussian_filter(soft, gauss_k)
+    for i in range(layout.n):
+        U = gaussian_filter(layout.view(data, i).double() / (float(am[i]) + 1e-8), gauss_k)
         U = torch.clamp(U / (U.max() + 1e-8), 1e-6, 1.0 - 1e-6)
-        unary[:, o:o + H * W] = (-torch.log(torch.stack([1.0 - U, U], 0))).float().view(2, -1)
+        o = int(layout.offsets[i])
+        unary[:, o:o + U.numel()] = (-torch.log(torch.stack([1.0 - U, U], 0))).float().view(2, -1)
     return unary
 
 
 def dense_crf_ragged(unary, images, offsets, hw, sxy, srgb, compat, iters=50, radius=None, want_q=True, want_labels=True, q_out=None,
                      labels_out=None):
     """The dense CRF of dense_crf on n frames of their own sizes in one call of udet_dense_crf_ragged (iters + 2 launches whatever
-    n is).  unary: device float32 [2,total] (the energies of label 0 / 1), images: device uint8 [3 * total] (rgb), both packed:
-    sample i = hw[i] = (H_i, W_i) elements at element offset offsets[i] (host arrays [n] / [n,2]).  radius None: ceil(3 sxy).
+    n is).  unary: device float32 [2,total] (the energies of label 0 / 1), images: device uint8 [3 * total] (rgb), both in the layout
+    offsets / hw of `total` elements (host arrays [n] / [n,2], or a PackedLayout with hw=None).  radius None: ceil(3 sxy).
     Returns (q1, labels): the marginal of label 1 (device float32 [total]) and the label (device uint8 [total], 1 where Q1 > Q0), each
     None when not wanted; elements between the samples are not written (q_out / labels_out: caller-owned buffers of `total`
-    elements, else fresh zeroed ones).  The tables are validated on the host before anything is launched (ValueError)."""
-    if not (isinstance(unary, torch.Tensor) and unary.is_cuda and unary.dtype == torch.float32 and unary.dim() == 2 and
-            unary.shape[0] == 2 and unary.is_contiguous()):
-        raise ValueError("unary must be a contiguous float32 CUDA(HIP) tensor [2,total]")
+    elements, else fresh zeroed ones).  Raw tables are validated on the host before anything is launched (ValueError)."""
+    if require_tensor(unary, "unary [2,total]", torch.float32, 2).shape[0] != 2:
+        raise ValueError("unary must be [2,total]")
     total, dev = int(unary.shape[1]), unary.device
-    if not (isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.is_contiguous() and images.numel() == 3 * total and
-            images.device == dev):
-        raise ValueError("images must be a contiguous uint8 tensor of 3 * total bytes on the device of unary")
+    require_tensor(images, "images (rgb, packed like unary)", torch.uint8, None, 3 * total, dev)
     if not (want_q or want_labels):
         raise ValueError("at least one of want_q and want_labels")
     for buf, dt, name in ((q_out, torch.float32, "q_out"), (labels_out, torch.uint8, "labels_out")):
-        if buf is not None and not (buf.dtype == dt and buf.dim() == 1 and buf.numel() == total and buf.is_contiguous() and buf.device == dev):
-            raise ValueError("{} must be a contiguous 1-D tensor of total elements on the device of unary".format(name))
-    off, size, d_off, d_hw = _crf_tables(offsets, hw, total, dev)
+        if buf is not None:
+            require_tensor(buf, name, dt, 1, total, dev)
+    layout = as_layout(offsets, hw, total, max_samples=CRF_MAX_SAMPLES)
+    d_off, d_hw = layout.device_tables(dev)
     R = default_radius(sxy) if radius is None else int(radius)
     q1 = (torch.zeros(total, dtype=torch.float32, device=dev) if q_out is None else q_out) if want_q else None
     labels = (torch.zeros(total, dtype=torch.uint8, device=dev) if labels_out is None else labels_out) if want_labels else None
-    ws = torch.empty((int(lib.udet_dense_crf_workspace_bytes(total, len(off))) + 15) // 16 * 4, dtype=torch.float32, device=dev)
-    check(lib.udet_dense_crf_ragged(unary.data_ptr(), images.data_ptr(), len(off), d_off.data_ptr(), d_hw.data_ptr(), int(size[:, 0].max()),
-                                    int(size[:, 1].max()), total, float(sxy), float(srgb), float(compat), int(iters), R,
+    ws = workspace(lib.udet_dense_crf_workspace_bytes(total, layout.n), 16, dev)
+    check(lib.udet_dense_crf_ragged(unary.data_ptr(), images.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.max_h,
+                                    layout.max_w, total, float(sxy), float(srgb), float(compat), int(iters), R,
                                     None if q1 is None else q1.data_ptr(), None if labels is None else labels.data_ptr(), ws.data_ptr(),
-                                    ws.numel() * 4, torch.cuda.current_stream(dev).cuda_stream))
+                                    ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
     return q1, labels
 
 
@@ -538,6 +520,15 @@ def run_crf_original_resolution(path_soft, frame_lists, sxy, srgb, scomp, gauss_
 
 
 # ----------------------------------------------------------------------------------------------------- file drivers ----
+def _save_soft(out_dir, masks, imgs, gts, fwd, bwd):
+    """result_<k>.mat of one sequence as buffer_to_soft_score writes them."""
+    import scipy.io as sio
+    for k in range(len(masks)):
+        sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
+                    {"pred_mask": masks[k].cpu().numpy(), "img1": imgs[k], "gt_mask": gts[k],
+                     "running_avg_f": fwd[k].cpu().numpy(), "running_avg_b": bwd[k].cpu().numpy()})
+
+
 def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2, base_crop=90.0, dprefix="davis_shift", flow_fn=None,
                          flow_batch=None):
     """generate_soft_score_from_buffer.buffer_to_soft_score over the result_<k>.mat buffers test_generator_ensemble writes
@@ -567,18 +558,11 @@ def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2,
         if flow_batch is not None:
             held.append((out_dir, masks, imgs, gts))
             continue
-        fwd, bwd = propagate(masks, imgs, flow_fn or PWCFlow())
-        for k in range(num):
-            sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
-                        {"pred_mask": masks[k].cpu().numpy(), "img1": imgs[k], "gt_mask": gts[k],
-                         "running_avg_f": fwd[k].cpu().numpy(), "running_avg_b": bwd[k].cpu().numpy()})
+        _save_soft(out_dir, masks, imgs, gts, *propagate(masks, imgs, flow_fn or PWCFlow()))
     if held:
         avgs = _propagate_batched([h[1] for h in held], [h[2] for h in held], flow_fn or PWCFlow(), 0.85, flow_batch)
         for (out_dir, masks, imgs, gts), (fwd, bwd) in zip(held, avgs):
-            for k in range(len(masks)):
-                sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
-                            {"pred_mask": masks[k].cpu().numpy(), "img1": imgs[k], "gt_mask": gts[k],
-                             "running_avg_f": fwd[k].cpu().numpy(), "running_avg_b": bwd[k].cpu().numpy()})
+            _save_soft(out_dir, masks, imgs, gts, fwd, bwd)
 
 
 def _run_crf_group(frames, sxy, srgb, scomp, gauss_k, iters, radius):
@@ -597,8 +581,7 @@ def _run_crf_group(frames, sxy, srgb, scomp, gauss_k, iters, radius):
     d = torch.from_numpy(buf).cuda()
     dfl = d[:16 * n * hw].view(torch.float32).view(4, n, H, W)
     choice, _, soft, unary = select_unary_batch(dfl[0], dfl[1], dfl[2], dfl[3], gauss_k)
-    _, labels = dense_crf_ragged(unary, d[16 * n * hw:], np.arange(n, dtype=np.int64) * hw, np.full((n, 2), (H, W), np.int64), sxy, srgb, scomp,
-                                 iters, radius, want_q=False)
+    _, labels = dense_crf_ragged(unary, d[16 * n * hw:], PackedLayout.packed([(H, W)] * n), None, sxy, srgb, scomp, iters, radius, want_q=False)
     gt, bm = dfl[3].reshape(n, hw) > 0.1, labels.view(n, hw) > 0
     counts = torch.stack([(gt & bm).sum(1), (gt | bm).sum(1)], 0)  # int64 [2,n]: exact
     back = torch.cat([soft.reshape(-1).view(torch.uint8), counts.reshape(-1).view(torch.uint8), labels]).cpu().numpy()
@@ -629,22 +612,20 @@ def run_crf(path_soft, sxy, srgb, scomp, gauss_k, out_path="./post_processed_dav
         out_dir = os.path.join(out_path, seq)
         os.makedirs(out_dir, exist_ok=True)
         print(out_dir)
-        if batch is not None:
-            for k0 in range(0, seq_len, int(batch)):
-                ks = range(k0, min(seq_len, k0 + int(batch)))
-                frames = [load(seq_path, k) for k in ks]
+        group = 1 if batch is None else int(batch)
+        for k0 in range(0, seq_len, group):
+            ks = range(k0, min(seq_len, k0 + group))
+            frames = [load(seq_path, k) for k in ks]
+            if batch is None:
+                pm, pf, pb, gt, img = frames[0]
+                mask, _ = select_candidate(pm, pf, pb, gt)
+                new_mask, iou = refine(mask, img, gauss_k, sxy, srgb, scomp, gt, crf_iters, crf_radius)
+                soft, masks, ious = [mask], [new_mask], [iou]
+            else:
                 soft, labels, inter, union = _run_crf_group(frames, sxy, srgb, scomp, gauss_k, crf_iters, crf_radius)
-                for i, k in enumerate(ks):
-                    total += 1.0
-                    sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)),
-                                {"gt_mask": frames[i][3], "soft_mask": soft[i], "mask": labels[i].astype(np.float32)})
-                    sum_iou += np.float32(inter[i]) / np.float32(union[i])
-            continue
-        for k in range(seq_len):
-            pm, pf, pb, gt, img = load(seq_path, k)
-            total += 1.0
-            mask, _ = select_candidate(pm, pf, pb, gt)
-            new_mask, iou = refine(mask, img, gauss_k, sxy, srgb, scomp, gt, crf_iters, crf_radius)
-            sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)), {"gt_mask": gt, "soft_mask": mask, "mask": new_mask})
-            sum_iou += iou
+                masks, ious = labels.astype(np.float32), [np.float32(a) / np.float32(b) for a, b in zip(inter, union)]
+            for i, k in enumerate(ks):
+                total += 1.0
+                sio.savemat(os.path.join(out_dir, "result_%d.mat" % (k + 1)), {"gt_mask": frames[i][3], "soft_mask": soft[i], "mask": masks[i]})
+                sum_iou += ious[i]
     return sum_iou / total
