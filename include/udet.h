@@ -269,6 +269,41 @@ int udet_post_propagate_sequences(const float* masks, const float* flow_prev, co
 int udet_post_select_unary(const float* pred, const float* avg_f, const float* avg_b, const float* gt, int n, int hw, int* choice,
                            double* scores, float* soft, float* unary, void* stream);
 
+/* The soft scores of the ensemble for a batch of frames (csrc/soft_score.hip): the per-frame body of
+ * generate_soft_score_from_buffer.py buffer_to_soft_score :38-93 -- what udet_post_border_mean, udet_post_bytescale, udet_post_resample_u8,
+ * udet_post_place and udet_post_minmax_norm compute in about a hundred launches and a host round trip per frame -- for n frames in four
+ * launches, without a host synchronisation or a copy to the host, bit for bit.
+ *   masks      device float32 [n][2][ns][nc][h][w]: direction 0 the backward run (-shift), 1 the forward run; shift index, crop index
+ *   pred_mask  device float64 [n][h][w] (8-byte aligned)
+ *   san_t      the sanity threshold as a double: the reference compares a float64 mean with the Python float 0.6
+ *   geom       device int32 [ns * nc][UDET_SOFT_SCORE_GEOM], row shift index * nc + crop index =
+ *                {mode, sy0, sx0, sh, sw, hh, ww, y0, x0, hk, hb, hks, vk, vb, vks, 0}
+ *              mode 0, identity (shift 1 at the base crop): the term is the raw s_b + s_f and the rest of the row is not read; mode 1,
+ *              rectify: the window [sy0, sy0 + sh) x [sx0, sx0 + sw) of the mask is bytescaled with the window's own min / max (cscale == 0
+ *              -> 1) and resampled to the hh x ww patch that lands at (y0, x0) of the h x w canvas, zeros around it (rectify_pred_mask
+ *              :98-114); hk / hb / hks: the int32 offsets into coef of the horizontal pass's (sw -> ww) Pillow coefficients kk [ww][hks] and
+ *              bounds [ww][2] = (first tap, taps) and their row length, as udet_restore_masks_ragged takes them; vk / vb / vks: the vertical
+ *              pass (sh -> hh); hk / vk < 0: the pass is skipped (out == in)
+ *   coef       device int32: the concatenated coefficient blocks
+ * Launch 1, per mask: the border mean (udet_post_border_mean's loop and tree: the same double) and the min / max of the source window as
+ * partial pairs.  Launch 2: every raw mask of a rectify row is bytescaled and resampled on 64 x 16 tiles of its patch (horizontal pass into a
+ * uint8 LDS strip, vertical pass out of it) into the workspace, the patch's largest byte by an integer atomicMax.  Launch 3, one thread per
+ * pixel: per (frame, shift, crop) both means >= san_t: both slots are zeros; only the backward run's: its slot takes the forward run's patch
+ * and maximum; only the forward run's: the reverse; term = vb / (maxb + 1e-6) + vf / (maxf + 1e-6) in double with zeros outside the patch
+ * (identity: (double)s_b + (double)s_f); score = term_0, then score += term_k shift-major, crop-minor -- the order of the reference's loops;
+ * the score and a (min, max) pair per workgroup.  Launch 4: (score - min) / (max - min + 1e-6).  No workgroup waits for another, no
+ * floating-point atomics: bit-identical from run to run and between a frame alone and inside a batch.
+ * workspace: udet_post_soft_score_workspace_bytes(n, ns, nc, h, w) bytes, 16-byte aligned: the uint8 patches (n * 2 * ns * nc * h * w
+ * bytes) and per-mask / per-workgroup scalars; linear in n; 0 for an argument below 1.
+ * UDET_ERR_ARG, nothing enqueued: n, ns, nc below 1, h or w below 4, h * w >= 2^31, n * 2 * ns * nc above 65535 (a grid dimension), a NULL
+ * pointer, pred_mask not 8-byte aligned, a non-finite san_t, a short or misaligned workspace.  The tables are device memory and are not read
+ * here: windows and patches inside the frame, coefficient blocks inside coef and taps inside their window must hold
+ * (post_processing.check_soft_score_tables validates them on the host before anything is launched). */
+#define UDET_SOFT_SCORE_GEOM 16
+size_t udet_post_soft_score_workspace_bytes(int n, int ns, int nc, int h, int w);
+int udet_post_soft_score_batch(const float* masks, int n, int ns, int nc, int h, int w, const int* geom, const int* coef, double san_t,
+                               double* pred_mask, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Visualisation and training summaries (models/utils/flow_utils.py:14-100, models/adversarial_learner.py:260-298,
  * test_generator.py:93-117): the images and gradient histograms of a run, from buffers that already sit on the device.
  *  - udet_flow_to_image: flow_to_image + compute_color (flow_utils.py:46-100) with the arithmetic the reference has on a float32

@@ -9,8 +9,13 @@ val's shape -- 192 x 384 frames, 20 sequences of the lengths generate_soft_score
   crf           the device part of run_crf on --crf_frames frames: select_candidate + refine per frame (three host round trips, then
                 udet_post_dense_crf) against post_processing._run_crf_group (one upload, udet_post_select_unary, udet_dense_crf_ragged,
                 one copy back); host clock around calls that end in a device-to-host copy.
+  soft_score    synthetic ensemble masks of DAVIS's shape (2 shifts x 4 crops x 2 directions per frame) on the device, --score_frames frames:
+                post_processing.soft_score per frame (about a hundred launches and a host wait each) against post_processing.soft_score_batch
+                on --score_batch frames per call (udet_post_soft_score_batch: four launches); host clock, both sides ending in a device
+                synchronise, because the per-frame path waits on the host.  The two must agree byte for byte.
 
-    python tools/sequence_bench.py [--rounds 3] [--flow_batch 8] [--flow_pairs 64] [--crf_batch 16] [--crf_frames 16] [--skip crf,flows]
+    python tools/sequence_bench.py [--rounds 3] [--flow_batch 8] [--flow_pairs 64] [--crf_batch 16] [--crf_frames 16]
+                                   [--score_frames 64] [--score_batch 16] [--skip crf,flows,soft_score]
 
 The paths alternate over --rounds rounds after a warm-up.  One JSON line: milliseconds per path (median, min .. max) and the ratios."""
 import argparse
@@ -139,6 +144,39 @@ def bench_crf(PP, frames_n, batch, rounds, sxy, srgb, compat, iters):
             "ratio_per_frame_over_batched": float(np.median(to) / np.median(tn))}
 
 
+def bench_soft_score(PP, frames_n, batch, rounds):
+    ns, crops = 2, (85, 90, 95, 100)
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    yy, xx = torch.meshgrid(torch.arange(H, device="cuda"), torch.arange(W, device="cuda"), indexing="ij")
+    c = torch.rand((frames_n * 2 * ns * len(crops), 2), generator=gen, device="cuda") * 0.2 + 0.4
+    m = torch.exp(-(((yy[None] - c[:, :1, None] * H) / (0.2 * H)) ** 2 + ((xx[None] - c[:, 1:, None] * W) / (0.15 * W)) ** 2))
+    m = m + 0.05 * torch.rand(m.shape, generator=gen, device="cuda")
+    preds = (m / m.amax((1, 2), keepdim=True)).float().view(frames_n, 2, ns, len(crops), H, W).contiguous()
+    preds[1::7, 0, 0, 2] = 1.0  # a mask that fails the sanity rule now and then: its slot takes the partner
+    preds[3::11, :, 1, 1] = 1.0  # ... and a pair that fails together
+    per_frame_args = [([list(r) for r in preds[i, 0]], [list(r) for r in preds[i, 1]]) for i in range(frames_n)]
+
+    def old():
+        return [PP.soft_score(pb, pf, crops, 90.0, (H, W)) for pb, pf in per_frame_args]
+
+    def new():
+        return [PP.soft_score_batch(preds[k:k + batch], crops, 90.0) for k in range(0, frames_n, batch)]
+    o, n = old(), new()
+    torch.cuda.synchronize()
+    assert torch.equal(torch.stack(o), torch.cat(n))  # byte for byte
+    del o, n
+    to, tn = [], []
+    for _ in range(rounds):
+        tn.append(host_ms(new)[0] / frames_n)
+        to.append(host_ms(old)[0] / frames_n)
+    davis = sum(DAVIS_VAL_LENGTHS)
+    return {"frames": frames_n, "score_batch": batch, "ensemble": [2, ns, len(crops)], "per_frame": stat(to), "batched_per_frame": stat(tn),
+            "identical": True, "batched_median_below_per_frame_min": bool(np.median(tn) < min(to)),
+            "ratio_per_frame_over_batched": float(np.median(to) / np.median(tn)),
+            "davis_val_frames": davis, "davis_val_per_frame_s": float(np.median(to) * davis / 1e3),
+            "davis_val_batched_s": float(np.median(tn) * davis / 1e3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -146,12 +184,14 @@ def main():
     ap.add_argument("--flow_pairs", type=int, default=64)
     ap.add_argument("--crf_batch", type=int, default=16)
     ap.add_argument("--crf_frames", type=int, default=16)
+    ap.add_argument("--score_frames", type=int, default=64)
+    ap.add_argument("--score_batch", type=int, default=16)
     ap.add_argument("--sxy", type=float, default=25.0)
     ap.add_argument("--srgb", type=float, default=5.0)
     ap.add_argument("--compat", type=float, default=5.0)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--sequences", type=int, default=len(DAVIS_VAL_LENGTHS), help="the first so many of DAVIS val's 20 lengths")
-    ap.add_argument("--skip", default="", help="comma-separated: propagation, flows, crf")
+    ap.add_argument("--skip", default="", help="comma-separated: propagation, flows, crf, soft_score")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from unsupervised_detection_amd import post_processing as PP
@@ -163,6 +203,8 @@ def main():
         res["flows"] = bench_flows(PP, a.flow_pairs, a.flow_batch, a.rounds)
     if "crf" not in skip:
         res["crf"] = bench_crf(PP, a.crf_frames, a.crf_batch, a.rounds, a.sxy, a.srgb, a.compat, a.iters)
+    if "soft_score" not in skip:
+        res["soft_score"] = bench_soft_score(PP, a.score_frames, a.score_batch, a.rounds)
     print(json.dumps(res))
 
 

@@ -13,6 +13,7 @@
                                                       [--crf_radius R]                                      (crf_refine.py:65-108)
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
                                                       [--sxy 25] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_batch 16] [--flow_batch 8]
+                                                      [--score_batch 0]
                                                       [--benchmark --dataset ... --root_dir ... [--native_sxy 60] [--component best_gt]]
                                                                                                             (post_processing.py)
 
@@ -36,7 +37,8 @@ reference's hard-coded DAVIS lists): buffer_to_soft_score into O/soft (all flows
 propagated in one call), run_crf into O/crf_resized (--crf_batch frames per dense-CRF call) and, with --benchmark,
 run_crf_original_resolution into O/crf_original (the CRF at --native_sxy on the untouched frames of --dataset under --root_dir, one
 --component per mask); O/post_process.json holds the parameters, the training-size IoU and the benchmark table.  --crf_batch 0 /
---flow_batch 0 select the per-frame paths.
+--flow_batch 0 select the per-frame paths.  --score_batch N (default 0: a soft_score call per frame) computes the soft scores of N frames of a
+sequence per call (post_processing.soft_score_batch).
 
 The TF-specific lines of the originals (tf.train.Saver / Supervisor, `train.py:19`, `test_generator.py:45-55`) have no
 counterpart; checkpoints are torch.save'd {tf_name: tensor} dicts.  --dataset picks the reader:
@@ -178,6 +180,7 @@ def parse_post_process_args(argv):
     ap.add_argument("--gauss_k", type=float, default=0.1)
     ap.add_argument("--crf_batch", type=int, default=16, help="frames per dense-CRF call; 0: a frame at a time")
     ap.add_argument("--flow_batch", type=int, default=8, help="frame pairs per flow-network call; 0: a pair at a time, a step at a time")
+    ap.add_argument("--score_batch", type=int, default=0, help="frames per soft-score call; 0: a frame at a time")
     ap.add_argument("--benchmark", action="store_true", help="also refine and score at every frame's own size")
     ap.add_argument("--native_sxy", type=float, default=60.0)
     ap.add_argument("--dataset", default="DAVIS2016", choices=("DAVIS2016", "FBMS", "SEGTRACK"))
@@ -188,8 +191,8 @@ def parse_post_process_args(argv):
     a = ap.parse_args(argv)
     if a.benchmark and not a.root_dir:
         ap.error("--benchmark needs --root_dir (and --dataset)")
-    if a.max_shift < 1 or a.crf_batch < 0 or a.flow_batch < 0:
-        ap.error("--max_shift >= 1, --crf_batch >= 0 and --flow_batch >= 0")
+    if a.max_shift < 1 or a.crf_batch < 0 or a.flow_batch < 0 or a.score_batch < 0:
+        ap.error("--max_shift >= 1, --crf_batch >= 0, --flow_batch >= 0 and --score_batch >= 0")
     flags = default_flags()
     for k, v in vars(a).items():
         setattr(flags, k, v)
@@ -226,10 +229,12 @@ def post_process(a):
     from . import post_processing as pp
     names, lengths = discover_sequences(a.buffer_dir, a.dprefix)
     soft, resized, original = (os.path.join(a.out_dir, d) for d in ("soft", "crf_resized", "crf_original"))
-    pp.buffer_to_soft_score(a.buffer_dir, soft, names, lengths, max_shift=a.max_shift, dprefix=a.dprefix, flow_batch=a.flow_batch or None)
+    score = {"score_batch": a.score_batch} if a.score_batch > 0 else {}  # 0: the keyword is not passed at all (the per-frame path)
+    pp.buffer_to_soft_score(a.buffer_dir, soft, names, lengths, max_shift=a.max_shift, dprefix=a.dprefix, flow_batch=a.flow_batch or None, **score)
     iou = pp.run_crf(soft, a.sxy, a.srgb, a.scomp, a.gauss_k, out_path=resized, batch=a.crf_batch or None)
     report = {"sequences": dict(zip(names, lengths)), "sxy": a.sxy, "srgb": a.srgb, "scomp": a.scomp, "gauss_k": a.gauss_k,
               "crf_batch": a.crf_batch, "flow_batch": a.flow_batch, "iou_resized": float(iou)}
+    report.update(score)
     if a.benchmark:
         from .native_results import frame_lists_from_reader
         report["native_sxy"] = a.native_sxy

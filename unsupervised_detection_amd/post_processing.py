@@ -12,6 +12,8 @@ meaning as post_processing/generate_soft_score_from_buffer.py and post_processin
   propagate_sequences(...) / PWCFlow.batch(...) / select_unary_batch(...)   the sequence stage batched (csrc/sequence.hip):
                     propagate(flow_batch=), buffer_to_soft_score(flow_batch=) and run_crf(batch=) reach them; the defaults (None) keep the
                     per-frame paths
+  soft_score_batch(...) / soft_score_geometry(...)   soft_score for a batch of frames in four launches (csrc/soft_score.hip):
+                    buffer_to_soft_score(score_batch=) reaches it; the default (None) keeps the per-frame path
 
 The kernels of the stage -- border statistics, bytescale, Pillow's 8-bit resampler, canvas placement, min-max / max
 normalisations, remap, blending, the separable Gaussian and the dense-CRF mean field -- run in libudet.so (csrc/postproc.hip); torch
@@ -21,6 +23,7 @@ published algorithms -- see oracle/oracle_post.py for the restatement the kernel
 not be pinned to the original libraries."""
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -28,7 +31,9 @@ import numpy as np
 import torch
 
 from ._ffi import c_f, c_i, c_p, c_sz, check, lib, sig
-from .ragged import PackedLayout, as_layout, check_ranges, require_tensor, upload_tables, workspace
+from .ragged import INT32_MAX, PackedLayout, as_layout, check_ranges, require_tensor, upload_tables, workspace
+
+c_d = ctypes.c_double
 
 for _n, _a in (("udet_post_border_mean", [c_p, c_i, c_i, c_i, c_p, c_p]),
                ("udet_post_bytescale", [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
@@ -45,8 +50,11 @@ for _n, _a in (("udet_post_border_mean", [c_p, c_i, c_i, c_i, c_p, c_p]),
                ("udet_crf_unary_lookup", [c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p]),
                # the sequence stage, batched (csrc/sequence.hip)
                ("udet_post_propagate_sequences", [c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p, c_p, c_sz, c_p]),
-               ("udet_post_select_unary", [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p])):
+               ("udet_post_select_unary", [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+               # the soft scores of a batch of frames (csrc/soft_score.hip)
+               ("udet_post_soft_score_batch", [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_d, c_p, c_p, c_sz, c_p])):
     sig(_n, c_i, *_a)
+sig("udet_post_soft_score_workspace_bytes", c_sz, c_i, c_i, c_i, c_i, c_i)
 sig("udet_post_crf_workspace_bytes", c_sz, c_i, c_i)
 sig("udet_dense_crf_workspace_bytes", c_sz, c_sz, c_i)
 sig("udet_post_propagate_workspace_bytes", c_sz, c_i, c_i)
@@ -182,6 +190,120 @@ def soft_score(preds_b, preds_f, crops=(85, 90, 95, 100), base_crop=90.0, base_h
             score = term if score is None else score + term
     out = torch.empty_like(score)
     check(lib.udet_post_minmax_norm(score.data_ptr(), score.numel(), out.data_ptr(), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- soft score, batched ----
+SOFT_SCORE_GEOM = 16  # UDET_SOFT_SCORE_GEOM (include/udet.h): mode | sy0 sx0 sh sw | hh ww y0 x0 | hk hb hks | vk vb vks | 0
+_soft_tables = {}
+
+
+def soft_score_geometry(ns, crops, base_crop, base_hw):
+    """The tables of udet_post_soft_score_batch (pure host): geom int32 [ns * len(crops), SOFT_SCORE_GEOM], one row per (shift index, crop
+    index) with rectify_pred_mask's integer rules (int(H * crop), int((H - hh) / 2), max(..., 0), the crop > 1 branch), and coef int32, the
+    concatenated _pil_coeffs_host blocks (kk then bounds, one pair per distinct (in, out) size) the rows' offsets point into.  Row layout:
+    mode (0: shift 1 at the base crop, the raw masks; 1: rectify), the source window (sy0, sx0, sh, sw) inside the mask, the patch (hh, ww)
+    and where it lands (y0, x0), then (kk offset, bounds offset, ksize) of the horizontal and of the vertical pass, a negative offset for a
+    pass whose output is as long as its input."""
+    H, W = (int(v) for v in base_hw)
+    ns, nc = int(ns), len(crops)
+    if ns < 1 or nc < 1 or H < 1 or W < 1:
+        raise ValueError("soft_score_geometry: at least one shift, one crop and a frame of 1 x 1")
+    geom = np.zeros((ns * nc, SOFT_SCORE_GEOM), np.int32)
+    blocks, where = [], {}
+
+    def one_pass(n_in, n_out):
+        if n_in == n_out:
+            return (-1, -1, 0)
+        if (n_in, n_out) not in where:
+            kk, bounds, ks = _pil_coeffs_host(n_in, n_out)
+            pos = sum(len(b) for b in blocks)
+            where[(n_in, n_out)] = (pos, pos + kk.size, ks)
+            blocks.extend([kk.reshape(-1), bounds.reshape(-1)])
+        return where[(n_in, n_out)]
+    for si in range(ns):
+        for ci, crop in enumerate(crops):
+            r = si * nc + ci
+            if si == 0 and crop == base_crop:
+                geom[r, :9] = (0, 0, 0, H, W, H, W, 0, 0)
+                geom[r, 9:15] = (-1, -1, 0, -1, -1, 0)
+                continue
+            ratio = crop / base_crop
+            if ratio > 1:  # a central window of the mask, enlarged to the whole canvas
+                c = 1.0 / ratio
+                hh, ww = int(H * c), int(W * c)
+                win, patch = (int((H - hh) / 2), int((W - ww) / 2), hh, ww), (H, W, 0, 0)
+            else:          # the whole mask, shrunk and placed on the canvas
+                hh, ww = int(H * ratio), int(W * ratio)
+                win, patch = (0, 0, H, W), (hh, ww, max(int((H - hh) / 2), 0), max(int((W - ww) / 2), 0))
+            if hh < 1 or ww < 1:
+                raise ValueError("soft-score geometry row {} (shift {}, crop {}): a frame of {} x {} leaves no pixel".format(r, si + 1, crop, H, W))
+            geom[r, :9] = (1,) + win + patch
+            geom[r, 9:15] = one_pass(win[3], patch[1]) + one_pass(win[2], patch[0])
+    coef = np.concatenate(blocks).astype(np.int32) if blocks else np.zeros(1, np.int32)  # (never empty: the call takes no NULL table)
+    return geom, coef
+
+
+def check_soft_score_tables(geom, coef, base_hw):
+    """Host validation of the tables of udet_post_soft_score_batch, before the device is touched (the kernels take every index from them):
+    ValueError, naming the row, unless every rectify row's source window and patch lie inside the H x W frame, its coefficient blocks
+    inside coef, and every tap inside the window (first taps and ends non-decreasing, as Pillow's are).  Returns (geom, coef) as
+    contiguous int32 arrays."""
+    H, W = (int(v) for v in base_hw)
+    g = np.ascontiguousarray(np.asarray(geom, dtype=np.int64))
+    co = np.ascontiguousarray(np.asarray(coef, dtype=np.int64).reshape(-1))
+    if g.ndim != 2 or g.shape[1] != SOFT_SCORE_GEOM or len(g) < 1 or len(co) < 1:
+        raise ValueError("soft-score tables: geom must be [rows, {}] with at least one row, coef not empty".format(SOFT_SCORE_GEOM))
+    if (np.abs(g) > INT32_MAX).any() or (np.abs(co) > INT32_MAX).any():
+        raise ValueError("soft-score tables: values must fit int32")
+    for r, row in enumerate(g.tolist()):
+        mode, sy0, sx0, sh, sw, hh, ww, y0, x0 = row[:9]
+        if mode not in (0, 1):
+            raise ValueError("soft-score geometry row {}: mode must be 0 (identity) or 1 (rectify)".format(r))
+        if mode == 0:
+            continue
+        if min(sy0, sx0) < 0 or min(sh, sw) < 1 or sy0 + sh > H or sx0 + sw > W:
+            raise ValueError("soft-score geometry row {}: the source window {}x{} at ({}, {}) leaves the {}x{} frame".format(r, sh, sw, sy0, sx0, H, W))
+        if min(y0, x0) < 0 or min(hh, ww) < 1 or y0 + hh > H or x0 + ww > W:
+            raise ValueError("soft-score geometry row {}: the patch {}x{} at ({}, {}) leaves the {}x{} canvas".format(r, hh, ww, y0, x0, H, W))
+        for name, (k, b, ks), n_in, n_out in (("horizontal", row[9:12], sw, ww), ("vertical", row[12:15], sh, hh)):
+            if k < 0:
+                if n_in != n_out:
+                    raise ValueError("soft-score geometry row {}: the {} pass {} -> {} cannot be skipped".format(r, name, n_in, n_out))
+                continue
+            if ks < 1 or b < 0 or k + n_out * ks > len(co) or b + 2 * n_out > len(co):
+                raise ValueError("soft-score geometry row {}: the {} coefficient block leaves coef".format(r, name))
+            lo, cnt = co[b:b + 2 * n_out].reshape(-1, 2).T
+            if (lo < 0).any() or (cnt < 1).any() or (cnt > ks).any() or (lo + cnt > n_in).any() or (np.diff(lo) < 0).any() or \
+                    (np.diff(lo + cnt) < 0).any():
+                raise ValueError("soft-score geometry row {}: a tap of the {} pass leaves the window of {}".format(r, name, n_in))
+    return g.astype(np.int32), co.astype(np.int32)
+
+
+def _soft_score_tables(ns, crops, base_crop, H, W, device):
+    """Device copies of soft_score_geometry's validated tables, cached per (ns, crops, base_crop, H, W) and device."""
+    key = (ns, tuple(crops), float(base_crop), H, W, device)
+    if key not in _soft_tables:
+        geom, coef = check_soft_score_tables(*soft_score_geometry(ns, crops, base_crop, (H, W)), base_hw=(H, W))
+        _soft_tables[key] = tuple(upload_tables([geom.reshape(-1), coef], device))
+        torch.cuda.current_stream(device).synchronize()  # once per key: a later call may run on another stream
+    return _soft_tables[key]
+
+
+def soft_score_batch(preds, crops=(85, 90, 95, 100), base_crop=90.0, san_t=0.6):
+    """soft_score for n frames in one call of udet_post_soft_score_batch: four launches whatever n is, no host synchronisation and no copy
+    to the host.  preds: [n, 2, ns, nc, H, W] (device tensor or array), preds[i, 0] / preds[i, 1] = frame i's preds_b / preds_f with nc =
+    len(crops); the frame is the masks' own H x W.  Returns device float64 [n, H, W], row i bit-identical to soft_score(preds[i, 0],
+    preds[i, 1], crops, base_crop, (H, W), san_t)."""
+    t = _dev(preds, torch.float32)
+    if t.dim() != 6 or t.shape[1] != 2 or t.shape[3] != len(crops) or t.shape[0] < 1:
+        raise ValueError("preds must be [n, 2, ns, {}, H, W] (one mask per direction, shift and crop), n at least 1".format(len(crops)))
+    n, _, ns, nc, H, W = (int(v) for v in t.shape)
+    d_geom, d_coef = _soft_score_tables(ns, crops, base_crop, H, W, t.device)
+    out = torch.empty((n, H, W), dtype=torch.float64, device=t.device)
+    ws = workspace(lib.udet_post_soft_score_workspace_bytes(n, ns, nc, H, W), 16, t.device)
+    check(lib.udet_post_soft_score_batch(t.data_ptr(), n, ns, nc, H, W, d_geom.data_ptr(), d_coef.data_ptr(), float(san_t), out.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), torch.cuda.current_stream(t.device).cuda_stream))
     return out
 
 
@@ -530,19 +652,25 @@ def _save_soft(out_dir, masks, imgs, gts, fwd, bwd):
 
 
 def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2, base_crop=90.0, dprefix="davis_shift", flow_fn=None,
-                         flow_batch=None):
+                         flow_batch=None, score_batch=None):
     """generate_soft_score_from_buffer.buffer_to_soft_score over the result_<k>.mat buffers test_generator_ensemble writes
     (evaluation.evaluate_ensemble), followed by propagate(); writes result_<k>.mat with pred_mask / img1 / gt_mask /
     running_avg_f / running_avg_b like the reference (:91-93, :148, :184, :199, :229).  flow_batch (None: propagate() per sequence as
-    it is read): an integer computes the soft scores of the whole folder first and propagates all its sequences in one call."""
+    it is read): an integer computes the soft scores of the whole folder first and propagates all its sequences in one call.
+    score_batch (None: a soft_score call per frame): an integer takes a sequence's frames in groups of that many -- one host buffer, one
+    upload and one soft_score_batch call per group, the last group of a sequence shorter; the same files, keys and dtypes.  The frame is
+    the masks' own size (the reference's 192 x 384)."""
     import scipy.io as sio
     crops = list(range(85, 101, 5))
+    if score_batch is not None and int(score_batch) < 1:
+        raise ValueError("buffer_to_soft_score: score_batch must be None or at least 1")
     held = []  # flow_batch: (out_dir, masks, imgs, gts) of every sequence until the one propagation
     for name, num in zip(seq_names, seq_num):
         out_dir = os.path.join(out_path, name)
         os.makedirs(out_dir, exist_ok=True)
         print(out_dir)
         masks, imgs, gts = [], [], []
+        group = None  # score_batch: the host buffer [frames, 2, shifts, crops, H, W] of the group being read
         for k in range(1, num + 1):
             pb, pf, r_f1 = [], [], None
             for shift in range(1, max_shift + 1):
@@ -552,7 +680,15 @@ def buffer_to_soft_score(buffer_path, out_path, seq_names, seq_num, max_shift=2,
                 pf.append([np.squeeze(r_f["pred_mask_%03d" % c]) for c in crops])
                 if shift == 1:
                     r_f1 = r_f
-            masks.append(soft_score(pb, pf, crops, base_crop))
+            if score_batch is None:
+                masks.append(soft_score(pb, pf, crops, base_crop, pb[0][0].shape))
+            else:
+                at = (k - 1) % int(score_batch)
+                if at == 0:
+                    group = np.empty((min(int(score_batch), num - k + 1), 2, max_shift, len(crops)) + pb[0][0].shape, np.float32)
+                group[at, 0], group[at, 1] = np.asarray(pb), np.asarray(pf)
+                if at == len(group) - 1:
+                    masks.extend(soft_score_batch(group, crops, base_crop))
             imgs.append(((r_f1["img_1_%03d" % int(base_crop)] + 0.5) * 255).astype("uint8"))
             gts.append(r_f1["gt_mask_%03d" % int(base_crop)])
         if flow_batch is not None:
