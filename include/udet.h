@@ -346,6 +346,32 @@ size_t udet_grad_histogram_workspace_bytes(int nseg);
 int udet_grad_histogram(const float* g, const long long* seg_offsets, int nseg, double* stats, unsigned* counts, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* The final mask of every frame drawn on the untouched frame at the frame's own size, for a ragged batch in one launch (csrc/visualize.hip,
+ * DESIGN.md 7.6): the picture of test_generator.py:101-106 without its resize, plus the mask's contour.  Packed layout of
+ * udet_dense_crf_ragged: sample i = H_i x W_i elements at element offset offsets[i] (device int64 [n]), hw device int32 [n][2]; image_rgb
+ * and out_rgb 3 bytes per element (sample i at byte 3 * offsets[i]); mask 1 byte per element (the `binary`, `labels` or `selected` buffer
+ * of the calls above), fg = mask != 0.  Colours are 0xRRGGBB.  Per sample and channel c, with m_c the channel of mask_rgb on a
+ * foreground pixel and 0 elsewhere:
+ *   t = rint(fl32(fl32(img_c) * alpha) + fl32(fl32(m_c) * beta))   two float32 products and one float32 sum, each rounded on its own (no
+ *                                                                  FMA), rint to even, saturated to 0..255: cv2.addWeighted as
+ *                                                                  udet_overlay_mask has it (0.5, 0.4, 0x00FF00: the reference's picture)
+ * edge >= 1: a foreground pixel (y, x) is a contour pixel when some (y + dy, x + dx), |dy|, |dx| <= edge, INSIDE the frame is background
+ * (positions outside the frame never count as background: an object cut by the frame border gets no line along the border) -- fg &
+ * ~binary_erosion(fg, ones((2 edge + 1, 2 edge + 1)), border_value=1); it is written as edge_rgb, unblended.  edge = 0: no contour, no
+ * neighbour is read.  Bytes of out_rgb between the samples are not written; out_rgb must not overlap the inputs.
+ * One launch whatever n is, no workspace, no atomics, no workgroup waits for another: the grid is the 32 x 64 tiles of (max_h, max_w)
+ * times n, workgroups beyond a smaller sample's tiles leave at once; the tile's foreground bits and an edge-wide halo are bit-packed in
+ * LDS (128 columns per row), the windowed minimum is separable on the packed words; a thread takes the four pixels whose twelve colour
+ * bytes form three aligned 32-bit words (the tile's columns are shifted per row by the row's element offset modulo 4, since 3 *
+ * offsets[i] is not aligned in general; image_rgb / out_rgb that are not 4-byte aligned, and the groups cut by a row end, go byte by byte).
+ * UDET_ERR_ARG, nothing enqueued: n outside 1..65535, a NULL pointer, max_h or max_w < 1 (or max_h * max_w >= 2^31), total_pixels < 1,
+ * edge < 0, a negative or non-finite alpha or beta.  UDET_ERR_UNSUPPORTED: edge > UDET_OVERLAY_MAX_EDGE.  UDET_ERR_SHAPE: more than 2^23
+ * tiles per sample.  The tables are device memory: the host caller validates them before the launch (ragged.as_layout / PackedLayout). */
+#define UDET_OVERLAY_MAX_EDGE 8
+int udet_overlay_native_ragged(const unsigned char* image_rgb, const unsigned char* mask, int n, const long long* offsets,
+                               const int* hw, int max_h, int max_w, size_t total_pixels, float alpha, float beta,
+                               unsigned mask_rgb, int edge, unsigned edge_rgb, unsigned char* out_rgb, void* stream);
+
 /* tf.nn.conv2d / tf.layers.conv2d, padding='SAME', + bias + activation
  * (models/utils/convolution_utils.py:46,81-84; models/PWCNet/model_pwcnet.py:161-165,484-504,562-574).
  * upsample2x != 0 first applies tf.image.resize_nearest_neighbor(x2, align_corners=True)

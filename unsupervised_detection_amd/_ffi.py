@@ -75,6 +75,7 @@ sig("udet_tune_load", c_i, ctypes.c_char_p)
 sig("udet_flow_to_image_workspace_bytes", c_sz, c_i)
 sig("udet_flow_to_image", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_sz, c_p)
 sig("udet_overlay_mask", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p)
+sig("udet_overlay_native_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_f, c_f, ctypes.c_uint, c_i, ctypes.c_uint, c_p, c_p)
 sig("udet_histogram_limits", c_i, c_p, c_i)
 sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
 sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)

@@ -45,6 +45,15 @@ _DEFS = [
     ("gauss_k", float, 0.1),
     ("crf_iters", int, 50),
     ("crf_radius", int, 0),
+    # not reference flags: with --native_resolution, --overlay also draws every final mask on its frame at the frame's own size
+    # (visualize.overlay_native) into D/native/overlay: the mask blended overlay_alpha / overlay_beta in overlay_colour (r,g,b), its
+    # contour overlay_edge pixels wide (0..8; 0: none) in overlay_edge_colour
+    ("overlay", bool, False),
+    ("overlay_edge", int, 2),
+    ("overlay_alpha", float, 0.5),
+    ("overlay_beta", float, 0.4),
+    ("overlay_colour", str, "0,255,0"),
+    ("overlay_edge_colour", str, "255,255,255"),
 ]
 
 

@@ -3,6 +3,8 @@
 //   models/adversarial_learner.py     collect_summaries :260-298 (flow images, the masked flow image, tf.summary.histogram of every
 //                                     variable's gradient)
 //   test_generator.py                 :93-117 (postprocess_image / postprocess_mask, cv2.addWeighted, cv2.resize to 384 x 640)
+//                                     :101-106 once more at every frame's own size, without the resize and with the mask's contour, for a
+//                                     ragged batch of untouched frames and final masks (overlay_native_ragged)
 // The inputs already sit in plan buffers (image, flow, mask, pred, the flat gradient buffers); these kernels turn them into the uint8
 // images and the bucket counts a writer stores, so that a summary step costs a few hundred microseconds of device time (profiles/NOTES.md) and two small copies.
 // Written for exact agreement with the reference's arithmetic, not for a roofline.  Compiled with -ffp-contract=off (Makefile): the
@@ -164,6 +166,144 @@ __global__ __launch_bounds__(256) void overlay_mask_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// overlay_native_ragged
+// ---------------------------------------------------------------------------------------------------------------------------------
+// One workgroup owns a tile of ON_TH rows x ON_TW columns of one sample of the packed batch.
+//   1. the foreground bits of the tile's rows plus `edge` rows above and below are packed into LDS, one __ballot per (row, word): a row
+//      is 128 bits, bit p = column x0 - ON_LEFT + p; positions outside the frame are 1 (they never count as background);
+//   2. the (2 edge + 1)^2 windowed minimum is two passes of ANDs on the packed words: a thread per row ANDs the row with its shifts
+//      by 1 .. edge in both directions, then a thread per tile row ANDs 2 edge + 1 of those rows;
+//   3. a thread takes four pixels of a row whose twelve colour bytes are three aligned 32-bit words: the row's groups start where the
+//      element index offsets[i] + y W + x is a multiple of 4, so the tile's columns are [x0 - s, x0 + ON_TW - s) with s = (offsets[i] +
+//      y W) mod 4 in that row (hence the ON_LEFT - edge = 4 spare columns, and a grid of ceil((max_w + 3) / ON_TW) tile columns).  A
+//      group cut by a row end, and every group when image / out are not 4-byte aligned themselves, goes byte by byte.
+#define ON_TH 32
+#define ON_TW 64
+#define ON_LEFT (4 + UDET_OVERLAY_MAX_EDGE)            // columns of the packed row in front of the tile's first
+#define ON_ROWS (ON_TH + 2 * UDET_OVERLAY_MAX_EDGE)
+static_assert(ON_LEFT + ON_TW + UDET_OVERLAY_MAX_EDGE <= 128, "a packed row is two 64-bit words");
+
+// bits pos .. pos + 3 of the 128-bit row (lo, hi), 1 <= pos <= 124
+__device__ __forceinline__ unsigned row_bits4(unsigned long long lo, unsigned long long hi, int pos) {
+  return (unsigned)(pos < 64 ? (lo >> pos) | (hi << (64 - pos)) : hi >> (pos - 64)) & 15u;
+}
+// cv2.addWeighted of one byte: v * alpha and the mask's term mb = m * beta are float32 products, their sum a float32 sum (no FMA: the
+// file is compiled with -ffp-contract=off), rounded half to even and saturated (both terms are >= 0)
+__device__ __forceinline__ unsigned native_blend(unsigned v, float alpha, float mb) {
+  return (unsigned)fminf(rintf((float)v * alpha + mb), 255.f);
+}
+__global__ __launch_bounds__(256) void overlay_native_kernel(const unsigned char* __restrict__ image, const unsigned char* __restrict__ mask,
+                                                             const long long* __restrict__ offsets, const int* __restrict__ hw, int tiles_x,
+                                                             float alpha, float beta, unsigned mask_rgb, int edge, unsigned edge_rgb,
+                                                             unsigned char* __restrict__ out, int wide) {
+  __shared__ unsigned long long F[ON_ROWS][2];  // foreground, row 0 = image row y0 - edge
+  __shared__ unsigned long long Hm[ON_ROWS][2];  // its minimum over x - edge .. x + edge
+  __shared__ unsigned long long E[ON_TH][2];     // the eroded mask of the tile's own rows
+  const int n = blockIdx.y;
+  const int H = hw[2 * n], W = hw[2 * n + 1];
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = ty * ON_TH, x0 = tx * ON_TW;
+  if (y0 >= H || x0 - 3 >= W) return;  // beyond this sample's tiles (the whole workgroup: nothing below is reached)
+  const long off = offsets[n];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int items = 2 * (ON_TH + 2 * edge);  // (row, word) pairs to pack
+
+  // 1. pack: four (row, word) items per wave and round, the loads issued before the ballots.  Only the columns a contour of this tile
+  // can depend on are read: [x0 - 3 - edge, x0 + ON_TW - 1 + edge] inside the frame.
+  const int need_lo = max(x0 - 3 - edge, 0), need_hi = min(x0 + ON_TW - 1 + edge, W - 1);
+  for (int it0 = wave; it0 < items; it0 += 16) {
+    unsigned char v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int it = it0 + 4 * u;
+      const int gy = y0 - edge + (it >> 1), gx = x0 - ON_LEFT + 64 * (it & 1) + lane;
+      v[u] = 1;
+      if (it < items && gy >= 0 && gy < H && gx >= need_lo && gx <= need_hi) v[u] = mask[off + (long)gy * W + gx];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int it = it0 + 4 * u;
+      const unsigned long long b = __ballot(v[u] != 0);
+      if (it < items && lane == 0) F[it >> 1][it & 1] = b;
+    }
+  }
+  __syncthreads();
+
+  // 2. the windowed minimum, separable; bits shifted in from beyond the 128 columns are 1 (no result that is used depends on them)
+  if (edge > 0) {
+    if ((int)threadIdx.x < ON_TH + 2 * edge) {
+      const unsigned long long lo = F[threadIdx.x][0], hi = F[threadIdx.x][1];
+      unsigned long long mlo = lo, mhi = hi;
+      for (int d = 1; d <= edge; ++d) {
+        mlo &= ((lo >> d) | (hi << (64 - d))) & ((lo << d) | (~0ull >> (64 - d)));
+        mhi &= ((hi >> d) | (~0ull << (64 - d))) & ((hi << d) | (lo >> (64 - d)));
+      }
+      Hm[threadIdx.x][0] = mlo;
+      Hm[threadIdx.x][1] = mhi;
+    }
+    __syncthreads();
+    if (threadIdx.x < ON_TH) {
+      unsigned long long mlo = ~0ull, mhi = ~0ull;
+      for (int r = 0; r <= 2 * edge; ++r) {
+        mlo &= Hm[threadIdx.x + r][0];
+        mhi &= Hm[threadIdx.x + r][1];
+      }
+      E[threadIdx.x][0] = mlo;
+      E[threadIdx.x][1] = mhi;
+    }
+    __syncthreads();
+  }
+
+  // 3. blend and contour: two groups of four pixels per thread, 16 groups (192 contiguous bytes) per row
+  const float mb0 = (float)((mask_rgb >> 16) & 255u) * beta, mb1 = (float)((mask_rgb >> 8) & 255u) * beta, mb2 = (float)(mask_rgb & 255u) * beta;
+  const unsigned e0 = (edge_rgb >> 16) & 255u, e1 = (edge_rgb >> 8) & 255u, e2 = edge_rgb & 255u;
+  const int k = threadIdx.x & 15;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int ry = (threadIdx.x >> 4) + 16 * half, gy = y0 + ry;
+    if (gy >= H) continue;
+    const long b = off + (long)gy * W;  // element index of the row's first pixel
+    const int s = (int)(b & 3);
+    const int xf = x0 - s + 4 * k;      // the group's first pixel: b + xf is a multiple of 4
+    if (xf + 3 < 0 || xf >= W) continue;
+    const int pos = ON_LEFT - s + 4 * k;
+    const unsigned fg = row_bits4(F[ry + edge][0], F[ry + edge][1], pos);
+    const unsigned ct = edge > 0 ? fg & ~row_bits4(E[ry][0], E[ry][1], pos) : 0u;
+    if (wide && xf >= 0 && xf + 3 < W) {
+      const long w0 = 3 * ((b + xf) >> 2);  // 32-bit word index of the group's first byte
+      const unsigned* p = reinterpret_cast<const unsigned*>(image) + w0;
+      const unsigned src0 = p[0], src1 = p[1], src2 = p[2];
+      unsigned dst[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int i = 0; i < 12; ++i) {
+        const int j = i / 3, c = i % 3;
+        const unsigned v = ((i < 4 ? src0 : (i < 8 ? src1 : src2)) >> (8 * (i & 3))) & 255u;
+        const float mb = ((fg >> j) & 1u) ? (c == 0 ? mb0 : (c == 1 ? mb1 : mb2)) : 0.f;
+        const unsigned r = ((ct >> j) & 1u) ? (c == 0 ? e0 : (c == 1 ? e1 : e2)) : native_blend(v, alpha, mb);
+        dst[i >> 2] |= r << (8 * (i & 3));
+      }
+      unsigned* q = reinterpret_cast<unsigned*>(out) + w0;
+      q[0] = dst[0];
+      q[1] = dst[1];
+      q[2] = dst[2];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int x = xf + j;
+        if (x < 0 || x >= W) continue;
+        const long at = 3 * (b + x);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const float mb = ((fg >> j) & 1u) ? (c == 0 ? mb0 : (c == 1 ? mb1 : mb2)) : 0.f;
+          out[at + c] = (unsigned char)(((ct >> j) & 1u) ? (c == 0 ? e0 : (c == 1 ? e1 : e2)) : native_blend(image[at + c], alpha, mb));
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // grad_histogram
 // ---------------------------------------------------------------------------------------------------------------------------------
 #define GH_BUCKETS UDET_HISTOGRAM_BUCKETS
@@ -289,6 +429,35 @@ int udet_overlay_mask(const float* image, const float* mask, const double* stats
   const long q = (long)oh * ow;
   hipLaunchKernelGGL(overlay_mask_kernel, dim3((unsigned)((q + 255) / 256), n), dim3(256), 0, (hipStream_t)stream, image, mask, stats8,
                      threshold, h, w, out, oh, ow, (double)h / oh, (double)w / ow);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+int udet_overlay_native_ragged(const unsigned char* image_rgb, const unsigned char* mask, int n, const long long* offsets,
+                               const int* hw, int max_h, int max_w, size_t total_pixels, float alpha, float beta,
+                               unsigned mask_rgb, int edge, unsigned edge_rgb, unsigned char* out_rgb, void* stream) {
+  if (bad_batch("overlay_native_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!image_rgb || !mask || !offsets || !hw || !out_rgb) {
+    set_error("overlay_native_ragged: bad argument (non-null image_rgb, mask, offsets, hw and out_rgb)");
+    return UDET_ERR_ARG;
+  }
+  if (edge < 0 || !(alpha >= 0.f) || !(beta >= 0.f) || isinf(alpha) || isinf(beta)) {
+    set_error("overlay_native_ragged: edge %d >= 0 and finite alpha %g >= 0 and beta %g >= 0 are required", edge, alpha, beta);
+    return UDET_ERR_ARG;
+  }
+  if (edge > UDET_OVERLAY_MAX_EDGE) {
+    set_error("overlay_native_ragged: edge %d above UDET_OVERLAY_MAX_EDGE = %d", edge, UDET_OVERLAY_MAX_EDGE);
+    return UDET_ERR_UNSUPPORTED;
+  }
+  // a row's groups of four pixels start up to three columns before the tile's first: ceil((max_w + 3) / ON_TW) tile columns
+  const long tiles_x = ((long)max_w + 3 + ON_TW - 1) / ON_TW, tiles_y = ((long)max_h + ON_TH - 1) / ON_TH;
+  if (tiles_x * tiles_y > (1L << 23)) {
+    set_error("overlay_native_ragged: more than 2^23 tiles per sample");
+    return UDET_ERR_SHAPE;
+  }
+  const int wide = ((reinterpret_cast<uintptr_t>(image_rgb) | reinterpret_cast<uintptr_t>(out_rgb)) & 3) == 0;
+  hipLaunchKernelGGL(overlay_native_kernel, dim3((unsigned)(tiles_x * tiles_y), n), dim3(256), 0, (hipStream_t)stream, image_rgb, mask,
+                     offsets, hw, (int)tiles_x, alpha, beta, mask_rgb, edge, edge_rgb, out_rgb, wide);
   UDET_HIP(hipGetLastError());
   return UDET_OK;
 }

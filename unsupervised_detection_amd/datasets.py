@@ -12,6 +12,8 @@ data.Davis2016Reader, and the draws of a training batch come in the DAVIS order:
   FBMS59Reader.get_filenames_list / get_test_tuples / image_inputs / test_inputs / augmented_inputs   :172-392
   SegTrackV2 DirectoryIterator(directory)                                    segtrackv2_data_utils.py:11-69
   SegTrackV2Reader.get_filenames_list / image_inputs / test_inputs / augmented_inputs                 :72-330
+  FrameFolderReader (natural_key, frame_files, frame_folder_sequences)       a plain folder of frames without annotations: the
+                                                                             use of scripts/create_data_frvideo.py + test_video.sh
 
 Batches are the dicts {"img1","img2","gt_mask","fname"} AdversarialLearner consumes; FBMS test batches also carry
 "samples_per_cat" (float32 per row, the number of annotated frames of the row's sequence)."""
@@ -109,7 +111,7 @@ class _RaggedReader(object):
             for crop in test_crops:
                 d["img_1s"][crop] = data.central_cropping(batch["img1"], crop)[0]
                 d["img_2s"][crop] = data.central_cropping(batch["img2"], crop)[0]
-                d["seg_1s"][crop] = data.central_cropping(batch["gt_mask"], crop)[0]
+                d["seg_1s"][crop] = None if batch["gt_mask"] is None else data.central_cropping(batch["gt_mask"], crop)[0]
             yield d, batch["fname"][0]
 
 
@@ -416,4 +418,101 @@ class SegTrackV2Reader(_RaggedReader):
 
     def augmented_inputs(self, t_len=2, test_crops=(1.0,)):
         """Per frame a dict of centrally cropped versions for the ensemble (:306-330), batch size 1."""
+        return self._augment(self.test_inputs(batch_size=1, t_len=t_len, with_fname=True, test_crop=1.0), test_crops)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A plain folder of frames (no annotations)
+# ---------------------------------------------------------------------------------------------------------------------------------
+
+FRAME_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp")
+
+
+def natural_key(name):
+    """Sort key of the natural order of file names: runs of digits compare as integers (frame_2 < frame_10), everything between them
+    as plain strings, ties (frame_02 / frame_2) broken by the plain string."""
+    return [int(t) if i & 1 else t for i, t in enumerate(re.split(r"(\d+)", name))], name
+
+
+def frame_files(names):
+    """The frames among the file names of one directory, in natural order: names ending in .jpg / .jpeg / .png / .bmp (any case);
+    dot-files and everything else are ignored."""
+    return sorted((n for n in names if not n.startswith(".") and n.lower().endswith(FRAME_EXTENSIONS)), key=natural_key)
+
+
+def frame_folder_sequences(root_dir):
+    """[(sequence name, [frame paths in natural order]), ...] of a folder of frames: every sub-directory of root_dir that holds images is
+    a sequence, sorted by name; if none does and root_dir itself holds images, it is one sequence named basename(root_dir).  No image
+    at all (or no such directory) is an IOError."""
+    root = os.path.abspath(root_dir) if root_dir else ""  # (a frame's category is the directory above it: "." would not name one)
+    layout = "FRAMES layout: <root_dir>/<sequence>/<frame>.jpg|.jpeg|.png|.bmp, or the frames in <root_dir> itself"
+    if not (root and os.path.isdir(root)):
+        raise IOError("Directory {!r} not found ({})".format(root_dir, layout))
+    seqs = []
+    for name in sorted(os.listdir(root)):
+        d = os.path.join(root, name)
+        if name.startswith(".") or not os.path.isdir(d):
+            continue
+        frames = frame_files(os.listdir(d))
+        if frames:
+            seqs.append((name, [os.path.join(d, f) for f in frames]))
+    if not seqs:
+        frames = frame_files(os.listdir(root))
+        if frames:
+            seqs.append((os.path.basename(root), [os.path.join(root, f) for f in frames]))
+    if not seqs:
+        raise IOError("Did not find any image under {!r} ({})".format(root_dir, layout))
+    return seqs
+
+
+class FrameFolderReader(_RaggedReader):
+    """A reader for one's own footage: frames on disk (frame_folder_sequences), no annotation anywhere -- the job of the reference's
+    scripts/create_data_frvideo.py + scripts/test_video.sh without the faked DAVIS tree.  Batches carry "gt_mask": None, which
+    learner.inference, evaluate_masks and evaluate_ensemble take.  No partition argument, like SegTrackV2Reader.  A sequence must hold
+    max_temporal_len + 1 frames to train on and |t_len| + 1 to test on (IOError naming it); in a test sequence shorter than 2 |t_len|
+    the second frame of a pair is clamped into its own sequence."""
+
+    def __init__(self, root_dir, max_temporal_len=3, min_temporal_len=2, num_threads=6, device="cuda", seed=None, loader=None,
+                 shard=(0, 1)):
+        super().__init__(root_dir, max_temporal_len, min_temporal_len, num_threads, device, seed, loader, shard)
+
+    def get_filenames_list(self, min_frames=1):
+        """(per-sequence frame lists, per-sequence lists of None); a sequence of fewer than min_frames frames is an IOError."""
+        seqs = frame_folder_sequences(self.root_dir)
+        for name, frames in seqs:
+            if len(frames) < min_frames:
+                raise IOError("Sequence {!r} under {!r} holds {} frame(s), {} are needed".format(name, self.root_dir, len(frames), min_frames))
+        self.val_samples = sum(len(f) for _, f in seqs)
+        print("Found {} images belonging to {} experiments.".format(self.val_samples, len(seqs)))
+        return [f for _, f in seqs], [[None] * len(f) for _, f in seqs]
+
+    def image_inputs(self, batch_size=32, train_crop=1.0, num_threads=6):
+        """Endless training batches {"img1","img2"}: img2 = img1 +- U{min..max} frames, augmented (the other readers' image_inputs)."""
+        file_list, _ = self.get_filenames_list(self.max_temporal_len + 1)
+        filenames = np.concatenate(file_list)
+        table = data.pair_table([len(f) for f in file_list], self.max_temporal_len, True)
+        return self._train_batches(filenames, table, batch_size, train_crop)
+
+    def test_inputs(self, batch_size=32, t_len=2, with_fname=False, test_crop=1.0):
+        """One pass over every frame: time(img2) - time(img1) = t_len except at sequence ends; "gt_mask" is None."""
+        file_list, _ = self.get_filenames_list(abs(t_len) + 1)
+        filenames = np.concatenate(file_list)
+        lengths = [len(f) for f in file_list]
+        table = data.pair_table(lengths, t_len, False)
+        first = np.repeat(np.cumsum([0] + lengths[:-1]), lengths)  # per frame: the first and the last frame of its sequence
+        last = first + np.repeat(lengths, lengths) - 1
+
+        def gen():
+            for s in range(0, len(table), batch_size):  # drop_remainder=False
+                rows = table[s:s + batch_size]
+                i1 = rows[:, 0].astype(np.int32)
+                i2 = (np.float32(abs(t_len)) * rows[:, 1] + rows[:, 0]).astype(np.int32)
+                i2 = np.clip(i2, first[i1], last[i1])
+                a, b = self._image_pairs(filenames[i1], filenames[i2])
+                yield {"img1": data.central_cropping(a, test_crop), "img2": data.central_cropping(b, test_crop), "gt_mask": None,
+                       "fname": [f.encode() for f in filenames[i1]]}
+        return gen()
+
+    def augmented_inputs(self, t_len=2, test_crops=(1.0,)):
+        """Per frame a dict of centrally cropped versions for the ensemble, batch size 1; seg_1s[crop] is None."""
         return self._augment(self.test_inputs(batch_size=1, t_len=t_len, with_fname=True, test_crop=1.0), test_crops)

@@ -19,7 +19,10 @@ post_processing/post_processing.py:32-46:
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
   restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] + J / F +
                                                 <sequence>/<frame>.png, result_<k>.mat, native_eval.json
-  frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order
+  frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order; (image, None) for
+                                                a folder of frames without annotations (--dataset FRAMES), which restore_results_dir
+                                                takes in its annotation-free mode; overlay=... draws the final masks on the frames
+                                                (visualize.overlay_native)
 
 scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  The "best detection candidate from
 the set of predicted connected masks" the reference only mentions in a comment (post_processing.py:32-35) is select_components
@@ -419,10 +422,26 @@ def crf_refine_restored(res, images, crf) -> RestoredMasks:
     return RestoredMasks(res.data, labels, res.layout, None, res.amax)
 
 
+def load_sizes_header(paths):
+    """[(H, W), ...] of image files from their headers alone (Pillow opens lazily: nothing is decoded)."""
+    from PIL import Image
+    sizes = []
+    for p in paths:
+        with Image.open(p) as im:
+            sizes.append((im.size[1], im.size[0]))
+    return sizes
+
+
+def draw_overlays(frames, masks, overlay):
+    """visualize.overlay_native(frames, masks, **overlay): the masks of a batch on their frames, one launch."""
+    from .visualize import overlay_native
+    return overlay_native(frames, masks, **overlay)
+
+
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
                         gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True,
                         component=None, connectivity=8, select=select_components, crf=None, load_images=load_images_device,
-                        refine=crf_refine_restored):
+                        refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -442,21 +461,42 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     returns the restored batch with the CRF's labels as its binary masks; they take the place of the thresholded masks for
     everything downstream (component selection, J / F, the .png, `mask`); soft_mask stays the restored soft mask and the json gains
     "crf" with the parameters used.
-    restore / load_gt / score / select / load_images / refine are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    Annotation-free mode (a folder of one's own frames, datasets.FrameFolderReader): every annotation of frame_lists is None (a mix
+    of None and paths is a ValueError).  The frames' sizes then come from load_sizes(paths) -> [(H, W), ...] (load_sizes_header: the
+    image header, no decode); load_gt and score are not called and gt_rule is not looked at; component "best_gt" is a ValueError;
+    result_<k>.mat holds mask and soft_mask only; native_eval.json carries "annotations": false, no J / F / IoU key, and per sequence
+    frames, foreground_mean (the mean over its frames of |mask| / (H W), from integer counts) and, with a component mode,
+    components_mean.
+    overlay (None: off): a dict of the parameters of visualize.overlay_native (alpha, beta, colour, edge, edge_colour; {} for the
+    defaults).  Every frame's final binary mask -- after the CRF and the component selection -- is drawn on the untouched frame at its
+    own size (draw: one call of overlay_native per batch, on the frames the CRF already loaded when it is on) and written to
+    <out_dir>/overlay/<category>/<frame stem>.png; the mask folders keep only masks; the json gains "overlay" with the parameters used.
+    restore / load_gt / score / select / load_images / refine / load_sizes / draw are injectable: the host logic runs without a GPU on
+    numpy stand-ins."""
     import json
     import re
     import scipy.io as sio
     from PIL import Image
     from .evaluation import BOUND_TH, _davis_summary, _nanmean, _print_davis_table
     bound_th = BOUND_TH if bound_th is None else bound_th
-    rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
     batch = max(1, int(batch))
     if component not in (None, "largest", "best_gt"):
         raise ValueError('component must be None, "largest" or "best_gt"')
     if component is not None and connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8")
     crf = None if crf is None else crf_params(crf)
-    cat_j, cat_f, cat_nc = {}, {}, {}
+    if overlay is not None:
+        from .visualize import overlay_params
+        overlay = overlay_params(overlay)
+    missing = [a is None for entries in frame_lists.values() for _, a in entries]
+    free = bool(missing) and all(missing)  # annotation-free: sizes from the frames, nothing to score against
+    if any(missing) and not free:
+        raise ValueError("frame_lists mixes frames with and without an annotation")
+    if free and component == "best_gt":
+        raise ValueError('component "best_gt" needs annotations: use "largest" or None')
+    if not free:
+        rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
+    cat_j, cat_f, cat_nc, cat_fg = {}, {}, {}, {}
     for cat, entries in frame_lists.items():
         d = os.path.join(results_dir, cat)
         ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
@@ -464,7 +504,9 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             raise IOError("category {!r}: {} result_<k>.mat under {!r} for {} listed frames".format(cat, len(ks), d, len(entries)))
         od = os.path.join(out_dir, cat)
         os.makedirs(od, exist_ok=True)
-        j, f, nc = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries))
+        if overlay is not None:
+            os.makedirs(os.path.join(out_dir, "overlay", cat), exist_ok=True)
+        j, f, nc, fg = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries)), np.zeros(len(entries))
         for s in range(0, len(entries), batch):
             rows = entries[s:s + batch]
             masks = []
@@ -475,27 +517,64 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                 masks.append(np.squeeze(mat[mask_key]).astype(np.float32))
                 if masks[-1].ndim != 2 or masks[-1].shape != masks[0].shape:
                     raise ValueError("{}: result_{}.mat: masks must be 2-D and of one shape".format(d, k))
-            gt = load_gt([a for _, a in rows], rule)
-            res = restore(np.stack(masks), getattr(gt, "layout", gt.hw), crop, threshold)  # the annotations' layout is the batch's
+            if free:
+                gt = None
+                sizes = np.asarray(load_sizes([img for img, _ in rows]), dtype=np.int64).reshape(-1, 2)
+                if len(sizes) != len(rows):
+                    raise ValueError("load_sizes must return one (H, W) per path")
+                res = restore(np.stack(masks), sizes, crop, threshold)
+            else:
+                gt = load_gt([a for _, a in rows], rule)
+                res = restore(np.stack(masks), getattr(gt, "layout", gt.hw), crop, threshold)  # the annotations' layout is the batch's
             pred = res  # what is scored and exported as the binary mask
+            frames = load_images([img for img, _ in rows]) if crf is not None or overlay is not None else None  # read once for both
             if crf is not None:
-                pred = refine(res, load_images([img for img, _ in rows]), crf)
+                pred = refine(res, frames, crf)
             if component is not None:
                 pred = select(pred, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity)
                 nc[s:s + len(rows)] = _host(pred.info)[:, 0]
-            shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
-            for shape in sorted(set(shapes)):
-                idx = [i for i, sh in enumerate(shapes) if sh == shape]
-                jj, ff = score(gt.stack(idx), pred.stack(idx), bound_th)
-                j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
+            if not free:
+                shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
+                for shape in sorted(set(shapes)):
+                    idx = [i for i, sh in enumerate(shapes) if sh == shape]
+                    jj, ff = score(gt.stack(idx), pred.stack(idx), bound_th)
+                    j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
+            drawn = draw(frames, pred, overlay) if overlay is not None else None
             for i, (img, _) in enumerate(rows):
+                stem = os.path.splitext(os.path.basename(img))[0]
                 binm = _host(pred.binary_sample(i)).astype(np.uint8)
-                Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, os.path.splitext(os.path.basename(img))[0] + ".png"))
-                sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)),
-                            {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32), "gt_mask": _host(gt.sample(i)).astype(np.uint8)})
+                Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, stem + ".png"))
+                mat = {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32)}
+                if free:
+                    fg[s + i] = int(np.count_nonzero(binm)) / int(binm.size)
+                else:
+                    mat["gt_mask"] = _host(gt.sample(i)).astype(np.uint8)
+                sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)), mat)
+                if drawn is not None:
+                    Image.fromarray(np.ascontiguousarray(_host(drawn.sample(i)), dtype=np.uint8), "RGB").save(
+                        os.path.join(out_dir, "overlay", cat, stem + ".png"))
         cat_j[cat], cat_f[cat], cat_nc[cat] = j.tolist(), f.tolist(), float(nc.mean()) if len(nc) else 0.0
+        cat_fg[cat] = float(fg.mean()) if len(fg) else 0.0
     if not cat_j:
         raise IOError("no category to restore")
+    if free:
+        out = {"mask_key": mask_key, "threshold": threshold, "crop": crop, "annotations": False,
+               "sequences": {c: {"frames": len(cat_j[c]), "foreground_mean": cat_fg[c]} for c in cat_j}}
+        if component is not None:
+            out["component"], out["connectivity"] = component, int(connectivity)
+            for c in out["sequences"]:
+                out["sequences"][c]["components_mean"] = cat_nc[c]
+        if crf is not None:
+            out["crf"] = crf
+        if overlay is not None:
+            out["overlay"] = overlay
+        if verbose:
+            print("Native resolution ({} frames, crop {}, no annotations):".format(sum(len(v) for v in cat_j.values()), crop))
+            for c, v in out["sequences"].items():
+                print("  {:<24s} {:5d} frames   foreground {:.4f}".format(c, v["frames"], v["foreground_mean"]))
+        with open(os.path.join(out_dir, "native_eval.json"), "w") as fh:
+            json.dump(out, fh, indent=1)
+        return out
     per, tot = _davis_summary(cat_j, cat_f, skip_ends)
     cat_iou = {c: _nanmean(cat_j[c]) for c in cat_j}
     out = {"mask_key": mask_key, "threshold": threshold, "crop": crop, "bound_th": bound_th, "skip_ends": bool(skip_ends),
@@ -507,6 +586,8 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             out["sequences"][c]["components_mean"] = cat_nc[c]
     if crf is not None:
         out["crf"] = crf
+    if overlay is not None:
+        out["overlay"] = overlay
     if verbose:
         print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
         _print_davis_table(per, tot)
@@ -520,6 +601,8 @@ def frame_lists_from_reader(flags):
     test_inputs visits a category's frames; categories named as evaluate_masks names them (fname.split("/")[-2])."""
     from .cli import _reader
     rd = _reader(flags, 0, 1)
+    if flags.dataset == "FRAMES":  # no annotations: (image, None)
+        return {str(seq[0]).split("/")[-2]: [(str(i), None) for i in seq] for seq in rd.get_filenames_list()[0]}
     if flags.dataset == "FBMS":
         pairs = [(t[0], t[2]) for t in rd.get_test_tuples(flags.test_partition, flags.test_temporal_shift)]
     else:

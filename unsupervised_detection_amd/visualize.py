@@ -4,6 +4,8 @@
                                                    models/adversarial_learner.py:269-272 when `mask` is given)
   overlay_mask(image, mask, out_hw=(384, 640))     test_generator.py:101-107 (postprocess_image / postprocess_mask, cv2.addWeighted,
                                                    cv2.resize)
+  overlay_native(images, masks, ...)               the same blend at every frame's own size for a ragged batch, without the resize, plus
+                                                   the mask's contour: what native_results writes with overlay=...
   grad_histograms(g, net) / bucket_limits()        tf.summary.histogram of every variable's gradient (adversarial_learner.py:284-289)
   postprocess_image / postprocess_mask             models/utils/general_utils.py:23-51 on host arrays (RGB order is kept)
   SummaryWriter(dir)                               the step_sum summaries of collect_summaries (:260-291) as plain files:
@@ -26,6 +28,7 @@ import torch
 from . import evaluation as _ev  # (declares udet_mask_stats)
 from . import weights as W
 from ._ffi import check, lib
+from .ragged import PackedLayout, PackedSamples, as_layout, require_tensor
 
 N_BUCKETS = 1551  # UDET_HISTOGRAM_BUCKETS
 DES_HW = (384, 640)  # test_generator.py:14-15
@@ -84,6 +87,85 @@ def overlay_mask(image: torch.Tensor, mask: torch.Tensor, out_hw=DES_HW, thresho
     out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=image.device)
     check(lib.udet_overlay_mask(image.data_ptr(), mask.data_ptr(), st.data_ptr(), threshold, n, h, w, out.data_ptr(), oh, ow, _stream()))
     return out
+
+
+# ------------------------------------------------------------------------------------------- overlays at native size ----
+OVERLAY_MAX_EDGE = 8  # UDET_OVERLAY_MAX_EDGE
+OVERLAY_DEFAULTS = {"alpha": 0.5, "beta": 0.4, "colour": (0, 255, 0), "edge": 2, "edge_colour": (255, 255, 255)}
+
+
+def _rgb24(colour, name):
+    c = [int(v) for v in colour]
+    if len(c) != 3 or min(c) < 0 or max(c) > 255 or any(int(v) != v for v in colour):
+        raise ValueError("{} must be three integers in 0..255 (r, g, b)".format(name))
+    return (c[0] << 16) | (c[1] << 8) | c[2]
+
+
+def overlay_params(overlay=None):
+    """The parameters of overlay_native (a dict, or None for the defaults) with the defaults filled in and checked (ValueError):
+    alpha, beta finite and >= 0, edge an integer in 0..OVERLAY_MAX_EDGE, colour / edge_colour three integers in 0..255."""
+    p = dict(OVERLAY_DEFAULTS)
+    if overlay is not None:
+        if not isinstance(overlay, dict) or not set(overlay) <= set(OVERLAY_DEFAULTS):
+            raise ValueError("overlay must be a dict with keys among {}".format(sorted(OVERLAY_DEFAULTS)))
+        p.update({k: v for k, v in overlay.items() if v is not None})
+    p["alpha"], p["beta"] = float(p["alpha"]), float(p["beta"])
+    if not (0.0 <= p["alpha"] < float("inf") and 0.0 <= p["beta"] < float("inf")):
+        raise ValueError("overlay: alpha and beta must be finite and >= 0")
+    if int(p["edge"]) != p["edge"] or not 0 <= int(p["edge"]) <= OVERLAY_MAX_EDGE:
+        raise ValueError("overlay: edge must be an integer in 0..{}".format(OVERLAY_MAX_EDGE))
+    p["edge"] = int(p["edge"])
+    p["colour"], p["edge_colour"] = tuple(int(v) for v in p["colour"]), tuple(int(v) for v in p["edge_colour"])
+    _rgb24(p["colour"], "colour"), _rgb24(p["edge_colour"], "edge_colour")
+    return p
+
+
+class NativeOverlays(PackedSamples):
+    """Result of overlay_native: data (packed uint8 rgb, device) in the frames' own layout (three bytes per pixel)."""
+
+    def __init__(self, data, layout):
+        PackedSamples.__init__(self, layout, data.device)
+        self.data = data
+
+    def sample(self, i):
+        """[H_i, W_i, 3] uint8 view of sample i."""
+        return self._view(self.data, i)
+
+
+def overlay_native(images, masks, alpha=0.5, beta=0.4, colour=(0, 255, 0), edge=2, edge_colour=(255, 255, 255), out=None) -> NativeOverlays:
+    """Every mask of a ragged batch drawn on its own frame at the frame's own size, in one call of udet_overlay_native_ragged (one
+    launch whatever the batch): cv2.addWeighted(frame, alpha, mask painted `colour`, beta) -- with the defaults the picture of
+    test_generator.py:101-106 without its resize -- and, for edge >= 1, the mask's contour (the foreground pixels with a background pixel
+    of the frame within `edge` columns and rows) in edge_colour, unblended.  images: a RaggedBatch of rgb frames (or anything with its
+    data / offsets / hw); masks: anything that holds packed 0 / non-0 bytes of the same sizes in the same order at a third of the frames'
+    offsets -- a RestoredMasks (its binary masks), a ComponentSelection (its selected component), a GtBatch (its data).  out: a
+    caller-owned uint8 buffer of the frames' bytes that does not overlap the inputs (bytes between the samples stay as they are);
+    default: a fresh zeroed one.  Everything is validated on the host before the device is touched (ValueError)."""
+    p = overlay_params({"alpha": alpha, "beta": beta, "colour": colour, "edge": edge, "edge_colour": edge_colour})
+    frames = images.layout if hasattr(images, "layout") else PackedLayout(images.offsets, images.hw, images.data.numel(), 3, overlap_ok=True)
+    buf = next((b for b in (getattr(masks, k, None) for k in ("binary", "selected", "data")) if b is not None), None)
+    if buf is None:
+        raise ValueError("masks holds no packed binary buffer (binary, selected or data)")
+    total = int(require_tensor(buf, "masks (packed samples)", torch.uint8, 1, cuda=False).numel())
+    layout = masks.layout if hasattr(masks, "layout") else as_layout(masks.offsets, masks.hw, total)
+    if frames.c != 3 or not frames.same_as(layout, scale=3):
+        raise ValueError("the frames must be rgb and packed like the masks (their sizes, three times their offsets)")
+    as_layout(layout, None, total, max_samples=65535)
+    dev = buf.device
+    require_tensor(buf, "masks (packed samples)", torch.uint8, 1)
+    require_tensor(images.data, "images (rgb, packed like the masks)", torch.uint8, 1, 3 * total, dev)
+    if out is None:
+        out = torch.zeros(3 * total, dtype=torch.uint8, device=dev)
+    else:
+        require_tensor(out, "out", torch.uint8, 1, 3 * total, dev)
+        for t in (images.data, buf):
+            if out.data_ptr() < t.data_ptr() + t.numel() and t.data_ptr() < out.data_ptr() + out.numel():
+                raise ValueError("out must not overlap the frames or the masks")
+    d_off, d_hw = layout.device_tables(dev)
+    check(lib.udet_overlay_native_ragged(images.data.data_ptr(), buf.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.max_h,
+                                         layout.max_w, total, p["alpha"], p["beta"], _rgb24(p["colour"], "colour"), p["edge"],
+                                         _rgb24(p["edge_colour"], "edge_colour"), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return NativeOverlays(out, frames)
 
 
 # ------------------------------------------------------------------------------------------------------- histograms ----
