@@ -17,6 +17,11 @@ void udet_debug_force_conv(int bm, int bn, int ks);
 /* fp16 multiplication (fp32 accumulation) in the single-operator convolution entry points; plans take it from
  * udet_config.conv_fp16.  Process-global state: tests only. */
 void udet_debug_conv_fp16(int on);
+/* while that hook is on and s > 0: the single-operator backward-data launches scale their gradient operand dy by s on the fp16
+ * conversion (f16_xscale = s) and the backward-filter launches theirs (f16_yscale = s; udet_debug_conv2d_backward_filter_ex included),
+ * and divide the fp32 accumulators by it -- what a plan does with 4096.  Forward and transposed-forward launches keep scale 1;
+ * s <= 0 restores the default (scale 1 everywhere).  Plans are untouched.  Process-global state: tests only. */
+void udet_debug_conv_fp16_grad_scale(float s);
 /* while on, the first single-op launch of every distinct problem shape times its candidate configurations and caches the winner
  * (what udet_autotune does for a plan); tools/conv_bench.py / wgrad_bench.py use it to measure the tuned kernels stand-alone */
 /* filter gradient: nsplit > 0 pins the number of pixel slices (clamped to the workspace capacity), dma = 0 / 1 / 2 the staging variant

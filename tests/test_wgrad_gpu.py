@@ -7,7 +7,16 @@ with the oracle's conv2d_same / resize_nearest_align_corners, computed once per 
   (ii)  every output within 2e-4 * max(1, max|ref|) of the reference (the project's filter-gradient rule; dgamma / dbeta too),
   (iii) every output within 1e-4 * max(1, max|ref|) of the heuristic configuration's result on the same data,
   (iv)  bit-identical outputs of two runs (fixed summation orders),
-and that nothing was written outside the outputs (NaN guards on both sides)."""
+and that nothing was written outside the outputs (NaN guards on both sides).
+
+The fp16 mode of the same machinery (`f16` = the gradient scale; section g): fp16 hook on, udet_debug_conv_fp16_grad_scale set, operands drawn
+as U[0.25, 1] * scale with a random sign, and (ii) made against the float64 result of the operands ROUNDED as the kernel rounds them (see
+tests/test_fp16_kernels_gpu.py) at the same 2e-4.  In every form -- plain, operand-swapped, fused NN x2, BN-folded (fused or separate
+finalisation) and class-structured -- the GEMM of conv_wgrad_dma_kernel multiplies x and dy AS PASSED (gamma * c is applied to the fp32 sums by
+the reduction / finalisation, the class-structured form's dy is the caller's dU, read on its parity sub-lattices), so exactly x and dy are
+rounded, dy under the scale, whichever GEMM side it sits on.  db and dbeta are fp32 column sums of the unrounded dy; dgamma is formed from the
+GEMM's dW (the dot with w), so it follows the rounded operands.  The unit of the bounds is the magnitude of dy (1, or 1e-6 under scale 4096:
+the operation is linear in dy), not 1."""
 import ctypes
 import functools
 
@@ -17,6 +26,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import oracle_torch as O  # noqa: E402
+from test_fp16_kernels_gpu import mag, r16  # noqa: E402
 
 BN_C = float(O.BN_SCALE)
 ACT = {"none": 0, "leaky": 1, "elu": 2}
@@ -34,6 +44,8 @@ def dbg():
         yield _dbg
     finally:
         _dbg.udet_debug_force_wgrad(0, -1)
+        _dbg.udet_debug_conv_fp16_grad_scale(0.0)
+        _dbg.udet_debug_conv_fp16(0)
 
 
 def case(n, h, w, cin, cout, k, s=1, d=1, act="none", alpha=0.0, bn=False):
@@ -51,26 +63,51 @@ def r4(v):
 
 
 # ---- reference (once per case) ----------------------------------------------------------------------------------------------------
+def dy_unit(f16):
+    """magnitude of dy in fp16 mode: order 1 at scale 1, 1e-6 (subnormal / flushed by an unscaled fp16 conversion) under a real scale"""
+    return 1.0 if f16 in (0.0, 1.0) else 1e-6
+
+
 @functools.lru_cache(maxsize=None)
-def reference(c, up):
+def reference(c, up, f16=0.0):
+    """f16 = 0: the fp32 mode.  f16 > 0 (the gradient scale): `ref` is what the launch must produce -- from the rounded x / dy where the
+    dispatch rules run the fp16 kernel (no act' on load), from the unrounded ones where they keep fp32 -- and ins["alt_dw"] the other dW"""
     n, h, w, cin, cout, k, s, d, act, alpha, bn = c
-    x = rnd(n, h, w, cin, seed=101).double()
+    x = (mag(n, h, w, cin, seed=101) if f16 else rnd(n, h, w, cin, seed=101)).double()
     wt = rnd(k, k, cin, cout, seed=102, scale=(2.0 / (k * k * cin)) ** 0.5).double().requires_grad_(True)
     b = rnd(cout, seed=103, scale=0.1).double().requires_grad_(True)
     gamma = (1.0 + 0.3 * rnd(cout, seed=104)).double().requires_grad_(True)
     beta = rnd(cout, seed=105, scale=0.1).double().requires_grad_(True)
-    xu = O.resize_nearest_align_corners(x, 2 * h, 2 * w) if up else x
-    y = O.conv2d_same(xu, wt, b, s, d)
-    if bn:
-        y = gamma * BN_C * y + beta
-    a = O.leaky_relu(y, alpha) if act == "leaky" else (torch.nn.functional.elu(y) if act == "elu" else y)
-    dy = rnd(*y.shape, seed=106).double()
     leaves = [wt, b, gamma, beta] if bn else [wt, b]
-    g = [t.float() for t in torch.autograd.grad((a * dy).sum(), leaves)]
-    ref = dict(zip(("dw", "db", "dgamma", "dbeta"), g))
-    ref["dw"] = ref["dw"].reshape(-1)
-    ins = dict(x=x.float(), dy=dy.float(), ya=a.detach().float() if act != "none" else None, w=wt.detach().float(), b=b.detach().float(),
+
+    def forward(xs):
+        xu = O.resize_nearest_align_corners(xs, 2 * h, 2 * w) if up else xs
+        y = O.conv2d_same(xu, wt, b, s, d)
+        if bn:
+            y = gamma * BN_C * y + beta
+        return O.leaky_relu(y, alpha) if act == "leaky" else (torch.nn.functional.elu(y) if act == "elu" else y)
+
+    def grads(xs, dys):
+        g = [t.float() for t in torch.autograd.grad((forward(xs) * dys).sum(), leaves)]
+        r = dict(zip(("dw", "db", "dgamma", "dbeta"), g))
+        r["dw"] = r["dw"].reshape(-1)
+        return r
+
+    a = forward(x).detach()
+    dy = (mag(*a.shape, seed=106, scale=dy_unit(f16)) if f16 else rnd(*a.shape, seed=106)).double()
+    ref = grads(x, dy)
+    ins = dict(x=x.float(), dy=dy.float(), ya=a.float() if act != "none" else None, w=wt.detach().float(), b=b.detach().float(),
                gamma=gamma.detach().float())
+    if f16:
+        rounded = grads(r16(x.float()), r16(dy.float(), f16))
+        ins["dgamma_u"] = ref.get("dgamma")
+        if act == "none":  # the fp16 kernel runs
+            ins["alt_dw"] = ref["dw"]
+            ref["dw"] = rounded["dw"]
+            if bn:
+                ref["dgamma"] = rounded["dgamma"]
+        else:
+            ins["alt_dw"] = rounded["dw"]
     return ins, ref
 
 
@@ -107,7 +144,7 @@ def dispatch(c, mode):
     return dict(T=T if mode != 2 else 9, ntaps=ntaps, swap=swap, mreal=mreal, total=(mreal + 1) * g_cout, g_cout=g_cout,
                 cap=max(1, nchunks // 2), fixed=(1024 * cout + 15) // 16 * 16, per_split=(4 if mode == 2 else 1) * ldn + m_tiles * 128 * ldn,
                 reserve=16 * cin * cout + 64 * cout + 1024 if mode == 2 else 0, fused=fused, separate=bn and not fused,
-                classes=mode == 2, dma_ok=act == "none")
+                classes=mode == 2, dma_ok=act == "none", tile_n=tile_n)
 
 
 def reduce_word(g, ns, cout):
@@ -161,10 +198,10 @@ def place(t, ld, coff, seed):
     return buf.cuda(), buf.shape[-1], coff
 
 
-def operands(c, up, win):
-    key = (c, up, win)
+def operands(c, up, win, f16=0.0):
+    key = (c, up, win, f16)
     if key not in _dev:
-        ins, _ = reference(c, up)
+        ins, _ = reference(c, up, f16)
         ldx, xo, ldy, yo = win if win else (None, 0, None, 0)
         x, ldx, xo = place(ins["x"], ldx, xo, 201)
         dy, ldy, yo = place(ins["dy"], ldy, yo, 202)
@@ -174,11 +211,11 @@ def operands(c, up, win):
     return _dev[key]
 
 
-def launch(dbg, c, mode, win=None):
+def launch(dbg, c, mode, win=None, f16=0.0):
     """one call of the hook; outputs as CPU tensors with their NaN guards still attached"""
     n, h, w, cin, cout, k, s, d, act, alpha, bn = c
     g = dispatch(c, mode)
-    op = operands(c, mode != 0, win)
+    op = operands(c, mode != 0, win, f16)
     floats = 64 + g["fixed"] + g["per_split"] * g["cap"] + g["reserve"]  # every split count up to the cap fits
     ws = workspace(floats)
     sizes = dict(dw=g["T"] * cin * cout, db=cout, dgamma=cout, dbeta=cout)
@@ -201,24 +238,37 @@ def inner(t):
     return t[GUARD:-GUARD]
 
 
-def sweep(dbg, c, mode, variants, splits, win=None):
-    """assertions (i)-(iv) and the guards for every (variant, split count); returns {(variant, asked): (outputs, reduce word)}"""
+WORST_F16 = {"dw": 0.0}  # fp16 mode: worst dW error against the rounded-operand reference, relative to the tensor's scale
+
+
+def sweep(dbg, c, mode, variants, splits, win=None, f16=0.0):
+    """assertions (i)-(iv) and the guards for every (variant, split count); returns {(variant, asked): (outputs, reduce word)}.
+    f16 > 0: the same in fp16 mode under that gradient scale (see the module docstring)"""
     cout = c[4]
     g = dispatch(c, mode)
-    _, ref = reference(c, mode != 0)
-    scale = {nm: max(1.0, float(r.abs().max())) for nm, r in ref.items()}
+    ins, ref = reference(c, mode != 0, f16)
+    unit = dy_unit(f16)
+    scale = {nm: max(unit, float(r.abs().max())) for nm, r in ref.items()}
     dbg.udet_debug_force_wgrad(0, -1)
-    heur, _ = launch(dbg, c, mode, win)
     results = {}
     try:
+        dbg.udet_debug_conv_fp16(1 if f16 else 0)
+        dbg.udet_debug_conv_fp16_grad_scale(f16)
+        heur, (hcfg, _) = launch(dbg, c, mode, win, f16)
+        if f16:  # the built-in choice of an fp16 launch is the LDS-DMA kernel wherever it can run
+            assert hcfg >> 20 == (1 if g["dma_ok"] else 0), hex(hcfg)
         for v in variants:
             for asked in splits:
-                tag = f"variant {v}, {asked} splits"
+                tag = f"variant {v}, {asked} splits" + (f", fp16 scale {f16:g}" if f16 else "")
                 dbg.udet_debug_force_wgrad(asked, v)
-                out, (cfg, red) = launch(dbg, c, mode, win)
-                again, words2 = launch(dbg, c, mode, win)
+                out, (cfg, red) = launch(dbg, c, mode, win, f16)
+                again, words2 = launch(dbg, c, mode, win, f16)
                 ns = min(asked, g["cap"])
                 want_v = v if g["dma_ok"] else 0  # act' on load lives in the register-staged kernel only
+                if f16 and g["dma_ok"]:
+                    want_v = 1  # the one fp16 kernel: variants 0 / 3 multiply in fp32 only, variant 2 has no fp16 instantiation
+                elif f16 and v == 3:
+                    want_v = 0
                 assert cfg == ns | want_v << 20, (tag, hex(cfg))                                                   # (i)
                 assert red == reduce_word(g, ns, cout), (tag, hex(red), hex(reduce_word(g, ns, cout)))
                 assert words2 == (cfg, red)
@@ -227,12 +277,27 @@ def sweep(dbg, c, mode, variants, splits, win=None):
                     assert torch.isnan(o[:GUARD]).all() and torch.isnan(o[-GUARD:]).all(), (tag, nm, "guard overwritten")
                     assert torch.isfinite(inner(o)).all(), (tag, nm)
                     err, dh = float((inner(o) - r).abs().max()), float((inner(o) - inner(heur[nm])).abs().max())
+                    if f16:
+                        print("%s %s: %.2e of the scale against the reference" % (tag, nm, err / scale[nm]))
                     assert err < 2e-4 * scale[nm], (tag, nm, "against the reference", err, scale[nm])  # (ii)
                     assert dh < 1e-4 * scale[nm], (tag, nm, "against the heuristic configuration", dh, scale[nm])  # (iii)
                     assert torch.equal(inner(o), inner(again[nm])), (tag, nm, "two runs differ")               # (iv)
+                if f16:
+                    # fp16 arithmetic ran (the unrounded operands' dW is at least 10x further away than the rounded operands'), or -- a
+                    # launch the rules keep in fp32 -- provably did not; dgamma also within the fp32-mode bound of the unrounded value
+                    e_ref = float((inner(out["dw"]) - ref["dw"]).abs().max())
+                    e_alt = float((inner(out["dw"]) - ins["alt_dw"]).abs().max())
+                    assert e_alt > 0 and e_alt >= 10 * e_ref, (tag, "fp16 arithmetic ran" if g["dma_ok"] else "stayed fp32", e_ref, e_alt)
+                    if g["dma_ok"]:
+                        WORST_F16["dw"] = max(WORST_F16["dw"], e_ref / scale["dw"])
+                    if "dgamma" in ref:
+                        du = ins["dgamma_u"]
+                        assert float((inner(out["dgamma"]) - du).abs().max()) < 2e-4 * max(1.0, float(du.abs().max())), (tag, "dgamma")
                 results[(v, asked)] = (out, red)
     finally:
         dbg.udet_debug_force_wgrad(0, -1)
+        dbg.udet_debug_conv_fp16_grad_scale(0.0)
+        dbg.udet_debug_conv_fp16(0)
     for nm, r in ref.items():  # the heuristic configuration itself
         assert float((inner(heur[nm]) - r).abs().max()) < 2e-4 * scale[nm], ("heuristic", nm)
     return results
@@ -378,3 +443,78 @@ def test_channel_windows(dbg, name):
     res = sweep(dbg, c, mode, variants, splits, win)
     (_, red0), = tight.values()
     assert all(red == red0 for _, red in res.values())
+
+
+# ---- g) the fp16 kernel (conv_wgrad_dma_kernel<..., 2, true>) in every view ----------------------------------------------------------------
+F16_SCALE = 4096.0  # what the plans use; dy = 1e-6 * U[0.25, 1]: an unscaled fp16 conversion would be subnormal or flush
+
+
+@pytest.fixture(scope="module", autouse=True)
+def worst_fp16_line():
+    yield
+    print("\nfp16 backward-filter against the rounded-operand reference, worst error relative to the tensor's scale: %.2e (bound 2e-4)"
+          % WORST_F16["dw"])
+
+
+def test_fp16_plain_cases_reach_every_tile():
+    """wgrad_launch<128, 128>, <128, 64> and <128, 32>: every (BM, BN) launch_wgrad_T can pick"""
+    assert {dispatch(c, mode)["tile_n"] for c, mode in PLAIN.values() if dispatch(c, mode)["dma_ok"]} == {32, 64, 128}
+
+
+@pytest.mark.parametrize("name", list(PLAIN))
+def test_fp16_direct_variant_and_split_counts(dbg, name):
+    """every PLAIN case (both swapped views and the fused NN x2 loader among them) on the LDS-DMA variant in fp16, scale 4096; `leaky` and
+    `elu` pass act' on load, are not dma_ok and must stay fp32: they meet the UNROUNDED reference, and the rounded one 10x worse"""
+    c, mode = PLAIN[name]
+    g = dispatch(c, mode)
+    assert g["dma_ok"] == (name not in ("leaky", "elu"))
+    res = sweep(dbg, c, mode, (1,), (1, 2, 3, 7, ALL), f16=F16_SCALE)
+    for out, red in res.values():
+        assert bool(red & SWAPPED) == name.startswith("swapped") and (red >> 8) & 0xff == 0 and not red & (FUSED_BN | SEPARATE_BN | CLASSES)
+
+
+def test_fp16_plain_case_at_scale_1(dbg):
+    c, mode = PLAIN["bn64"]
+    sweep(dbg, c, mode, (1,), (1, 3, ALL), f16=1.0)
+
+
+@pytest.mark.parametrize("c,splits", [(case(1, 12, 20, 128, 64, 3, bn=True), (1, 4)), (case(2, 7, 9, 64, 32, 3, bn=True), (1, 2))])
+def test_fp16_class_structured_up_form(dbg, c, splits):
+    res = sweep(dbg, c, 2, (1,), splits, f16=F16_SCALE)
+    for out, red in res.values():
+        assert red & CLASSES and red & SEPARATE_BN and not red & (FUSED_BN | SWAPPED) and (red >> 8) & 0xff == 0
+    (o1, red1), = sweep(dbg, c, 1, (1,), (splits[-1],), f16=F16_SCALE).values()  # the fused NN x2 loader with the fused BN reduction
+    assert red1 & FUSED_BN and not red1 & CLASSES
+    _, ref = reference(c, True, F16_SCALE)
+    for out, _ in res.values():
+        for nm, r in ref.items():
+            assert float((inner(out[nm]) - inner(o1[nm])).abs().max()) < 1e-4 * max(dy_unit(F16_SCALE), float(r.abs().max())), nm
+
+
+def test_fp16_fused_bn_reduction(dbg):
+    c, table, _ = FUSED[1]
+    for (v, asked), (_, red) in sweep(dbg, c, 0, (1,), tuple(table), f16=F16_SCALE).items():
+        assert red & FUSED_BN and ((red >> 8) & 0xff, red & 0xff) == table[asked]
+
+
+def test_fp16_separate_bn_form_swapped(dbg):
+    c = SEPARATE["swapped"]
+    for out, red in sweep(dbg, c, 0, (1,), (1, 3, ALL), f16=F16_SCALE).values():
+        assert red & SEPARATE_BN and red & SWAPPED and not red & (FUSED_BN | CLASSES)
+
+
+def test_fp16_channel_window(dbg):
+    c, mode, _, splits, win = WINDOWS["plain"]
+    tight = sweep(dbg, c, mode, (1,), splits, f16=F16_SCALE)
+    res = sweep(dbg, c, mode, (1,), splits, win, f16=F16_SCALE)
+    (_, red0), = tight.values()
+    assert all(red == red0 for _, red in res.values())
+
+
+def test_fp16_forced_variants_without_an_fp16_form_run_the_dma_kernel(dbg):
+    """every configuration of an fp16 launch multiplies alike.  The Winograd-domain family (3; wgrad_wino_ok) and the register-staged kernel
+    (0) multiply in fp32 only and the three-stage ring (2) has no fp16 instantiation: forced on a shape that takes all of them in fp32 mode,
+    the fp16 launch runs conv_wgrad_dma_kernel<..., 2, true> and the report word says variant 1 (sweep asserts it, and that fp16
+    arithmetic ran)"""
+    c = case(2, 24, 48, 64, 64, 3)
+    sweep(dbg, c, 0, (0, 2, 3), (4,), f16=F16_SCALE)

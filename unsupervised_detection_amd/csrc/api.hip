@@ -292,6 +292,7 @@ int udet_conv2d_backward_data(const float* dy, const float* y_saved, const float
     if (!conv_setup_dgrad(p, cls, n, h, w, kh, kw, stride, dilation)) continue;
     p.x = dyin; p.ldx = ldy; p.xa = yain; p.xact = act; p.xalpha = alpha;
     p.wp = wp; p.Kc = kc; p.ldw = ldw; p.kreal = cout;
+    p.f16_xscale = conv_debug_f16_grad_scale_now();  // (test hook; 0: none -- the x operand of this launch is a gradient)
     p.y = dx; p.ldy = cin; p.Cout = cin;
     p.partial = part; p.partial_cap = SPLITK_FLOATS;
     p.zero16 = zero;
@@ -357,6 +358,7 @@ int udet_conv2d_backward_filter(const float* x, const float* dy, const float* y_
   memcpy(p.taps, g.taps, sizeof(g.taps));
   p.dw = dw_hwio; p.db = dbias; p.partial = part; p.partial_floats = takef;
   p.zero16 = zero;
+  p.f16_yscale = conv_debug_f16_grad_scale_now();  // (test hook; 0: none)
   return launch_wgrad_T(p, kh * kw, stream);
 }
 

@@ -28,6 +28,10 @@ int launch_wino_pack(const float* src, float* dst, int R, int C, int Kc, int np,
 int launch_wino_from_packed(const ConvParams& p, float* dst, int np, hipStream_t stream);
 void conv_debug_f16(int on);  // fp16 multiplication in the single-operator launches (plans carry udet_config.conv_fp16)
 int conv_debug_f16_on();
+// gradient-operand scale of the single-operator backward launches while that hook is on (plans set theirs in plan_exec.hip); s <= 0: none.
+// conv_debug_f16_grad_scale_now(): the value such a launch takes -- s while the fp16 hook is on and s > 0, else 0 ("not set": scale 1)
+void conv_debug_f16_grad_scale(float s);
+float conv_debug_f16_grad_scale_now();
 int conv_last_config();  // family | bm field << 8 | split count << 20 | ... of the most recent launch (conv_select.hip; udet_debug_last_conv)
 void conv_set_tuning(int on);   // autotuner: while on, unseen problem shapes are timed and the best configuration cached
 // the tuning caches (conv_tune.hip): entries in all three, their text form (the lines behind udet_tune_save's header), one line back in

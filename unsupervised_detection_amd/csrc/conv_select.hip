@@ -117,6 +117,9 @@ static ConvCfg runnable_cfg(const ConvParams& p, ConvCfg c) {
   // LDS-DMA staging only where the launch allows it, self-staging only on its tiles
   if (stages_by_dma(c.family) && !dma_ok(p)) c.family = FAM_WAVE_SPEC;
   if (c.family == FAM_SELF_STAGING && !conv_self_staging_tile(c.bm, c.bn)) c.family = FAM_DMA2;
+  // every configuration of an fp16 launch multiplies alike: the register-staged families have no fp16 form, so where
+  // the launcher itself would multiply in fp16 (heuristic_cfg) such an entry runs the LDS-DMA kernel on the same tile and split
+  if (p.f16 && dma_ok(p) && (c.family == FAM_PLAIN || c.family == FAM_WAVE_SPEC)) c.family = FAM_DMA2;
   // eligibility of the families that take only some launches; the direct kernels multiply in fp32 only
   if (is_direct(c.family) && (p.f16 || !(c.family == FAM_THIN_K ? conv_thin_k_ok(p) : conv_thin_n_ok(p)))) return heuristic_cfg(p);
   if (c.family == FAM_TILE && !tile_ok(p, c.tile_height(), c.tile_channels())) return heuristic_cfg(p);
@@ -189,6 +192,9 @@ static void apply_forced(ConvParams& p, ConvCfg& c, hipStream_t stream) {
 static int g_debug_f16 = 0;  // test hook: fp16 multiplication for the single-operator entry points too
 void conv_debug_f16(int on) { g_debug_f16 = on; }
 int conv_debug_f16_on() { return g_debug_f16; }
+static float g_debug_f16_grad_scale = 0.f;  // test hook: what the single-operator backward launches scale their gradient operand by
+void conv_debug_f16_grad_scale(float s) { g_debug_f16_grad_scale = s > 0.f ? s : 0.f; }
+float conv_debug_f16_grad_scale_now() { return g_debug_f16 ? g_debug_f16_grad_scale : 0.f; }
 // argument checks + the derived fields every kernel family reads (Mall, fast divisors, uniform-cursor flags, segment rows)
 static int conv_prepare(ConvParams& p) {
   if (g_debug_f16) p.f16 = 1;

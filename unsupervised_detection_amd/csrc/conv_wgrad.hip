@@ -815,6 +815,9 @@ int launch_wgrad_T(WgradParams& p, int T, hipStream_t stream) {
   }
   if ((nsplit >> 20) == 3 && !wino_ok) nsplit = (nsplit & 0xfffff) | ((dma_ok ? 1 : 0) << 20);  // (a cached entry of another build's rules)
   if ((nsplit >> 20) == 3) nsplit = wgrad_wino_slices(g, (nsplit & 0xfffff) > (int)maxs ? (int)maxs : (nsplit & 0xfffff)) | (3 << 20);
+  // every configuration of an fp16 launch multiplies alike: the fp16 kernel is the two-stage LDS-DMA one, so a forced or file-loaded
+  // variant 0 (register-staged, fp32 only) or 2 (no fp16 instantiation) runs and reports variant 1 where the launch allows it
+  if (p.f16 && dma_ok && (nsplit >> 20) != 1) nsplit = (nsplit & 0xfffff) | (1 << 20);
   g_wlast = nsplit;
   UDET_TRY(run(nsplit));
   UDET_HIP(hipGetLastError());

@@ -13,6 +13,7 @@ extern "C" {
 int udet_debug_last_conv(void) { return conv_last_config(); }
 void udet_debug_force_conv(int bm, int bn, int ks) { conv_force_config(bm, bn, ks); }
 void udet_debug_conv_fp16(int on) { conv_debug_f16(on); }
+void udet_debug_conv_fp16_grad_scale(float s) { conv_debug_f16_grad_scale(s); }
 void udet_debug_force_wgrad(int nsplit, int dma) { wgrad_force(nsplit, dma); }
 int udet_debug_last_wgrad(void) { return wgrad_last_config(); }
 int udet_debug_last_wgrad_reduce(void) { return wgrad_last_reduce(); }
@@ -59,6 +60,7 @@ int udet_debug_conv2d_backward_filter_ex(const float* x, int ldx, int x_coff, co
   p.dw = dw; p.db = db;
   p.partial = zero + 64; p.partial_floats = workspace_bytes / sizeof(float) - 64;
   p.zero16 = zero;
+  p.f16_yscale = conv_debug_f16_grad_scale_now();  // (udet_debug_conv_fp16_grad_scale; 0: none)
   if (gamma) { p.w = w; p.b = b; p.gamma = gamma; p.dgamma = dgamma; p.dbeta = dbeta; p.bn_c = bn_c; }
   ConvParams g;
   memset(&g, 0, sizeof(g));
