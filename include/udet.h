@@ -169,6 +169,42 @@ int udet_select_components_ragged(const unsigned char* binary, const unsigned ch
                                   int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
                                   unsigned char* selected, long long* info, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Every connected component of a ragged batch as a scored box: the detections at native size.  labels: the packed device
+ * int32 buffer udet_select_components_ragged writes (mode UDET_COMPONENTS_LABEL, or any mode with `labels`): root + 1 on every foreground
+ * pixel, root = the smallest row-major index of its component, 0 on background; a value outside 0..H_i*W_i is background, so no label
+ * indexes outside its sample.  score: optional device uint8, packed like labels (the restored soft bytes).  offsets / hw / max_h / max_w
+ * / total_pixels as for udet_select_components_ragged.  Per sample, in exact integers, for every component: area; the box y0, x0
+ * (inclusive minima) and y1, x1 (exclusive: maxima + 1, the `stop` of scipy.ndimage.find_objects' slices); sum_y and sum_x over its
+ * pixels (the numerators of the centroid); score_sum, the sum of its score bytes (0 without score).  The components with area >=
+ * min_area are kept and ranked by area, descending, ties to the smaller root (UDET_COMPONENTS_LARGEST's order); the first min(kept, k)
+ * go to dets[i][rank][0..8] (device int64 [n][k][UDET_DET_FIELDS]), every other row holds root = -1 and zeros.  counts: device int64
+ * [n][3] = {components, kept, rows written}.  Four launches whatever n and the number of components: zero the counters; area per root
+ * (one integer atomic per horizontal run of a wave) and the list of kept roots; one workgroup per sample picks the k winners in k
+ * rounds; box / sums of the winners (per-workgroup partials in LDS, then one 64-bit integer atomic per touched value).  No host round
+ * trip, no workgroup waits for another, no float atomics: identical from run to run and for a sample alone or inside a batch.
+ * workspace: udet_component_boxes_workspace_bytes(total_pixels, n, k) bytes (8 per pixel + 8 per sample), 8-byte aligned.
+ * UDET_ERR_ARG, nothing enqueued: NULL labels / offsets / hw / dets / counts, n outside 1..65535, max_h or max_w < 1, total_pixels < 1,
+ * k outside 1..UDET_DET_MAX_K, min_area < 1, a short or misaligned workspace, labels not 4-byte or dets / counts not 8-byte aligned.  The
+ * tables are device memory: the host caller validates them before the launch (native_results.check_component_tables). */
+#define UDET_DET_FIELDS 9   /* root, area, y0, x0, y1, x1, sum_y, sum_x, score_sum */
+#define UDET_DET_MAX_K 64
+size_t udet_component_boxes_workspace_bytes(size_t total_pixels, int n, int k);
+int udet_component_boxes_ragged(const int* labels, const unsigned char* score, int n, const long long* offsets, const int* hw,
+                                int max_h, int max_w, size_t total_pixels, int min_area, int k,
+                                long long* dets, long long* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The frames of the written detections painted onto packed rgb frames, in place: image_rgb is device uint8, sample i = H_i x W_i x 3
+ * bytes at byte 3 * offsets[i] (the contract of udet_overlay_native_ragged); dets / counts / k: what udet_component_boxes_ragged wrote,
+ * read on the device.  A pixel (y, x) of a box [y0, y1) x [x0, x1) is painted rgb (0xRRGGBB) when y < y0 + t, y >= y1 - t, x < x0 + t or
+ * x >= x1 - t, t = thickness in 1..UDET_DRAW_MAX_THICKNESS: the line goes inward (nothing is drawn outside the box), a box narrower
+ * than 2 t is filled.  One colour per call, so overlapping boxes write equal bytes and the result does not depend on order; every
+ * other byte is untouched.  One launch, one workgroup per (row, sample); a box is clipped to its frame and the row count to k, so
+ * nothing is written outside a sample whatever dets and counts hold.  UDET_ERR_ARG, nothing enqueued: a NULL pointer, n outside
+ * 1..65535, total_pixels < 1, k outside 1..UDET_DET_MAX_K, thickness outside 1..8, rgb above 0xffffff, misaligned dets / counts. */
+#define UDET_DRAW_MAX_THICKNESS 8
+int udet_draw_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
+                           const long long* dets, const long long* counts, int k, int thickness, unsigned rgb, void* stream);
+
 /* Dense CRF of a ragged batch at each frame's own size: step 2 of post_processing/crf_refine.py:65-108 run_crf_original_resolution
  * (DenseCRF2D + setUnaryEnergy + addPairwiseBilateral(sxy, srgb, rgbim, compat) + inference(iters) on the untouched frame).  Packed
  * layout of the two calls above: sample i = H_i x W_i elements at element offset offsets[i] (device int64 [n]); hw: device int32 [n][2].

@@ -76,6 +76,10 @@ sig("udet_flow_to_image_workspace_bytes", c_sz, c_i)
 sig("udet_flow_to_image", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_p, c_sz, c_p)
 sig("udet_overlay_mask", c_i, c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_p, c_i, c_i, c_p)
 sig("udet_overlay_native_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_f, c_f, ctypes.c_uint, c_i, ctypes.c_uint, c_p, c_p)
+# detections at native size (native_results.component_boxes, visualize.draw_boxes)
+sig("udet_component_boxes_workspace_bytes", c_sz, c_sz, c_i, c_i)
+sig("udet_component_boxes_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_draw_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_i, ctypes.c_uint, c_p)
 sig("udet_histogram_limits", c_i, c_p, c_i)
 sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
 sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)

@@ -13,11 +13,13 @@
                                                       [--crf_radius R]                                      (crf_refine.py:65-108)
                                                       [--overlay] [--overlay_edge 2] [--overlay_alpha 0.5] [--overlay_beta 0.4]
                                                       [--overlay_colour 0,255,0] [--overlay_edge_colour 255,255,255]   (test_generator.py:101-106)
+                                                      [--detections] [--det_min_area 64] [--det_max 16]     (no reference script)
+                                                      [--overlay_boxes] [--overlay_box_thickness 2] [--overlay_box_colour 255,255,0]
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
                                                       [--sxy 25] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_batch 16] [--flow_batch 8]
                                                       [--score_batch 0]
                                                       [--benchmark --dataset ... --root_dir ... [--native_sxy 60] [--component best_gt]
-                                                       [--overlay ...]]
+                                                       [--overlay ...] [--detections ...] [--overlay_boxes ...]]
                                                                                                             (post_processing.py)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
@@ -58,7 +60,12 @@ nothing and reports frames / foreground_mean per sequence; --component best_gt i
 keeps pred_mask as run_crf's candidate, what the reference's rule picks on its black fake annotation).  With --overlay (restore_results,
 test_generator --native_resolution, post_process --benchmark; any dataset) every frame's final mask is also drawn on the untouched frame
 at its own size -- blended --overlay_alpha / --overlay_beta in --overlay_colour, its contour --overlay_edge pixels wide (0..8, 0: none)
-in --overlay_edge_colour -- into <out>/overlay/<sequence>/<frame>.png (visualize.overlay_native, one kernel launch per batch).  Like the
+in --overlay_edge_colour -- into <out>/overlay/<sequence>/<frame>.png (visualize.overlay_native, one kernel launch per batch).  With
+--detections (the same three commands) every connected component (--connectivity) of at least --det_min_area pixels of a frame's mask --
+after the CRF, before --component -- is reported as a box, the largest first, at most --det_max (1..64) per frame: box [x0, y0, x1, y1],
+area, centroid, score (the mean restored soft mask over the component) and root, in <out>/detections/<sequence>.json
+(native_results.component_boxes).  --overlay_boxes (needs --overlay and --detections) also paints the boxes on the overlays,
+--overlay_box_thickness (1..8) pixels wide in --overlay_box_colour (visualize.draw_boxes).  Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
 runs)."""
@@ -152,19 +159,47 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--overlay_beta", type=float, default=0.4)
     ap.add_argument("--overlay_colour", default="0,255,0", help="r,g,b of the mask")
     ap.add_argument("--overlay_edge_colour", default="255,255,255", help="r,g,b of the contour")
+    ap.add_argument("--detections", action="store_true", help="report every connected component as a box: <out>/detections/<sequence>.json")
+    ap.add_argument("--det_min_area", type=int, default=64, help="the smallest component reported, in pixels")
+    ap.add_argument("--det_max", type=int, default=16, help="detections per frame, the largest first (1..64)")
+    ap.add_argument("--overlay_boxes", action="store_true", help="with --overlay and --detections: also paint the boxes on the overlays")
+    ap.add_argument("--overlay_box_thickness", type=int, default=2, help="width of a box's line in pixels, 1..8 (inward)")
+    ap.add_argument("--overlay_box_colour", default="255,255,0", help="r,g,b of the boxes")
 
 
 def _overlay(flags):
-    """--overlay and its parameters as restore_results_dir takes them: None without --overlay.  A bad value is a SystemExit."""
+    """--overlay and its parameters as restore_results_dir takes them: None without --overlay; with --overlay_boxes also "boxes".  A bad
+    value, or --overlay_boxes without --overlay and --detections, is a SystemExit."""
+    boxes = getattr(flags, "overlay_boxes", False)
+    if boxes and not (getattr(flags, "overlay", False) and getattr(flags, "detections", False)):
+        raise SystemExit("--overlay_boxes paints the detections on the overlays: it needs --overlay and --detections")
     if not getattr(flags, "overlay", False):
         return None
-    from .visualize import overlay_params
+    from .visualize import box_params, overlay_params
     try:
         colour, edge_colour = ([int(v) for v in str(c).split(",")] for c in (flags.overlay_colour, flags.overlay_edge_colour))
-        return overlay_params({"alpha": flags.overlay_alpha, "beta": flags.overlay_beta, "colour": colour, "edge": flags.overlay_edge,
-                               "edge_colour": edge_colour})
+        p = overlay_params({"alpha": flags.overlay_alpha, "beta": flags.overlay_beta, "colour": colour, "edge": flags.overlay_edge,
+                            "edge_colour": edge_colour})
     except ValueError as e:
         raise SystemExit("--overlay: {} (--overlay_colour / --overlay_edge_colour are r,g,b)".format(e))
+    if boxes:
+        try:
+            p["boxes"] = box_params({"thickness": flags.overlay_box_thickness,
+                                     "colour": [int(v) for v in str(flags.overlay_box_colour).split(",")]})
+        except ValueError as e:
+            raise SystemExit("--overlay_boxes: {} (--overlay_box_colour is r,g,b)".format(e))
+    return p
+
+
+def _detections(flags):
+    """--detections and its parameters as restore_results_dir takes them: None without --detections.  A bad value is a SystemExit."""
+    if not getattr(flags, "detections", False):
+        return None
+    from .native_results import detection_params
+    try:
+        return detection_params({"min_area": flags.det_min_area, "max_detections": flags.det_max})
+    except ValueError as e:
+        raise SystemExit("--detections: {} (--det_min_area / --det_max)".format(e))
 
 
 def check_frames_component(flags):
@@ -218,6 +253,7 @@ def parse_restore_results_args(argv):
         setattr(flags, k, v)
     check_frames_component(flags)
     _overlay(flags)
+    _detections(flags)
     return flags
 
 
@@ -244,6 +280,7 @@ def parse_post_process_args(argv):
     ap.add_argument("--test_partition", default="val")
     ap.add_argument("--test_temporal_shift", type=int, default=1)
     ap.add_argument("--component", default="best_gt", choices=("none", "largest", "best_gt"))
+    ap.add_argument("--connectivity", type=int, default=8, choices=(4, 8))
     _add_overlay_arguments(ap)
     a = ap.parse_args(argv)
     if a.benchmark and not a.root_dir:
@@ -256,6 +293,7 @@ def parse_post_process_args(argv):
     if a.benchmark:
         check_frames_component(flags)
         _overlay(flags)
+        _detections(flags)
     return flags
 
 
@@ -300,10 +338,12 @@ def post_process(a):
     if a.benchmark:
         from .native_results import frame_lists_from_reader
         report["native_sxy"] = a.native_sxy
-        overlay = _overlay(a)
+        overlay, detections = _overlay(a), _detections(a)
+        more = {} if overlay is None else {"overlay": overlay}
+        if detections is not None:
+            more.update(detections=detections, connectivity=a.connectivity)
         report["benchmark"] = pp.run_crf_original_resolution(resized, frame_lists_from_reader(a), a.native_sxy, a.srgb, a.scomp, a.gauss_k,
-                                                             out_path=original, component=_component(a), gt_rule=a.dataset,
-                                                             **({} if overlay is None else {"overlay": overlay}))
+                                                             out_path=original, component=_component(a), gt_rule=a.dataset, **more)
     os.makedirs(a.out_dir, exist_ok=True)
     with open(os.path.join(a.out_dir, "post_process.json"), "w") as f:
         json.dump(report, f, indent=1)
@@ -335,6 +375,7 @@ def check_native_flags(flags):
     if getattr(flags, "native_resolution", False):
         check_frames_component(flags)
         _overlay(flags)
+        _detections(flags)
 
 
 def main(argv=None):
@@ -350,7 +391,7 @@ def main(argv=None):
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
                             batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
-                            crf=_crf(a), overlay=_overlay(a))
+                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -378,7 +419,8 @@ def main(argv=None):
             from .native_results import frame_lists_from_reader, restore_results_dir
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
-                                connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags))
+                                connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags),
+                                detections=_detections(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

@@ -54,6 +54,16 @@ _DEFS = [
     ("overlay_beta", float, 0.4),
     ("overlay_colour", str, "0,255,0"),
     ("overlay_edge_colour", str, "255,255,255"),
+    # not reference flags: with --native_resolution, --detections reports every connected component (--connectivity) of at least
+    # det_min_area pixels as a box, at most det_max (1..64) per frame, into D/native/detections/<sequence>.json
+    # (native_results.component_boxes); --overlay_boxes (with --overlay) paints them on the overlays, overlay_box_thickness (1..8) pixels
+    # wide in overlay_box_colour (r,g,b)
+    ("detections", bool, False),
+    ("det_min_area", int, 64),
+    ("det_max", int, 16),
+    ("overlay_boxes", bool, False),
+    ("overlay_box_thickness", int, 2),
+    ("overlay_box_colour", str, "255,255,0"),
 ]
 
 

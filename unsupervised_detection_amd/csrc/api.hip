@@ -165,6 +165,49 @@ int udet_select_components_ragged(const unsigned char* binary, const unsigned ch
                                          workspace, (hipStream_t)stream);
 }
 
+size_t udet_component_boxes_workspace_bytes(size_t total_pixels, int n, int k) {
+  return (n < 1 || total_pixels < 1 || k < 1 || k > UDET_DET_MAX_K) ? 0 : component_boxes_workspace_bytes(total_pixels, n);
+}
+int udet_component_boxes_ragged(const int* labels, const unsigned char* score, int n, const long long* offsets, const int* hw,
+                                int max_h, int max_w, size_t total_pixels, int min_area, int k, long long* dets, long long* counts,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (bad_batch("component_boxes_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!labels || !offsets || !hw || !dets || !counts) {
+    set_error("component_boxes_ragged: bad argument (non-null labels, offsets, hw, dets and counts)");
+    return UDET_ERR_ARG;
+  }
+  if (k < 1 || k > UDET_DET_MAX_K || min_area < 1) {
+    set_error("component_boxes_ragged: k = %d in 1..UDET_DET_MAX_K = %d and min_area = %d >= 1 are required", k, UDET_DET_MAX_K, min_area);
+    return UDET_ERR_ARG;
+  }
+  if (bad_workspace("component_boxes_ragged", workspace, workspace_bytes, component_boxes_workspace_bytes(total_pixels, n), 8)) return UDET_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(labels) & 3) || ((reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts)) & 7)) {
+    set_error("component_boxes_ragged: labels must be 4-byte aligned, dets and counts 8-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_component_boxes_ragged(labels, score, n, offsets, hw, max_h, max_w, total_pixels, min_area, k, dets, counts, workspace,
+                                       (hipStream_t)stream);
+}
+
+int udet_draw_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
+                           const long long* dets, const long long* counts, int k, int thickness, unsigned rgb, void* stream) {
+  if (bad_batch("draw_boxes_ragged", n, 1, 1, total_pixels)) return UDET_ERR_ARG;
+  if (!image_rgb || !offsets || !hw || !dets || !counts) {
+    set_error("draw_boxes_ragged: bad argument (non-null image_rgb, offsets, hw, dets and counts)");
+    return UDET_ERR_ARG;
+  }
+  if (k < 1 || k > UDET_DET_MAX_K || thickness < 1 || thickness > UDET_DRAW_MAX_THICKNESS || rgb > 0xffffffu) {
+    set_error("draw_boxes_ragged: k = %d in 1..UDET_DET_MAX_K = %d, thickness = %d in 1..%d and rgb = 0x%x of 24 bits are required", k,
+              UDET_DET_MAX_K, thickness, UDET_DRAW_MAX_THICKNESS, rgb);
+    return UDET_ERR_ARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts)) & 7) {
+    set_error("draw_boxes_ragged: dets and counts must be 8-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_draw_boxes_ragged(image_rgb, n, offsets, hw, dets, counts, k, thickness, rgb, (hipStream_t)stream);
+}
+
 size_t udet_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int kh, int kw, int upsample2x) {
   const int kc = round_up(cin > cout ? cin : cout, 8), ldw = round_up(cin > cout ? cin : cout, 4);
   const size_t pix_in = (size_t)n * h * w, pix_out = pix_in * (upsample2x ? 4 : 1);

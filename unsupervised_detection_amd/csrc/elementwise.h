@@ -53,6 +53,13 @@ size_t components_workspace_bytes(size_t total_pixels, int n);
 int launch_select_components_ragged(const unsigned char* binary, const unsigned char* gt, int n, const long long* offsets, const int* hw,
                                     int max_h, int max_w, size_t total_pixels, int connectivity, int mode, int* labels,
                                     unsigned char* selected, long long* info, void* workspace, hipStream_t s);
+// detections.hip: udet_component_boxes_ragged / udet_draw_boxes_ragged (arguments already checked)
+size_t component_boxes_workspace_bytes(size_t total_pixels, int n);
+int launch_component_boxes_ragged(const int* labels, const unsigned char* score, int n, const long long* offsets, const int* hw, int max_h,
+                                  int max_w, size_t total_pixels, int min_area, int k, long long* dets, long long* counts, void* workspace,
+                                  hipStream_t s);
+int launch_draw_boxes_ragged(unsigned char* rgb, int n, const long long* offsets, const int* hw, const long long* dets,
+                             const long long* counts, int k, int thickness, unsigned colour, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
 int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet

@@ -12,13 +12,16 @@ post_processing/post_processing.py:32-46:
   restore_masks(masks, native_hw, ...)          one call of the ragged kernel (csrc/restore.hip) -> RestoredMasks
   select_components(binary, offsets, hw, gt, mode, ...)   connected components of the restored masks and the choice of one per sample
                                                 (csrc/components.hip, udet_select_components_ragged) -> ComponentSelection
+  component_boxes(selection_or_labels, score, min_area, max_detections)   every component of the labelled masks as a scored box, the
+                                                largest first (csrc/detections.hip, udet_component_boxes_ragged) -> Detections;
+                                                detection_records: the same as plain records (box, area, centroid, score, root)
   RestoredMasks / GtBatch / ComponentSelection  buffers of one batch in one ragged.PackedLayout (the packed layout): the
                                                 annotations' layout is built once per batch and handed from call to call
   check_crf_tables / load_images_device / crf_refine_restored   the full-resolution dense CRF of run_crf_original_resolution on the
                                                 restored batch: unary from the restored bytes, the frames read at their own size,
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
-  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] + J / F +
-                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections] + J / F +
+                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json [, detections/<sequence>.json]
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order; (image, None) for
                                                 a folder of frames without annotations (--dataset FRAMES), which restore_results_dir
                                                 takes in its annotation-free mode; overlay=... draws the final masks on the frames
@@ -26,7 +29,8 @@ post_processing/post_processing.py:32-46:
 
 scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  The "best detection candidate from
 the set of predicted connected masks" the reference only mentions in a comment (post_processing.py:32-35) is select_components
-(DESIGN.md 7.3).  The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...})."""
+(DESIGN.md 7.3).  The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...}).  Every component as a box with
+its area, centroid and score -- the detections -- is restore_results_dir(detections={...})."""
 from __future__ import annotations
 
 import ctypes
@@ -374,6 +378,112 @@ def select_components(binary, offsets=None, hw=None, gt=None, mode="largest", co
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Every component as a scored box: the detections at native size (csrc/detections.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+DET_FIELDS = 9  # UDET_DET_FIELDS: root, area, y0, x0, y1, x1, sum_y, sum_x, score_sum
+DET_MAX_K = 64  # UDET_DET_MAX_K
+DETECTION_DEFAULTS = {"min_area": 64, "max_detections": 16}
+
+
+def detection_params(detections=None):
+    """The `detections` dict of restore_results_dir ({} or None: the defaults) with the defaults filled in and checked (ValueError):
+    min_area an integer >= 1, max_detections an integer in 1..DET_MAX_K."""
+    p = dict(DETECTION_DEFAULTS)
+    if detections is not None:
+        if not isinstance(detections, dict) or not set(detections) <= set(DETECTION_DEFAULTS):
+            raise ValueError("detections must be a dict with keys among {}".format(sorted(DETECTION_DEFAULTS)))
+        p.update({k: v for k, v in detections.items() if v is not None})
+    for k in p:
+        if isinstance(p[k], bool) or int(p[k]) != p[k]:
+            raise ValueError("detections: {} must be an integer".format(k))
+        p[k] = int(p[k])
+    if p["min_area"] < 1 or p["min_area"] > ragged.INT32_MAX or not 1 <= p["max_detections"] <= DET_MAX_K:
+        raise ValueError("detections: min_area >= 1 (below 2^31) and max_detections in 1..{} are required".format(DET_MAX_K))
+    return p
+
+
+class Detections(PackedSamples):
+    """Result of component_boxes: dets (device int64 [n, k, DET_FIELDS]: per sample the components with area >= min_area, largest first,
+    ties to the smaller root; the rows past the last one hold root = -1 and zeros), counts (device int64 [n, 3] = components, kept, rows
+    written), min_area, k; `layout` is that of the labels they were computed from."""
+
+    def __init__(self, dets, counts, layout, min_area, k):
+        PackedSamples.__init__(self, layout, dets.device)
+        self.dets, self.counts, self.min_area, self.k = dets, counts, int(min_area), int(k)
+        self._host = None
+
+    def host(self):
+        """(dets, counts) as numpy arrays: one copy of each per Detections, made on first use."""
+        if self._host is None:
+            self._host = (_host(self.dets), _host(self.counts))
+        return self._host
+
+    def rows(self, i):
+        """Host view int64 [rows written, DET_FIELDS] of sample i."""
+        dets, counts = self.host()
+        return dets[i, :int(counts[i, 2])]
+
+
+def component_boxes(selection_or_labels, score=None, min_area=64, max_detections=16, offsets=None, hw=None) -> Detections:
+    """Every connected component of n labelled masks as a scored box, in one call of udet_component_boxes_ragged (four launches
+    whatever n and the number of components; nothing comes back to the host).  selection_or_labels: a ComponentSelection that has labels
+    (select_components(..., want_labels=True), any mode), or a 1-D int32 device tensor of labels (root + 1 / 0) with host offsets [n] /
+    hw [n,2] (or a PackedLayout as offsets, hw=None).  score: optional, a RestoredMasks (its soft bytes `data`) or a 1-D uint8 device
+    tensor packed like the labels.  Per sample the components of at least min_area pixels, largest first (ties to the smaller root),
+    at most max_detections (1..DET_MAX_K) of them: root, area, y0, x0, y1, x1 (y1 / x1 exclusive), sum_y, sum_x, score_sum -- exact
+    integers.  Arguments and tables are validated on the host before the device is touched (ValueError)."""
+    if isinstance(selection_or_labels, ComponentSelection):
+        if selection_or_labels.labels is None:
+            raise ValueError("selected without want_labels: no labels")
+        if offsets is not None or hw is not None:
+            raise ValueError("a ComponentSelection brings its own layout")
+        labels, offsets = selection_or_labels.labels, selection_or_labels.layout
+    else:
+        labels = selection_or_labels
+    if offsets is None or (hw is None and not isinstance(offsets, PackedLayout)):
+        raise ValueError("a packed buffer needs its offsets and sizes")
+    p = detection_params({"min_area": min_area, "max_detections": max_detections})
+    total = int(require_tensor(labels, "labels (packed samples)", torch.int32, 1, cuda=False).numel())
+    layout = as_layout(offsets, hw, total, max_samples=65535)  # raw tables: validated before the device is touched
+    if isinstance(score, RestoredMasks):
+        if not score.layout.same_as(layout):
+            raise ValueError("the scores must be packed like the labels (same offsets and sizes)")
+        score = score.data
+    if score is not None:
+        require_tensor(score, "score (packed like the labels)", torch.uint8, 1, total, cuda=False)
+    require_tensor(labels, "labels (packed samples)", torch.int32, 1)
+    dev, n, k = labels.device, layout.n, p["max_detections"]
+    if score is not None:
+        require_tensor(score, "score (packed like the labels)", torch.uint8, 1, total, dev)
+    d_off, d_hw = layout.device_tables(dev)
+    dets = torch.empty((n, k, DET_FIELDS), dtype=torch.int64, device=dev)
+    counts = torch.empty((n, 3), dtype=torch.int64, device=dev)
+    ws = workspace(lib.udet_component_boxes_workspace_bytes(total, n, k), 8, dev)
+    check(lib.udet_component_boxes_ragged(labels.data_ptr(), None if score is None else score.data_ptr(), n, d_off.data_ptr(),
+                                          d_hw.data_ptr(), layout.max_h, layout.max_w, total, p["min_area"], k, dets.data_ptr(),
+                                          counts.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+    return Detections(dets, counts, layout, p["min_area"], k)
+
+
+def detection_records(detections, amax):
+    """The detections of a batch as plain records: per frame a list, in rank order, of {"box": [x0, y0, x1, y1] (x1 / y1 exclusive),
+    "area", "centroid": [sum_x / area, sum_y / area], "score": score_sum / (area * (amax + 1e-8)) in float64 -- the mean of
+    RestoredMasks.soft over the component -- and "root"}.  detections: a Detections (or anything with len() and rows(i)); amax: the
+    batch's RestoredMasks.amax (one integer per frame)."""
+    amax = _host(amax).reshape(-1)
+    if len(amax) != len(detections):
+        raise ValueError("one amax per frame")
+    out = []
+    for i in range(len(detections)):
+        recs = []
+        for root, area, y0, x0, y1, x1, sy, sx, ss in (tuple(int(v) for v in row) for row in detections.rows(i)):
+            recs.append({"box": [x0, y0, x1, y1], "area": area, "centroid": [sx / area, sy / area],
+                         "score": float(np.float64(ss) / (np.float64(area) * (np.float64(amax[i]) + 1e-8))), "root": root})
+        out.append(recs)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # The dense CRF at native resolution (csrc/crf.hip, DESIGN.md 7.4)
 # ---------------------------------------------------------------------------------------------------------------------------
 CRF_KEYS = ("sxy", "srgb", "compat", "gauss_k", "iters", "radius")
@@ -438,10 +548,17 @@ def draw_overlays(frames, masks, overlay):
     return overlay_native(frames, masks, **overlay)
 
 
+def draw_detection_boxes(overlays, detections, boxes):
+    """visualize.draw_boxes(overlays, detections, **boxes): the boxes of a batch on its overlays, in place, one launch."""
+    from .visualize import draw_boxes
+    return draw_boxes(overlays, detections, **boxes)
+
+
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
                         gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True,
                         component=None, connectivity=8, select=select_components, crf=None, load_images=load_images_device,
-                        refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays):
+                        refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays, detections=None,
+                        detect=component_boxes, draw_boxes=draw_detection_boxes):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -471,8 +588,17 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     defaults).  Every frame's final binary mask -- after the CRF and the component selection -- is drawn on the untouched frame at its
     own size (draw: one call of overlay_native per batch, on the frames the CRF already loaded when it is on) and written to
     <out_dir>/overlay/<category>/<frame stem>.png; the mask folders keep only masks; the json gains "overlay" with the parameters used.
-    restore / load_gt / score / select / load_images / refine / load_sizes / draw are injectable: the host logic runs without a GPU on
-    numpy stand-ins."""
+    detections (None: off): a dict with min_area (64) and max_detections (16; at most 64), {} for the defaults.  The batch's binary masks
+    -- after the CRF, before the component selection -- are labelled once under `connectivity`: with a component mode by the same select
+    call, made with want_labels=True, otherwise by one select call in mode "label"; detect(labelled, score=restored, min_area=...,
+    max_detections=...) (component_boxes: four launches per batch) then gives every component of at least min_area pixels as a box, the
+    largest first, at most max_detections per frame.  detection_records of each frame go to <out_dir>/detections/<category>.json ({frame
+    stem: [record, ...]}, in the list's order); the json gains "detections": {min_area, max_detections, connectivity} and per sequence
+    "detections_mean" (the mean number of records per frame).  With and without annotations.  overlay["boxes"] (needs detections; a dict
+    with thickness (2; 1..8) and colour ((255, 255, 0)), {} for the defaults): draw_boxes(overlays, detections, boxes) paints the boxes on
+    the batch's overlays after the mask (visualize.draw_boxes, one launch), and the json's "overlay" carries "boxes".
+    restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes are injectable: the host logic
+    runs without a GPU on numpy stand-ins."""
     import json
     import re
     import scipy.io as sio
@@ -482,12 +608,18 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     batch = max(1, int(batch))
     if component not in (None, "largest", "best_gt"):
         raise ValueError('component must be None, "largest" or "best_gt"')
-    if component is not None and connectivity not in (4, 8):
+    if (component is not None or detections is not None) and connectivity not in (4, 8):
         raise ValueError("connectivity must be 4 or 8")
     crf = None if crf is None else crf_params(crf)
+    detections = None if detections is None else detection_params(detections)
+    boxes = None
     if overlay is not None:
-        from .visualize import overlay_params
-        overlay = overlay_params(overlay)
+        from .visualize import box_params, overlay_params
+        if isinstance(overlay, dict) and overlay.get("boxes") is not None:
+            if detections is None:
+                raise ValueError('overlay["boxes"] draws the detections: it needs detections')
+            boxes = box_params(overlay["boxes"])
+        overlay = overlay_params({k: v for k, v in overlay.items() if k != "boxes"} if isinstance(overlay, dict) else overlay)
     missing = [a is None for entries in frame_lists.values() for _, a in entries]
     free = bool(missing) and all(missing)  # annotation-free: sizes from the frames, nothing to score against
     if any(missing) and not free:
@@ -496,7 +628,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         raise ValueError('component "best_gt" needs annotations: use "largest" or None')
     if not free:
         rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
-    cat_j, cat_f, cat_nc, cat_fg = {}, {}, {}, {}
+    cat_j, cat_f, cat_nc, cat_fg, cat_nd = {}, {}, {}, {}, {}
     for cat, entries in frame_lists.items():
         d = os.path.join(results_dir, cat)
         ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
@@ -507,6 +639,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         if overlay is not None:
             os.makedirs(os.path.join(out_dir, "overlay", cat), exist_ok=True)
         j, f, nc, fg = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries)), np.zeros(len(entries))
+        records = {}  # frame stem -> its detections, in the list's order
         for s in range(0, len(entries), batch):
             rows = entries[s:s + batch]
             masks = []
@@ -530,9 +663,19 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             frames = load_images([img for img, _ in rows]) if crf is not None or overlay is not None else None  # read once for both
             if crf is not None:
                 pred = refine(res, frames, crf)
+            labelled = None  # the batch's labels, for the detections: what the CRF left, labelled once
             if component is not None:
-                pred = select(pred, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity)
+                pred = select(pred, gt=gt if component == "best_gt" else None, mode=component, connectivity=connectivity,
+                              **({} if detections is None else {"want_labels": True}))
                 nc[s:s + len(rows)] = _host(pred.info)[:, 0]
+                labelled = pred
+            elif detections is not None:
+                labelled = select(pred, mode="label", connectivity=connectivity, want_labels=True)
+            det = None
+            if detections is not None:
+                det = detect(labelled, score=res, min_area=detections["min_area"], max_detections=detections["max_detections"])
+                for (img, _), recs in zip(rows, detection_records(det, res.amax)):
+                    records[os.path.splitext(os.path.basename(img))[0]] = recs
             if not free:
                 shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
                 for shape in sorted(set(shapes)):
@@ -540,6 +683,8 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                     jj, ff = score(gt.stack(idx), pred.stack(idx), bound_th)
                     j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
             drawn = draw(frames, pred, overlay) if overlay is not None else None
+            if boxes is not None:
+                drawn = draw_boxes(drawn, det, boxes)
             for i, (img, _) in enumerate(rows):
                 stem = os.path.splitext(os.path.basename(img))[0]
                 binm = _host(pred.binary_sample(i)).astype(np.uint8)
@@ -555,6 +700,11 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                         os.path.join(out_dir, "overlay", cat, stem + ".png"))
         cat_j[cat], cat_f[cat], cat_nc[cat] = j.tolist(), f.tolist(), float(nc.mean()) if len(nc) else 0.0
         cat_fg[cat] = float(fg.mean()) if len(fg) else 0.0
+        if detections is not None:
+            os.makedirs(os.path.join(out_dir, "detections"), exist_ok=True)
+            with open(os.path.join(out_dir, "detections", cat + ".json"), "w") as fh:
+                json.dump(records, fh, indent=1)
+            cat_nd[cat] = float(np.mean([len(r) for r in records.values()])) if records else 0.0
     if not cat_j:
         raise IOError("no category to restore")
     if free:
@@ -567,7 +717,11 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         if crf is not None:
             out["crf"] = crf
         if overlay is not None:
-            out["overlay"] = overlay
+            out["overlay"] = overlay if boxes is None else dict(overlay, boxes=boxes)
+        if detections is not None:
+            out["detections"] = dict(detections, connectivity=int(connectivity))
+            for c in out["sequences"]:
+                out["sequences"][c]["detections_mean"] = cat_nd[c]
         if verbose:
             print("Native resolution ({} frames, crop {}, no annotations):".format(sum(len(v) for v in cat_j.values()), crop))
             for c, v in out["sequences"].items():
@@ -587,7 +741,11 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     if crf is not None:
         out["crf"] = crf
     if overlay is not None:
-        out["overlay"] = overlay
+        out["overlay"] = overlay if boxes is None else dict(overlay, boxes=boxes)
+    if detections is not None:
+        out["detections"] = dict(detections, connectivity=int(connectivity))
+        for c in out["sequences"]:
+            out["sequences"][c]["detections_mean"] = cat_nd[c]
     if verbose:
         print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
         _print_davis_table(per, tot)

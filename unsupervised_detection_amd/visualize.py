@@ -168,6 +168,52 @@ def overlay_native(images, masks, alpha=0.5, beta=0.4, colour=(0, 255, 0), edge=
     return NativeOverlays(out, frames)
 
 
+DRAW_MAX_THICKNESS = 8  # UDET_DRAW_MAX_THICKNESS
+BOX_DEFAULTS = {"thickness": 2, "colour": (255, 255, 0)}
+
+
+def box_params(boxes=None):
+    """The parameters of draw_boxes (a dict, or None for the defaults) with the defaults filled in and checked (ValueError): thickness an
+    integer in 1..DRAW_MAX_THICKNESS, colour three integers in 0..255."""
+    p = dict(BOX_DEFAULTS)
+    if boxes is not None:
+        if not isinstance(boxes, dict) or not set(boxes) <= set(BOX_DEFAULTS):
+            raise ValueError("boxes must be a dict with keys among {}".format(sorted(BOX_DEFAULTS)))
+        p.update({k: v for k, v in boxes.items() if v is not None})
+    if isinstance(p["thickness"], bool) or int(p["thickness"]) != p["thickness"] or not 1 <= int(p["thickness"]) <= DRAW_MAX_THICKNESS:
+        raise ValueError("boxes: thickness must be an integer in 1..{}".format(DRAW_MAX_THICKNESS))
+    _rgb24(p["colour"], "colour")
+    p["thickness"], p["colour"] = int(p["thickness"]), tuple(int(v) for v in p["colour"])
+    return p
+
+
+def draw_boxes(overlays, detections, thickness=2, colour=(255, 255, 0)) -> NativeOverlays:
+    """The frames of a batch's detections painted on its overlays, in place, in one call of udet_draw_boxes_ragged (one launch; dets
+    and counts are read on the device).  overlays: a NativeOverlays (or anything with packed rgb `data` and its `layout`: a RaggedBatch of
+    frames); detections: the native_results.Detections of the same frames (their sizes in the same order at a third of the overlays'
+    offsets).  A pixel of a box [y0, y1) x [x0, x1) is painted `colour` when it lies within `thickness` (1..8) rows or columns of the
+    box's edge, inward; a box narrower than twice the thickness is filled; every other byte stays.  Returns overlays.  Validated on the
+    host before the device is touched (ValueError)."""
+    p = box_params({"thickness": thickness, "colour": colour})
+    frames, layout = overlays.layout, detections.layout
+    if frames.c != 3 or not frames.same_as(layout, scale=3):
+        raise ValueError("the overlays must be rgb and packed like the detections' frames (their sizes, three times their offsets)")
+    as_layout(layout, None, layout.numel, max_samples=65535)
+    for t, name, shape in ((detections.dets, "dets", (layout.n, detections.k, 9)), (detections.counts, "counts", (layout.n, 3))):
+        require_tensor(t, "detections." + name, torch.int64, len(shape), cuda=False)
+        if tuple(t.shape) != shape:
+            raise ValueError("detections.{} must be {} for {} frames".format(name, list(shape), layout.n))
+    dev = detections.dets.device
+    require_tensor(detections.dets, "detections.dets", torch.int64, 3)
+    require_tensor(detections.counts, "detections.counts", torch.int64, 2, device=dev)
+    require_tensor(overlays.data, "overlays (rgb, packed like the detections' frames)", torch.uint8, 1, 3 * layout.numel, dev)
+    d_off, d_hw = layout.device_tables(dev)
+    check(lib.udet_draw_boxes_ragged(overlays.data.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.numel,
+                                     detections.dets.data_ptr(), detections.counts.data_ptr(), detections.k, p["thickness"],
+                                     _rgb24(p["colour"], "colour"), torch.cuda.current_stream(dev).cuda_stream))
+    return overlays
+
+
 # ------------------------------------------------------------------------------------------------------- histograms ----
 def bucket_limits() -> np.ndarray:
     """TensorFlow's default histogram bucket limits, as the library builds them: 1551 ascending float64."""
