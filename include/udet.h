@@ -121,13 +121,14 @@ int udet_boundary_stats(const float* pred_masks, const float* gt_masks, const do
  * by the host exactly as Pillow's Resample.c does (BILINEAR); hk / vk = -1: the pass's output length equals its input length and the
  * pass is skipped (not run with identity weights).  Per sample:
  *   byte = uint8(clip((v - mn) * (255 / cscale), 0, 255) + 0.5) in double, mn / mx over the WHOLE mask, cscale = mx - mn or 1 if 0
- *          (scipy.misc.bytescale as udet_post_bytescale defines it);
+ *          (scipy.misc.bytescale as udet_post_bytescale defines it: pil_byte of csrc/pil_resample.h in both);
  *   horizontal pass, uint8 intermediate, vertical pass, each ss = 1 << 21; ss += pixel * kk; clip8(ss >> 22) (udet_post_resample_u8);
  *   the patch lands at (y0, x0), every other byte of the sample is 0; amax[i] (device int32 [n]) = the largest byte of the patch;
  *   binary (optional, NULL: off): packed like data, 1 where (double)byte / (amax + 1e-8) > threshold (a real float64 division,
  *          crf_refine.py:94), else 0.  A constant mask restores to zeros, amax = 0, binary zeros.
- * At most three launches whatever n is (min / max partials; bytescale + both passes + placement on 64 x 16 tiles of each frame,
- * integer atomicMax into amax; the binary mask), many workgroups per sample.  max_h / max_w: the largest H_i / W_i (sizes the grid).
+ * At most three launches whatever n is (min / max partials; bytescale + both passes + placement on 64 x 16 tiles of each frame, the
+ * tile routine of csrc/pil_resample.h, integer atomicMax into amax; the binary mask), many workgroups per sample.  max_h / max_w:
+ * the largest H_i / W_i (sizes the grid).
  * workspace: udet_restore_workspace_bytes(n) bytes, 4-byte aligned.  amax is zeroed by the call.  Only the scalars and pointers
  * are checked here (UDET_ERR_ARG; nothing is enqueued on an error): the tables are device memory, and every index the kernels form is
  * bounded by them -- offsets inside data, boxes inside their frames, coefficient windows inside coef and taps inside the mask must
@@ -322,8 +323,9 @@ int udet_post_select_unary(const float* pred, const float* avg_f, const float* a
  *              pass (sh -> hh); hk / vk < 0: the pass is skipped (out == in)
  *   coef       device int32: the concatenated coefficient blocks
  * Launch 1, per mask: the border mean (udet_post_border_mean's loop and tree: the same double) and the min / max of the source window as
- * partial pairs.  Launch 2: every raw mask of a rectify row is bytescaled and resampled on 64 x 16 tiles of its patch (horizontal pass into a
- * uint8 LDS strip, vertical pass out of it) into the workspace, the patch's largest byte by an integer atomicMax.  Launch 3, one thread per
+ * partial pairs.  Launch 2: every raw mask of a rectify row is bytescaled and resampled on 64 x 16 tiles of its patch (the tile routine of
+ * udet_restore_masks_ragged, csrc/pil_resample.h: horizontal pass into a uint8 LDS strip, vertical pass out of it) into the workspace, the
+ * patch's largest byte by an integer atomicMax.  Launch 3, one thread per
  * pixel: per (frame, shift, crop) both means >= san_t: both slots are zeros; only the backward run's: its slot takes the forward run's patch
  * and maximum; only the forward run's: the reverse; term = vb / (maxb + 1e-6) + vf / (maxf + 1e-6) in double with zeros outside the patch
  * (identity: (double)s_b + (double)s_f); score = term_0, then score += term_k shift-major, crop-minor -- the order of the reference's loops;

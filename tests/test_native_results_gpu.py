@@ -57,6 +57,14 @@ def test_bit_exact_against_pillow(batch):
     _assert_equals_np(restore_masks(torch.from_numpy(big).cuda(), [(480, 854)], 0.9, 0.5), restore_np(big, [(480, 854)], 0.9, 0.5))
 
 
+def test_tile_reads_more_than_one_strip(gpu):
+    """A tenfold vertical shrink: the 16 patch rows of one tile read about 160 mask rows, three 64-row strips of the horizontal
+    intermediate (every other shape here stays inside the first)."""
+    from unsupervised_detection_amd.native_results import restore_masks
+    masks, sizes = random_masks(2, 200, 40, seed=23), [(20, 30), (23, 31)]
+    _assert_equals_np(restore_masks(torch.from_numpy(masks).cuda(), sizes, 1.0, 0.5), restore_np(masks, sizes, 1.0, 0.5))
+
+
 def test_bit_exact_against_per_frame_path(batch):
     from unsupervised_detection_amd.native_results import restore_box
     from unsupervised_detection_amd.post_processing import _imresize_window

@@ -98,6 +98,20 @@ def test_other_ensemble_sizes(PP, ns, crops):
         assert np.array_equal(got[i], ref), i
 
 
+def test_tile_reads_more_than_one_strip(PP):
+    """Crop 20 against base crop 90 shrinks 96 rows to int(96 * 20 / 90) = 21: the 16 patch rows of the first tile read more than 64 window
+    rows, a second strip of the horizontal intermediate (every other shape here stays inside the first)."""
+    import torch
+    H, W, n, crops = 96, 40, 2, (20, 90)
+    preds = ensemble(n, 1, 2, H, W, seed=31)
+    got = batch(PP, preds, crops)
+    high = PP.soft_score_batch(preds, crops)
+    for i in range(n):
+        pb, pf = [list(row) for row in preds[i, 0]], [list(row) for row in preds[i, 1]]
+        assert np.array_equal(got[i], P.soft_score(pb, pf, crops, 90.0, base_hw=(H, W))), i
+        assert torch.equal(high[i], PP.soft_score(pb, pf, crops, 90.0, (H, W))), i
+
+
 def test_independent_of_the_batch_and_the_run(PP):
     H, W, n = 24, 40, 5
     edges, const = branches(3)

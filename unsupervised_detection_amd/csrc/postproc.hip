@@ -5,11 +5,13 @@
 //   post_processing/crf_refine.py                         refine :110-138 (gaussian unary, dense CRF mean field)
 // The frames are 192x384: every kernel here is a few microseconds of byte / integer / small-float work, written for exact
 // agreement with the CPU restatement (oracle/oracle_post.py), not for a roofline.  Masks and scores are accumulated in double like
-// the reference's numpy float64 arrays.  Compiled with -ffp-contract=off (Makefile).
+// the reference's numpy float64 arrays.  Compiled with -ffp-contract=off (Makefile).  The per-pixel arithmetic of bytescale and of a
+// Pillow pass is that of pil_resample.h, which the batched kernels (restore.hip, soft_score.hip) share.
 #include <math.h>
 
 #include "common.h"
 #include "host_checks.h"
+#include "pil_resample.h"
 #include "post_remap.h"
 
 namespace udet {
@@ -59,11 +61,7 @@ __global__ __launch_bounds__(1024) void post_bytescale_kernel(const double* __re
   double cscale = mx - mn;
   if (cscale == 0.0) cscale = 1.0;
   const double scale = 255.0 / cscale;
-  for (int i = threadIdx.x; i < h * w; i += 1024) {
-    double b = (src[(size_t)(y0 + i / w) * ld + x0 + i % w] - mn) * scale + 0.0;
-    b = fmin(fmax(b, 0.0), 255.0) + 0.5;
-    dst[i] = (unsigned char)b;
-  }
+  for (int i = threadIdx.x; i < h * w; i += 1024) dst[i] = (unsigned char)pil_byte(src[(size_t)(y0 + i / w) * ld + x0 + i % w], mn, scale);
 }
 
 // One pass of Pillow's 8-bit resampler (Resample.c ImagingResampleHorizontal_8bpc / Vertical_8bpc): for output index o along
@@ -77,13 +75,9 @@ __global__ __launch_bounds__(256) void post_resample_u8_kernel(const unsigned ch
     const int y = i / ow, x = i - y * ow;
     const int o = axis ? x : y;
     const int lo = bounds[2 * o], n = bounds[2 * o + 1];
-    int ss = 1 << 21;
-    for (int k = 0; k < n; ++k) {
-      const int pix = axis ? src[(size_t)y * w + lo + k] : src[(size_t)(lo + k) * w + x];
-      ss += pix * kk[o * ksize + k];
-    }
-    ss >>= 22;
-    dst[i] = (unsigned char)(ss < 0 ? 0 : (ss > 255 ? 255 : ss));
+    const unsigned char* __restrict__ p = axis ? src + (size_t)y * w + lo : src + (size_t)lo * w + x;
+    const int step = axis ? 1 : w;
+    dst[i] = (unsigned char)pil_taps(kk + o * ksize, n, [&](int k) -> int { return p[(size_t)k * step]; });
   }
 }
 

@@ -3,10 +3,9 @@
 // post_processing.soft_score does with about a hundred launches and a host round trip per frame, bit for bit:
 //   1. soft_stats_kernel      per mask: the border mean (post_border_mean_kernel's loop and tree: the same double) by workgroup 0, the
 //                             min / max of the mask's source window as SOFT_NB1 partial pairs by the others; zeroes the patch maximum
-//   2. soft_resample_kernel   one 64 x 16 tile of a mask's patch per workgroup (the tile form of restore_resample_kernel): bytescale of
-//                             the window on the fly, horizontal pass into an LDS strip (uint8, Pillow's intermediate image), vertical
-//                             pass out of it; the bytes go to the workspace at their place on the canvas, their maximum by an integer
-//                             atomicMax.  Every raw mask is resampled, whatever the sanity rule says: launch 3 chooses among the patches
+//   2. soft_resample_kernel   one 64 x 16 tile of a mask's patch per workgroup: pil_tile (pil_resample.h, the routine restore.hip runs)
+//                             on the mask's source window; the bytes go to the workspace at their place on the canvas, their maximum by an
+//                             integer atomicMax.  Every raw mask is resampled, whatever the sanity rule says: launch 3 chooses among the patches
 //   3. soft_fuse_kernel       one thread per pixel: the sanity rule per (frame, shift, crop), term = vb / (maxb + 1e-6) + vf / (maxf + 1e-6)
 //                             (identity row: s_b + s_f), score += term shift-major, crop-minor; the score into pred_mask, a (min, max)
 //                             pair per workgroup into the workspace
@@ -18,13 +17,11 @@
 
 #include "common.h"
 #include "host_checks.h"
+#include "pil_resample.h"
 
 namespace udet {
 
 #define SOFT_NB1 8       // partial min / max pairs per mask
-#define SOFT_TW 64       // tile: 64 columns of the patch (one lane per column)
-#define SOFT_TR 16       //       x 16 rows, four per thread
-#define SOFT_STRIP 64    // rows of the horizontal intermediate held in LDS at a time
 #define SOFT_GEOM UDET_SOFT_SCORE_GEOM
 // a geometry row: mode (0 identity, 1 rectify) | source window sy0 sx0 sh sw | patch hh ww at y0 x0 | hk hb hks | vk vb vks | 0
 enum { G_MODE, G_SY0, G_SX0, G_SH, G_SW, G_HH, G_WW, G_Y0, G_X0, G_HK, G_HB, G_HKS, G_VK, G_VB, G_VKS };
@@ -103,120 +100,35 @@ __global__ __launch_bounds__(1024) void soft_stats_kernel(SoftArgs a) {
   }
 }
 
-// scipy.misc.bytescale of one value: the doubles of post_bytescale_kernel
-__device__ __forceinline__ int soft_byte(float v, double mn, double scale) {
-  double b = ((double)v - mn) * scale + 0.0;
-  b = fmin(fmax(b, 0.0), 255.0) + 0.5;
-  return (int)(unsigned char)b;
-}
-
 // launch 2: grid (tiles of the largest patch, M), 256 threads
 __global__ __launch_bounds__(256) void soft_resample_kernel(SoftArgs a) {
-  __shared__ unsigned char strip[SOFT_STRIP * SOFT_TW];
-  __shared__ int smax[4];
   const int m = blockIdx.y, t = threadIdx.x, W = a.w;
   const int* __restrict__ g = a.geom + (m % a.R) * SOFT_GEOM;
   if (!g[G_MODE]) return;  // block-uniform: the identity row takes the raw masks
   const int hh = g[G_HH], ww = g[G_WW];
-  const int tiles_x = (ww + SOFT_TW - 1) / SOFT_TW, tiles_y = (hh + SOFT_TR - 1) / SOFT_TR;
+  const int tiles_x = (ww + PIL_TW - 1) / PIL_TW, tiles_y = (hh + PIL_TR - 1) / PIL_TR;
   if ((int)blockIdx.x >= tiles_x * tiles_y) return;  // block-uniform: the grid is sized for a patch that fills the canvas
-  const int* __restrict__ hk = g[G_HK] >= 0 ? a.coef + g[G_HK] : nullptr;
-  const int* __restrict__ hb = g[G_HK] >= 0 ? a.coef + g[G_HB] : nullptr;
-  const int hks = g[G_HKS];
-  const int* __restrict__ vk = g[G_VK] >= 0 ? a.coef + g[G_VK] : nullptr;
-  const int* __restrict__ vb = g[G_VK] >= 0 ? a.coef + g[G_VB] : nullptr;
-  const int vks = g[G_VKS];
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
-  const int col = t & (SOFT_TW - 1), x = tx * SOFT_TW + col;
+  const int x = tx * PIL_TW + (t & (PIL_TW - 1)), y = ty * PIL_TR + (t >> 6);  // patch coordinates
   const bool in_x = x < ww;
-  const int ya = ty * SOFT_TR, yb = min(ya + SOFT_TR, hh);  // patch rows [ya, yb) of this tile, ya < yb
-
-  int ss[4], vlo[4], vn[4];
+  const int ya = ty * PIL_TR, yb = min(ya + PIL_TR, hh);  // patch rows [ya, yb) of this tile, ya < yb
   bool live[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int y = ya + (t >> 6) + 4 * j;
-    live[j] = in_x && y < hh;
-    ss[j] = 1 << 21;
-    vlo[j] = 0;
-    vn[j] = 0;
-    if (live[j]) {
-      if (vb) { vlo[j] = vb[2 * y]; vn[j] = vb[2 * y + 1]; }
-      else { vlo[j] = y; vn[j] = 1; }
-    }
-  }
-  // bytescale constants of the window: the partial pairs of launch 1
-  float fmn = INFINITY, fmx = -INFINITY;
-  for (int b = 0; b < SOFT_NB1; ++b) {
-    fmn = fminf(fmn, a.wpart[((size_t)m * SOFT_NB1 + b) * 2]);
-    fmx = fmaxf(fmx, a.wpart[((size_t)m * SOFT_NB1 + b) * 2 + 1]);
-  }
-  const double mn = (double)fmn;
-  double cscale = (double)fmx - mn;
-  if (cscale == 0.0) cscale = 1.0;
-  const double scale = 255.0 / cscale;
+  for (int j = 0; j < 4; ++j) live[j] = in_x && y + 4 * j < hh;
+  double mn, scale;  // of the window: the partial pairs of launch 1
+  pil_scale(a.wpart + (size_t)m * SOFT_NB1 * 2, SOFT_NB1, mn, scale);
   const float* __restrict__ win = a.masks + (size_t)m * a.h * W + (size_t)g[G_SY0] * W + g[G_SX0];
-  // window rows the tile's patch rows read
-  const int r0 = vb ? vb[2 * ya] : ya;
-  const int r1 = vb ? vb[2 * (yb - 1)] + vb[2 * (yb - 1) + 1] : yb;
-  int hlo = 0, hn = 0;
-  if (in_x) {
-    if (hb) { hlo = hb[2 * x]; hn = hb[2 * x + 1]; }
-    else { hlo = x; hn = 1; }
-  }
-  for (int c0 = r0; c0 < r1; c0 += SOFT_STRIP) {
-    const int c1 = min(c0 + SOFT_STRIP, r1);
-    // horizontal pass of window rows [c0, c1) at the tile's columns -> strip
-    for (int r = c0 + (t >> 6); r < c1; r += 4) {
-      int v = 0;
-      if (in_x) {
-        const float* __restrict__ row = win + (size_t)r * W;
-        if (hk) {
-          int acc = 1 << 21;
-          for (int k = 0; k < hn; ++k) acc += soft_byte(row[hlo + k], mn, scale) * hk[x * hks + k];
-          acc >>= 22;
-          v = acc < 0 ? 0 : (acc > 255 ? 255 : acc);
-        } else {
-          v = soft_byte(row[hlo], mn, scale);
-        }
-      }
-      strip[(r - c0) * SOFT_TW + col] = (unsigned char)v;
-    }
-    __syncthreads();
-    // vertical taps that fall into this strip
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      if (!live[j]) continue;
-      const int ka = max(c0 - vlo[j], 0), kb = min(c1 - vlo[j], vn[j]);
-      if (vk) {
-        const int y = ya + (t >> 6) + 4 * j;
-        for (int k = ka; k < kb; ++k) ss[j] += (int)strip[(vlo[j] + k - c0) * SOFT_TW + col] * vk[y * vks + k];
-      } else if (ka < kb) {
-        ss[j] = (int)strip[(vlo[j] - c0) * SOFT_TW + col];
-      }
-    }
-    __syncthreads();
-  }
+  const PilBytes b = pil_tile(win, W, pil_pass(a.coef, g[G_HK], g[G_HB], g[G_HKS]), pil_pass(a.coef, g[G_VK], g[G_VB], g[G_VKS]), mn, scale,
+                              x, in_x, y, live, ya, yb);
   int best = 0;
   unsigned char* __restrict__ o = a.patch + (size_t)m * a.h * W + (size_t)g[G_Y0] * W + g[G_X0];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     if (!live[j]) continue;  // x < ww and y < hh: inside the canvas by the validated row
-    int v = ss[j];
-    if (vk) {
-      v >>= 22;
-      v = v < 0 ? 0 : (v > 255 ? 255 : v);
-    }
-    o[(size_t)(ya + (t >> 6) + 4 * j) * W + x] = (unsigned char)v;
-    best = max(best, v);
+    o[(size_t)(y + 4 * j) * W + x] = (unsigned char)b.v[j];
+    best = max(best, b.v[j]);
   }
-  for (int s = 32; s > 0; s >>= 1) best = max(best, __shfl_xor(best, s, 64));
-  if ((t & 63) == 0) smax[t >> 6] = best;
-  __syncthreads();
-  if (t == 0) {
-    best = max(max(smax[0], smax[1]), max(smax[2], smax[3]));
-    if (best > 0) atomicMax(&a.pmax[m], best);
-  }
+  pil_block_max(best, &a.pmax[m]);
 }
 
 // (min, max) over a workgroup of 256 threads; exact in any order
@@ -338,7 +250,7 @@ int udet_post_soft_score_batch(const float* masks, int n, int ns, int nc, int h,
   a.pred = pred_mask;
   a.san_t = san_t;
   a.n = n; a.R = (int)R; a.h = h; a.w = w; a.nblk = (int)nblk;
-  const size_t tiles = (size_t)((w + SOFT_TW - 1) / SOFT_TW) * ((h + SOFT_TR - 1) / SOFT_TR);
+  const size_t tiles = (size_t)((w + PIL_TW - 1) / PIL_TW) * ((h + PIL_TR - 1) / PIL_TR);
   hipStream_t s = (hipStream_t)stream;
   UDET_LAUNCH(soft_stats_kernel, dim3(1 + SOFT_NB1, (unsigned)M), dim3(1024), 0, s, a);
   UDET_LAUNCH(soft_resample_kernel, dim3((unsigned)tiles, (unsigned)M), dim3(256), 0, s, a);

@@ -41,7 +41,8 @@ import torch
 
 from . import ragged
 from ._ffi import c_i, c_p, c_sz, check, lib, sig
-from .post_processing import CRF_MAX_SAMPLES, _pil_coeffs_host, default_radius, dense_crf_ragged, unary_from_restored
+from .pil_tables import CoefBlocks, check_pass
+from .post_processing import CRF_MAX_SAMPLES, default_radius, dense_crf_ragged, unary_from_restored
 from .ragged import PackedLayout, PackedSamples, as_layout, check_packed_tables, require_tensor, workspace
 
 sig("udet_restore_workspace_bytes", c_sz, c_i)
@@ -66,16 +67,6 @@ def restore_box(H, W, crop):
     return (H - h) // 2, (W - w) // 2, h, w
 
 
-_host_coeffs = {}
-
-
-def _coeffs(in_size, out_size):
-    key = (int(in_size), int(out_size))
-    if key not in _host_coeffs:
-        _host_coeffs[key] = _pil_coeffs_host(*key)
-    return _host_coeffs[key]
-
-
 def build_restore_tables(native_hw, mh, mw, crop=0.9, offsets=None):
     """Host tables of udet_restore_masks_ragged for masks of mh x mw restored into frames native_hw [n,2]: (offsets int64 [n],
     tab int32 [n,12], coef int32 [m]).  offsets default to the packed layout (sample i right after sample i-1).  One coefficient
@@ -92,24 +83,11 @@ def build_restore_tables(native_hw, mh, mw, crop=0.9, offsets=None):
         if len(off) != n:
             raise ValueError("one offset per sample")
     tab = np.zeros((n, TAB), np.int32)
-    chunks, where, pos = [], {}, 0
-
-    def table(in_size, out_size):
-        nonlocal pos
-        if in_size == out_size:
-            return -1, -1, 0
-        key = (in_size, out_size)
-        if key not in where:
-            kk, bounds, ks = _coeffs(in_size, out_size)
-            where[key] = (pos, pos + kk.size, ks)
-            chunks.extend([kk.reshape(-1), bounds.reshape(-1)])
-            pos += kk.size + bounds.size
-        return where[key]
+    blocks = CoefBlocks()
     for i, (H, W) in enumerate(hw):
         y0, x0, h, w = restore_box(H, W, crop)
-        tab[i] = (y0, x0, h, w, H, W) + tuple(table(int(mw), w)) + tuple(table(int(mh), h))
-    coef = np.concatenate(chunks).astype(np.int32) if chunks else np.zeros(1, np.int32)
-    return off, tab, np.ascontiguousarray(coef)
+        tab[i] = (y0, x0, h, w, H, W) + blocks.block(mw, w) + blocks.block(mh, h)
+    return off, tab, blocks.coef()
 
 
 def check_restore_tables(offsets, tab, coef, numel, mh, mw):
@@ -126,26 +104,9 @@ def check_restore_tables(offsets, tab, coef, numel, mh, mw):
     n = len(off)
     if (y0 < 0).any() or (x0 < 0).any() or (h < 1).any() or (w < 1).any() or (y0 + h > H).any() or (x0 + w > W).any():
         raise ValueError("box outside its own frame")
-    seen = set()
     for i in range(n):
-        for name, (k0, b0, ks), n_in, n_out in (("horizontal", t[i, 6:9], mw, w[i]), ("vertical", t[i, 9:12], mh, h[i])):
-            key = (int(k0), int(b0), int(ks), int(n_in), int(n_out))
-            if key in seen:
-                continue
-            seen.add(key)
-            if (k0 < 0) != (b0 < 0):
-                raise ValueError("sample {}: {} coefficient index outside the coefficient buffer".format(i, name))
-            if k0 < 0:
-                if n_in != n_out:
-                    raise ValueError("sample {}: the {} pass {} -> {} cannot be skipped".format(i, name, n_in, n_out))
-                continue
-            if ks < 1 or k0 + n_out * ks > len(coef) or b0 + 2 * n_out > len(coef):
-                raise ValueError("sample {}: {} coefficient index outside the coefficient buffer".format(i, name))
-            b = coef[b0:b0 + 2 * n_out].reshape(-1, 2).astype(np.int64)
-            if (b[:, 0] < 0).any() or (b[:, 1] < 1).any() or (b[:, 1] > ks).any() or (b.sum(1) > n_in).any():
-                raise ValueError("sample {}: a {} tap lies outside the mask or the coefficient row".format(i, name))
-            if (np.diff(b[:, 0]) < 0).any() or (np.diff(b.sum(1)) < 0).any():
-                raise ValueError("sample {}: {} tap windows must not move backwards".format(i, name))
+        for name, block, n_in, n_out in (("horizontal", t[i, 6:9], mw, w[i]), ("vertical", t[i, 9:12], mh, h[i])):
+            check_pass(coef, block, n_in, n_out, "sample {}".format(i), name)
     return off, tab, coef
 
 

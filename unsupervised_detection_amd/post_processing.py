@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from ._ffi import c_f, c_i, c_p, c_sz, check, lib, sig
+from .pil_tables import CoefBlocks, check_pass, pil_coeffs_host as _pil_coeffs_host
 from .ragged import INT32_MAX, PackedLayout, as_layout, check_ranges, require_tensor, upload_tables, workspace
 
 c_d = ctypes.c_double
@@ -76,34 +77,6 @@ def _as_mask(m):
 
 # ---------------------------------------------------------------------------------------------- Pillow coefficients ----
 _coeff_cache = {}
-
-
-def _pil_coeffs_host(in_size: int, out_size: int):
-    """Pillow Resample.c precompute_coeffs + normalize_coeffs_8bpc for the BILINEAR filter (host side, exactly Pillow's double
-    arithmetic): int32 arrays kk [out][ksize] and bounds [out][2] = (first tap, taps), and ksize."""
-    scale = filterscale = in_size / out_size
-    if filterscale < 1.0:
-        filterscale = 1.0
-    support = 1.0 * filterscale
-    ksize = int(math.ceil(support)) * 2 + 1
-    kk = np.zeros((out_size, ksize), np.int32)
-    bounds = np.zeros((out_size, 2), np.int32)
-    ss = 1.0 / filterscale
-    for xx in range(out_size):
-        center = (xx + 0.5) * scale
-        xmin = max(int(center - support + 0.5), 0)
-        xmax = min(int(center + support + 0.5), in_size) - xmin
-        w = [0.0] * ksize
-        ww = 0.0
-        for x in range(xmax):
-            v = abs((x + xmin - center + 0.5) * ss)
-            w[x] = 1.0 - v if v < 1.0 else 0.0
-            ww += w[x]
-        for x in range(ksize):
-            v = w[x] / ww if (x < xmax and ww != 0.0) else w[x]
-            kk[xx, x] = int(-0.5 + v * (1 << 22)) if v < 0 else int(0.5 + v * (1 << 22))
-        bounds[xx] = (xmin, xmax)
-    return kk, bounds, ksize
 
 
 def _pil_coeffs(in_size: int, out_size: int):
@@ -201,7 +174,7 @@ _soft_tables = {}
 def soft_score_geometry(ns, crops, base_crop, base_hw):
     """The tables of udet_post_soft_score_batch (pure host): geom int32 [ns * len(crops), SOFT_SCORE_GEOM], one row per (shift index, crop
     index) with rectify_pred_mask's integer rules (int(H * crop), int((H - hh) / 2), max(..., 0), the crop > 1 branch), and coef int32, the
-    concatenated _pil_coeffs_host blocks (kk then bounds, one pair per distinct (in, out) size) the rows' offsets point into.  Row layout:
+    concatenated coefficient blocks of pil_tables.CoefBlocks (kk then bounds, one pair per distinct (in, out) size) the rows' offsets point into.  Row layout:
     mode (0: shift 1 at the base crop, the raw masks; 1: rectify), the source window (sy0, sx0, sh, sw) inside the mask, the patch (hh, ww)
     and where it lands (y0, x0), then (kk offset, bounds offset, ksize) of the horizontal and of the vertical pass, a negative offset for a
     pass whose output is as long as its input."""
@@ -210,17 +183,7 @@ def soft_score_geometry(ns, crops, base_crop, base_hw):
     if ns < 1 or nc < 1 or H < 1 or W < 1:
         raise ValueError("soft_score_geometry: at least one shift, one crop and a frame of 1 x 1")
     geom = np.zeros((ns * nc, SOFT_SCORE_GEOM), np.int32)
-    blocks, where = [], {}
-
-    def one_pass(n_in, n_out):
-        if n_in == n_out:
-            return (-1, -1, 0)
-        if (n_in, n_out) not in where:
-            kk, bounds, ks = _pil_coeffs_host(n_in, n_out)
-            pos = sum(len(b) for b in blocks)
-            where[(n_in, n_out)] = (pos, pos + kk.size, ks)
-            blocks.extend([kk.reshape(-1), bounds.reshape(-1)])
-        return where[(n_in, n_out)]
+    blocks = CoefBlocks()
     for si in range(ns):
         for ci, crop in enumerate(crops):
             r = si * nc + ci
@@ -239,9 +202,8 @@ def soft_score_geometry(ns, crops, base_crop, base_hw):
             if hh < 1 or ww < 1:
                 raise ValueError("soft-score geometry row {} (shift {}, crop {}): a frame of {} x {} leaves no pixel".format(r, si + 1, crop, H, W))
             geom[r, :9] = (1,) + win + patch
-            geom[r, 9:15] = one_pass(win[3], patch[1]) + one_pass(win[2], patch[0])
-    coef = np.concatenate(blocks).astype(np.int32) if blocks else np.zeros(1, np.int32)  # (never empty: the call takes no NULL table)
-    return geom, coef
+            geom[r, 9:15] = blocks.block(win[3], patch[1]) + blocks.block(win[2], patch[0])
+    return geom, blocks.coef()
 
 
 def check_soft_score_tables(geom, coef, base_hw):
@@ -266,17 +228,8 @@ def check_soft_score_tables(geom, coef, base_hw):
             raise ValueError("soft-score geometry row {}: the source window {}x{} at ({}, {}) leaves the {}x{} frame".format(r, sh, sw, sy0, sx0, H, W))
         if min(y0, x0) < 0 or min(hh, ww) < 1 or y0 + hh > H or x0 + ww > W:
             raise ValueError("soft-score geometry row {}: the patch {}x{} at ({}, {}) leaves the {}x{} canvas".format(r, hh, ww, y0, x0, H, W))
-        for name, (k, b, ks), n_in, n_out in (("horizontal", row[9:12], sw, ww), ("vertical", row[12:15], sh, hh)):
-            if k < 0:
-                if n_in != n_out:
-                    raise ValueError("soft-score geometry row {}: the {} pass {} -> {} cannot be skipped".format(r, name, n_in, n_out))
-                continue
-            if ks < 1 or b < 0 or k + n_out * ks > len(co) or b + 2 * n_out > len(co):
-                raise ValueError("soft-score geometry row {}: the {} coefficient block leaves coef".format(r, name))
-            lo, cnt = co[b:b + 2 * n_out].reshape(-1, 2).T
-            if (lo < 0).any() or (cnt < 1).any() or (cnt > ks).any() or (lo + cnt > n_in).any() or (np.diff(lo) < 0).any() or \
-                    (np.diff(lo + cnt) < 0).any():
-                raise ValueError("soft-score geometry row {}: a tap of the {} pass leaves the window of {}".format(r, name, n_in))
+        for name, block, n_in, n_out in (("horizontal", row[9:12], sw, ww), ("vertical", row[12:15], sh, hh)):
+            check_pass(co, block, n_in, n_out, "soft-score geometry row {}".format(r), name)
     return g.astype(np.int32), co.astype(np.int32)
 
 
