@@ -206,6 +206,58 @@ int udet_component_boxes_ragged(const int* labels, const unsigned char* score, i
 int udet_draw_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
                            const long long* dets, const long long* counts, int k, int thickness, unsigned rgb, void* stream);
 
+/* Detections linked into tracks across consecutive frames, by mask overlap.  labels / offsets / hw / max_h / max_w /
+ * total_pixels: the packed device int32 labels of n frames as for udet_component_boxes_ragged (a value outside 0..H_i*W_i is background);
+ * dets / counts / k: what udet_component_boxes_ragged wrote for those labels, read on the device; rows_i = counts[i][2] clamped to 0..k.
+ * link: device int32 [n]; link[i] != 0: frame i continues frame i - 1 (frame 0: the carried frame), link[i] = 0: frame i starts a
+ * sequence, so one call may hold several sequences.  The carried frame, the tail of the previous call, is optional: carry_labels (device
+ * int32, carry_h x carry_w), carry_dets (its k rows, int64 [k][UDET_DET_FIELDS]), carry_counts (int64 [3], its counts row), carry_ids
+ * (int32 [k], the track ids of its rows) and carry_next_id (int32 [1], the next free id of its sequence); absent: every one NULL and
+ * carry_h = carry_w = 0, and link[0] is then taken as 0.  A frame is linked when link says so and its predecessor has its H x W;
+ * linked (device int32 [n]) reports it as 1, else 0.  For a linked frame c with predecessor p, a < rows_p and b < rows_c, exact integers:
+ *  - inter[c][a][b] (device int64 [n][k][k]) = the number of positions where labels_p = root_a + 1 and labels_c = root_b + 1; every other
+ *    entry, and every entry of a frame that is not linked, is 0.
+ *  - union = area_a + area_b - inter (areas from dets); (a, b) is a candidate when inter > 0 and 1000 inter >= min_iou_permille union.
+ *  - greedy matching: repeatedly the candidate with the largest inter / union among rows still free on both sides, compared by 64-bit
+ *    cross-multiplication, ties to the smaller a, then to the smaller b.  match[c][b] (device int32 [n][k]) = a, or -1 for an unmatched
+ *    row, a row past rows_c and a frame that is not linked.
+ *  - ids (device int32 [n][k]), per sequence from 0: a sequence's first frame gives its rows 0 .. rows - 1 in rank order; in a linked
+ *    frame a matched row inherits ids[p][a] and the unmatched rows take the next free ids in rank order; rows past rows_c get -1.  A
+ *    sequence that continues the carried frame starts from carry_ids and carry_next_id.  A component that vanishes for a frame comes back
+ *    under a new id.
+ *  - seq_tracks (device int32 [n]): at a sequence's last frame within the call the number of ids handed out so far, elsewhere 0;
+ *    next_id (device int32 [1]): that number for the call's last sequence -- the carry_next_id of the call that continues it.
+ * Four launches whatever n and the number of sequences and components: zero inter and enter every row's rank at its root in the
+ * workspace; the overlap pass over every pixel of every linked frame (a rows_p x rows_c histogram in LDS, one LDS atomic per
+ * horizontal run of a wave, then one 64-bit integer atomic per non-zero entry per workgroup); one workgroup per linked frame matches; one
+ * wave per sequence walks its frames and hands out the ids.  No host round trip, no workgroup waits for another, integer atomics only:
+ * identical from run to run and for a sequence alone or inside a batch.
+ * workspace: udet_link_detections_workspace_bytes(total_pixels, n, k, carry_h, carry_w) bytes (4 per pixel, the carried frame's
+ * included), 4-byte aligned.  UDET_ERR_ARG, nothing enqueued: a NULL labels / offsets / hw / dets / counts / link or output, n outside
+ * 1..65535, max_h or max_w < 1, total_pixels < 1, k outside 1..UDET_DET_MAX_K, min_iou_permille outside 1..1000, a carried frame that is
+ * neither absent nor whole, a short or misaligned workspace, an int32 buffer not 4-byte or dets / counts / inter not 8-byte aligned.
+ * The tables are device memory: the host caller validates them before the launch (native_results.link_detections); every index a kernel
+ * forms is bounded whatever labels, dets, counts and the workspace hold. */
+size_t udet_link_detections_workspace_bytes(size_t total_pixels, int n, int k, int carry_h, int carry_w);
+int udet_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* The boxes of the written detections painted in the colour of their track, in place: the contract of udet_draw_boxes_ragged with two
+ * differences.  The colour of row r of sample i is palette[ids[i][r] mod palette_size] (ids: device int32 [n][k], what
+ * udet_link_detections_ragged wrote; palette: device uint32 [palette_size], 0xRRGGBB, palette_size in 1..UDET_TRACK_MAX_PALETTE), and a
+ * row whose id is -1 is not painted.  Where the lines of several painted boxes cover a pixel the smallest rank wins: a workgroup per
+ * (row, sample) skips every pixel that lies on the line of a painted lower-ranked box, so the result does not depend on the order in
+ * which workgroups run.  One launch.  UDET_ERR_ARG, nothing enqueued: a NULL pointer, n outside 1..65535, total_pixels < 1, k outside
+ * 1..UDET_DET_MAX_K, thickness outside 1..8, palette_size outside 1..64, misaligned dets / counts / ids / palette. */
+#define UDET_TRACK_MAX_PALETTE 64
+int udet_draw_track_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
+                                 const long long* dets, const long long* counts, int k, const int* ids, int thickness,
+                                 const unsigned* palette, int palette_size, void* stream);
+
 /* Dense CRF of a ragged batch at each frame's own size: step 2 of post_processing/crf_refine.py:65-108 run_crf_original_resolution
  * (DenseCRF2D + setUnaryEnergy + addPairwiseBilateral(sxy, srgb, rgbim, compat) + inference(iters) on the untouched frame).  Packed
  * layout of the two calls above: sample i = H_i x W_i elements at element offset offsets[i] (device int64 [n]); hw: device int32 [n][2].

@@ -80,6 +80,11 @@ sig("udet_overlay_native_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, 
 sig("udet_component_boxes_workspace_bytes", c_sz, c_sz, c_i, c_i)
 sig("udet_component_boxes_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_i, c_i, c_p, c_p, c_p, c_sz, c_p)
 sig("udet_draw_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_i, ctypes.c_uint, c_p)
+# detections linked into tracks (native_results.link_detections, visualize.draw_track_boxes)
+sig("udet_link_detections_workspace_bytes", c_sz, c_sz, c_i, c_i, c_i, c_i)
+sig("udet_link_detections_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i,
+    c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_draw_track_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p)
 sig("udet_histogram_limits", c_i, c_p, c_i)
 sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
 sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)

@@ -65,7 +65,11 @@ in --overlay_edge_colour -- into <out>/overlay/<sequence>/<frame>.png (visualize
 after the CRF, before --component -- is reported as a box, the largest first, at most --det_max (1..64) per frame: box [x0, y0, x1, y1],
 area, centroid, score (the mean restored soft mask over the component) and root, in <out>/detections/<sequence>.json
 (native_results.component_boxes).  --overlay_boxes (needs --overlay and --detections) also paints the boxes on the overlays,
---overlay_box_thickness (1..8) pixels wide in --overlay_box_colour (visualize.draw_boxes).  Like the
+--overlay_box_thickness (1..8) pixels wide in --overlay_box_colour (visualize.draw_boxes).  --tracks (needs --detections) links the
+detections of consecutive frames of a sequence by mask overlap -- a box continues the box of the frame before it with which its component
+shares the largest IoU, at least --track_min_iou (0.1) -- and numbers the tracks per sequence: the records gain track / prev / iou,
+<out>/tracks/<sequence>.json lists every track, and --overlay_boxes paints each box in its track's colour
+(native_results.link_detections, visualize.draw_track_boxes).  Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
 runs)."""
@@ -165,6 +169,8 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--overlay_boxes", action="store_true", help="with --overlay and --detections: also paint the boxes on the overlays")
     ap.add_argument("--overlay_box_thickness", type=int, default=2, help="width of a box's line in pixels, 1..8 (inward)")
     ap.add_argument("--overlay_box_colour", default="255,255,0", help="r,g,b of the boxes")
+    ap.add_argument("--tracks", action="store_true", help="with --detections: link the boxes of consecutive frames: <out>/tracks/<sequence>.json")
+    ap.add_argument("--track_min_iou", type=float, default=0.1, help="the smallest mask IoU that links two boxes")
 
 
 def _overlay(flags):
@@ -200,6 +206,20 @@ def _detections(flags):
         return detection_params({"min_area": flags.det_min_area, "max_detections": flags.det_max})
     except ValueError as e:
         raise SystemExit("--detections: {} (--det_min_area / --det_max)".format(e))
+
+
+def _tracks(flags):
+    """--tracks and its parameter as restore_results_dir takes them: None without --tracks.  --tracks without --detections, or a bad
+    value, is a SystemExit."""
+    if not getattr(flags, "tracks", False):
+        return None
+    if not getattr(flags, "detections", False):
+        raise SystemExit("--tracks links the detections of consecutive frames: it needs --detections")
+    from .native_results import track_params
+    try:
+        return track_params({"min_iou": flags.track_min_iou})
+    except ValueError as e:
+        raise SystemExit("--tracks: {} (--track_min_iou)".format(e))
 
 
 def check_frames_component(flags):
@@ -254,6 +274,7 @@ def parse_restore_results_args(argv):
     check_frames_component(flags)
     _overlay(flags)
     _detections(flags)
+    _tracks(flags)
     return flags
 
 
@@ -294,6 +315,7 @@ def parse_post_process_args(argv):
         check_frames_component(flags)
         _overlay(flags)
         _detections(flags)
+        _tracks(flags)
     return flags
 
 
@@ -342,6 +364,8 @@ def post_process(a):
         more = {} if overlay is None else {"overlay": overlay}
         if detections is not None:
             more.update(detections=detections, connectivity=a.connectivity)
+        if _tracks(a) is not None:
+            more.update(tracks=_tracks(a))
         report["benchmark"] = pp.run_crf_original_resolution(resized, frame_lists_from_reader(a), a.native_sxy, a.srgb, a.scomp, a.gauss_k,
                                                              out_path=original, component=_component(a), gt_rule=a.dataset, **more)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -376,6 +400,7 @@ def check_native_flags(flags):
         check_frames_component(flags)
         _overlay(flags)
         _detections(flags)
+        _tracks(flags)
 
 
 def main(argv=None):
@@ -391,7 +416,7 @@ def main(argv=None):
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
                             batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
-                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a))
+                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -420,7 +445,7 @@ def main(argv=None):
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
                                 connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags),
-                                detections=_detections(flags))
+                                detections=_detections(flags), tracks=_tracks(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

@@ -64,6 +64,10 @@ _DEFS = [
     ("overlay_boxes", bool, False),
     ("overlay_box_thickness", int, 2),
     ("overlay_box_colour", str, "255,255,0"),
+    # not reference flags: with --native_resolution and --detections, --tracks links the boxes of consecutive frames by mask overlap (IoU
+    # at least track_min_iou) into D/native/tracks/<sequence>.json (native_results.link_detections)
+    ("tracks", bool, False),
+    ("track_min_iou", float, 0.1),
 ]
 
 

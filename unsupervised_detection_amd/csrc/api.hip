@@ -208,6 +208,78 @@ int udet_draw_boxes_ragged(unsigned char* image_rgb, int n, const long long* off
   return launch_draw_boxes_ragged(image_rgb, n, offsets, hw, dets, counts, k, thickness, rgb, (hipStream_t)stream);
 }
 
+// the carried frame of udet_link_detections_ragged: absent (no pointer, 0 x 0) or whole (every pointer, at least 1 x 1, below 2^31 pixels)
+static bool link_carry_ok(const void* labels, int h, int w, const void* dets, const void* counts, const void* ids, const void* next_id) {
+  if (!labels && !dets && !counts && !ids && !next_id) return h == 0 && w == 0;
+  return labels && dets && counts && ids && next_id && h >= 1 && w >= 1 && (long)h * w <= 0x7fffffffL;
+}
+size_t udet_link_detections_workspace_bytes(size_t total_pixels, int n, int k, int carry_h, int carry_w) {
+  const bool carry = carry_h != 0 || carry_w != 0;
+  if (n < 1 || total_pixels < 1 || k < 1 || k > UDET_DET_MAX_K) return 0;
+  if (carry && (carry_h < 1 || carry_w < 1 || (long)carry_h * carry_w > 0x7fffffffL)) return 0;
+  return link_detections_workspace_bytes(total_pixels, carry_h, carry_w);
+}
+int udet_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  if (bad_batch("link_detections_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!labels || !offsets || !hw || !dets || !counts || !link || !inter || !match || !ids || !linked || !seq_tracks || !next_id) {
+    set_error("link_detections_ragged: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)");
+    return UDET_ERR_ARG;
+  }
+  if (k < 1 || k > UDET_DET_MAX_K || min_iou_permille < 1 || min_iou_permille > 1000) {
+    set_error("link_detections_ragged: k = %d in 1..UDET_DET_MAX_K = %d and min_iou_permille = %d in 1..1000 are required", k,
+              UDET_DET_MAX_K, min_iou_permille);
+    return UDET_ERR_ARG;
+  }
+  if (!link_carry_ok(carry_labels, carry_h, carry_w, carry_dets, carry_counts, carry_ids, carry_next_id)) {
+    set_error("link_detections_ragged: the carried frame is either absent (no pointer, 0 x 0) or whole (labels, dets, counts, ids and "
+              "next id, %d x %d at least 1 x 1 and below 2^31 pixels)", carry_h, carry_w);
+    return UDET_ERR_ARG;
+  }
+  if (bad_workspace("link_detections_ragged", workspace, workspace_bytes, link_detections_workspace_bytes(total_pixels, carry_h, carry_w), 4))
+    return UDET_ERR_ARG;
+  const uintptr_t a4 = reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(link) | reinterpret_cast<uintptr_t>(carry_labels) |
+                       reinterpret_cast<uintptr_t>(carry_ids) | reinterpret_cast<uintptr_t>(carry_next_id) |
+                       reinterpret_cast<uintptr_t>(match) | reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(linked) |
+                       reinterpret_cast<uintptr_t>(seq_tracks) | reinterpret_cast<uintptr_t>(next_id);
+  const uintptr_t a8 = reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(carry_dets) |
+                       reinterpret_cast<uintptr_t>(carry_counts) | reinterpret_cast<uintptr_t>(inter);
+  if ((a4 & 3) || (a8 & 7)) {
+    set_error("link_detections_ragged: the int32 buffers must be 4-byte aligned, dets, counts and inter 8-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_link_detections_ragged(labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k, link, carry_labels, carry_h,
+                                       carry_w, carry_dets, carry_counts, carry_ids, carry_next_id, min_iou_permille, inter, match, ids,
+                                       linked, seq_tracks, next_id, workspace, (hipStream_t)stream);
+}
+
+int udet_draw_track_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
+                                 const long long* dets, const long long* counts, int k, const int* ids, int thickness,
+                                 const unsigned* palette, int palette_size, void* stream) {
+  if (bad_batch("draw_track_boxes_ragged", n, 1, 1, total_pixels)) return UDET_ERR_ARG;
+  if (!image_rgb || !offsets || !hw || !dets || !counts || !ids || !palette) {
+    set_error("draw_track_boxes_ragged: bad argument (non-null image_rgb, offsets, hw, dets, counts, ids and palette)");
+    return UDET_ERR_ARG;
+  }
+  if (k < 1 || k > UDET_DET_MAX_K || thickness < 1 || thickness > UDET_DRAW_MAX_THICKNESS || palette_size < 1 ||
+      palette_size > UDET_TRACK_MAX_PALETTE) {
+    set_error("draw_track_boxes_ragged: k = %d in 1..UDET_DET_MAX_K = %d, thickness = %d in 1..%d and a palette of %d in 1..%d colours are "
+              "required", k, UDET_DET_MAX_K, thickness, UDET_DRAW_MAX_THICKNESS, palette_size, UDET_TRACK_MAX_PALETTE);
+    return UDET_ERR_ARG;
+  }
+  if (((reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts)) & 7) ||
+      ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(palette)) & 3)) {
+    set_error("draw_track_boxes_ragged: dets and counts must be 8-byte aligned, ids and palette 4-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_draw_track_boxes_ragged(image_rgb, n, offsets, hw, dets, counts, k, ids, thickness, palette, palette_size,
+                                        (hipStream_t)stream);
+}
+
 size_t udet_conv2d_workspace_bytes(int n, int h, int w, int cin, int cout, int kh, int kw, int upsample2x) {
   const int kc = round_up(cin > cout ? cin : cout, 8), ldw = round_up(cin > cout ? cin : cout, 4);
   const size_t pix_in = (size_t)n * h * w, pix_out = pix_in * (upsample2x ? 4 : 1);

@@ -20,26 +20,16 @@
 // that are no valid labelling still give each distinct value its own exact sums.
 #include "common.h"
 #include "elementwise.h"
+#include "wave_runs.h"
 
 namespace udet {
 
-#define DET_PPT 8      // pixels per thread of the pixel grids
+#define DET_PPT 8     // pixels per thread of the pixel grids
 #define DET_K UDET_DET_MAX_K
 #define DET_ACC 7      // accumulated per winner: y0, x0, y1, x1 (min / max), sum_y, sum_x, score_sum (add)
 #define DET_NONE 0x7fffffff
 
 static_assert(DET_K <= 64 && UDET_DET_FIELDS == 2 + DET_ACC, "row layout of include/udet.h");
-
-// The horizontal run of equal ids (id >= 0) that starts at this lane, for 64 consecutive pixels of one sample: its length, or 0 where
-// the lane does not start one.  x: the pixel's column (a run ends at the row's end).  Every lane of the wave calls this.
-__device__ __forceinline__ int det_run_length(int id, int x, int lane) {
-  const int prev = __shfl_up(id, 1);
-  const bool cont = id >= 0 && lane != 0 && x != 0 && prev == id;
-  const unsigned long long mcont = __ballot(cont);
-  if (id < 0 || cont) return 0;
-  const unsigned long long rest = lane == 63 ? 0ull : (mcont >> (lane + 1));  // the top bit of rest is 0: ~rest is never 0
-  return __ffsll((long long)~rest);                                          // 1 + the lanes after this one that continue the run
-}
 
 __global__ __launch_bounds__(256) void det_init_kernel(int* __restrict__ area, size_t total_pixels, int* __restrict__ counters, int n) {
   const size_t stride = (size_t)gridDim.x * 256;

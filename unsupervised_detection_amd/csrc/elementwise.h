@@ -60,6 +60,17 @@ int launch_component_boxes_ragged(const int* labels, const unsigned char* score,
                                   hipStream_t s);
 int launch_draw_boxes_ragged(unsigned char* rgb, int n, const long long* offsets, const int* hw, const long long* dets,
                              const long long* counts, int k, int thickness, unsigned colour, hipStream_t s);
+// tracks.hip: udet_link_detections_ragged / udet_draw_track_boxes_ragged (arguments already checked)
+size_t link_detections_workspace_bytes(size_t total_pixels, int carry_h, int carry_w);
+int launch_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                  size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                  const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                  const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
+                                  hipStream_t s);
+int launch_draw_track_boxes_ragged(unsigned char* rgb, int n, const long long* offsets, const int* hw, const long long* dets,
+                                   const long long* counts, int k, const int* ids, int thickness, const unsigned* palette,
+                                   int palette_size, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
 int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet

@@ -1,0 +1,325 @@
+// Detections linked into tracks across consecutive frames: udet_link_detections_ragged takes the labels components.hip
+// wrote for n frames (packed layout, sample i = H_i x W_i int32 at offsets[i]) and the dets / counts detections.hip wrote for them, counts
+// for every linked frame the pixels its rows share with the rows of the frame before it, matches the rows greedily by mask IoU and hands
+// out track ids per sequence; udet_draw_track_boxes_ragged paints the boxes in the colour of their track.  Four launches for the link
+// however many frames, sequences and components there are:
+//   1. link_init_kernel     zeroes `inter`, writes every row's rank at its root into the workspace (one int32 per pixel, written at the
+//                           winners' roots only and never zeroed: a lookup counts only when the row it names holds that root) and decides
+//                           `linked`
+//   2. link_overlap_kernel  every pixel of every linked frame: two labels, two lookups, the pair (a, b) of ranks; one LDS atomic per
+//                           horizontal run of a wave into the workgroup's k x k histogram, then one 64-bit integer atomic per non-zero
+//                           entry straight into `inter`
+//   3. link_match_kernel    one workgroup per linked frame: the candidates (inter > 0, IoU at or above the threshold) into LDS, then at most
+//                           min(rows_p, rows_c) rounds of a block arg-max over the entries whose rows are both free
+//   4. link_ids_kernel      one wave per sequence (the wave of the sequence's first frame; the others leave at once), one lane per row:
+//                           a matched row takes its predecessor's id by a shuffle, the unmatched rows the next free ids by a ballot prefix
+// Integer work only, no workgroup waits for another: the outputs are exact, identical from run to run and for a sequence alone or inside
+// a batch.  A label outside 1..H_i*W_i is background and a root outside 0..H_i*W_i-1 is not entered, so nothing indexes outside its own
+// sample whatever labels and dets hold; every other index comes from offsets / hw, which the caller validates on the host
+// (native_results.link_detections), and from ranks clamped to k.
+#include "common.h"
+#include "elementwise.h"
+#include "wave_runs.h"
+
+namespace udet {
+
+#define LINK_PPT 16    // pixels per thread of the overlap grid: 4096 pixels per workgroup and pass amortise the flush of k x k entries
+#define LINK_K UDET_DET_MAX_K
+#define LINK_NONE 0x7fffffff
+
+static_assert(LINK_K <= 64, "one lane per row in link_ids_kernel");
+
+// rows written for a frame, whatever its counts hold: 0..k
+__device__ __forceinline__ int link_rows(const long long* __restrict__ counts3, int k) {
+  const long long r = counts3[2];
+  return r < 0 ? 0 : r > k ? k : (int)r;
+}
+
+// What a frame is linked against: the frame before it in the call, or the carried frame for the call's first one.
+struct LinkCarry {
+  const int* labels;        // carry_h x carry_w, or nullptr: no carried frame
+  const long long* dets;    // [k][UDET_DET_FIELDS]
+  const long long* counts;  // [3]
+  const int* ids;           // [k]
+  const int* next_id;       // [1]
+  int h, w;
+};
+
+__device__ __forceinline__ void link_enter_roots(const long long* __restrict__ dets, int rows, long long HW, int* __restrict__ lookup,
+                                                 int r) {
+  if (r >= rows) return;
+  const long long root = dets[(size_t)r * UDET_DET_FIELDS];
+  if (root >= 0 && root < HW) lookup[root] = r;
+}
+
+__global__ __launch_bounds__(256) void link_init_kernel(int n, const long long* __restrict__ offsets, const int* __restrict__ hw,
+                                                        size_t total_pixels, const long long* __restrict__ dets,
+                                                        const long long* __restrict__ counts, int k, const int* __restrict__ link,
+                                                        LinkCarry carry, unsigned long long* __restrict__ inter,
+                                                        int* __restrict__ linked, int* __restrict__ lookup) {
+  const size_t stride = (size_t)gridDim.x * 256, g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t cells = (size_t)n * k * k;
+  for (size_t j = g; j < cells; j += stride) inter[j] = 0;
+  for (size_t j = g; j < (size_t)n * k; j += stride) {
+    const int i = (int)(j / k), r = (int)(j - (size_t)i * k);
+    link_enter_roots(dets + (size_t)i * k * UDET_DET_FIELDS, link_rows(counts + 3 * i, k), (long long)hw[2 * i] * hw[2 * i + 1],
+                     lookup + offsets[i], r);
+  }
+  if (carry.labels)
+    for (size_t r = g; r < (size_t)k; r += stride)
+      link_enter_roots(carry.dets, link_rows(carry.counts, k), (long long)carry.h * carry.w, lookup + total_pixels, (int)r);
+  for (size_t i = g; i < (size_t)n; i += stride) {
+    const int H = hw[2 * i], W = hw[2 * i + 1];
+    const bool same = i ? (hw[2 * i - 2] == H && hw[2 * i - 1] == W) : (carry.labels && carry.h == H && carry.w == W);
+    linked[i] = (link[i] != 0 && same) ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict__ labels, const long long* __restrict__ offsets,
+                                                           const int* __restrict__ hw, size_t total_pixels,
+                                                           const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
+                                                           LinkCarry carry, const int* __restrict__ linked, const int* __restrict__ lookup,
+                                                           unsigned long long* __restrict__ inter) {
+  extern __shared__ int link_lds[];  // hist [k * k], root_p [k], root_c [k]
+  const int i = blockIdx.y, t = threadIdx.x, lane = t & 63;
+  if (!linked[i]) return;  // block-uniform; a linked frame 0 has a carried frame of its size
+  int* __restrict__ hist = link_lds;
+  int* __restrict__ root_p = link_lds + k * k;
+  int* __restrict__ root_c = root_p + k;
+  const int W = hw[2 * i + 1];
+  const long long HW = (long long)hw[2 * i] * W;  // the predecessor's too
+  const size_t oc = (size_t)offsets[i], op = i ? (size_t)offsets[i - 1] : total_pixels;
+  const int* __restrict__ lab_c = labels + oc;
+  const int* __restrict__ lab_p = i ? labels + op : carry.labels;
+  const long long* __restrict__ dets_c = dets + (size_t)i * k * UDET_DET_FIELDS;
+  const long long* __restrict__ dets_p = i ? dets_c - (size_t)k * UDET_DET_FIELDS : carry.dets;
+  const int rows_c = link_rows(counts + 3 * i, k), rows_p = link_rows(i ? counts + 3 * i - 3 : carry.counts, k);
+  for (int j = t; j < k * k; j += 256) hist[j] = 0;
+  for (int j = t; j < k; j += 256) {
+    root_p[j] = j < rows_p ? (int)dets_p[(size_t)j * UDET_DET_FIELDS] : -1;  // a root >= 2^31 matches no label
+    root_c[j] = j < rows_c ? (int)dets_c[(size_t)j * UDET_DET_FIELDS] : -1;
+  }
+  __syncthreads();
+  for (long long base = (long long)blockIdx.x * 256; base < HW; base += (long long)gridDim.x * 256) {  // block-uniform bounds
+    const long long p = base + t;
+    const bool valid = p < HW;
+    const int vp = valid ? lab_p[p] : 0, vc = valid ? lab_c[p] : 0;
+    int a = -1, b = -1;
+    if (vp >= 1 && vp <= HW && vc >= 1 && vc <= HW) {
+      const int ra = lookup[op + vp - 1], rb = lookup[oc + vc - 1];  // never zeroed: only a rank whose row holds this root counts
+      if ((unsigned)ra < (unsigned)rows_p && root_p[ra] == vp - 1) a = ra;
+      if ((unsigned)rb < (unsigned)rows_c && root_c[rb] == vc - 1) b = rb;
+    }
+    const int pair = (a >= 0 && b >= 0) ? a * k + b : -1;
+    const int len = det_run_length(pair, valid ? (int)(p % W) : 0, lane);
+    if (len) atomicAdd(hist + pair, len);  // a workgroup sees fewer than 2^31 pixels
+  }
+  __syncthreads();
+  for (int j = t; j < k * k; j += 256)
+    if (hist[j]) atomicAdd(inter + (size_t)i * k * k + j, (unsigned long long)hist[j]);
+}
+
+// (inter, union, entry) of the better of two candidates: the larger inter / union by 64-bit cross-multiplication (inter < 2^31, union <
+// 2^32), ties to the smaller entry a * k + b -- the smaller a, then the smaller b.  (0, 1, LINK_NONE): none.
+__device__ __forceinline__ bool link_better(int i1, unsigned u1, int j1, int i2, unsigned u2, int j2) {
+  const unsigned long long p1 = (unsigned long long)i1 * u2, p2 = (unsigned long long)i2 * u1;
+  return p1 > p2 || (p1 == p2 && j1 < j2);
+}
+
+__global__ __launch_bounds__(256) void link_match_kernel(const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
+                                                         LinkCarry carry, const int* __restrict__ linked,
+                                                         const long long* __restrict__ inter, int permille, int* __restrict__ match) {
+  extern __shared__ int link_lds[];  // inter of the candidates [k * k] (0: none), their unions [k * k], free_p [k], free_c [k], match [k]
+  __shared__ int wi[4], wj[4];
+  __shared__ unsigned wu[4];
+  const int i = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  int* __restrict__ sint = link_lds;
+  unsigned* __restrict__ suni = (unsigned*)(link_lds + k * k);
+  int* __restrict__ free_p = link_lds + 2 * k * k;
+  int* __restrict__ free_c = free_p + k;
+  int* __restrict__ smatch = free_c + k;
+  if (!linked[i]) {  // block-uniform
+    for (int b = t; b < k; b += 256) match[(size_t)i * k + b] = -1;
+    return;
+  }
+  const long long* __restrict__ dets_c = dets + (size_t)i * k * UDET_DET_FIELDS;
+  const long long* __restrict__ dets_p = i ? dets_c - (size_t)k * UDET_DET_FIELDS : carry.dets;
+  const int rows_c = link_rows(counts + 3 * i, k), rows_p = link_rows(i ? counts + 3 * i - 3 : carry.counts, k);
+  for (int j = t; j < k * k; j += 256) {
+    const int a = j / k, b = j - a * k;
+    const long long v = inter[(size_t)i * k * k + j];
+    int keep = 0;
+    unsigned uni = 1;
+    if (a < rows_p && b < rows_c && v > 0 && v <= 0x7fffffffLL) {
+      const long long u = dets_p[(size_t)a * UDET_DET_FIELDS + 1] + dets_c[(size_t)b * UDET_DET_FIELDS + 1] - v;  // area_a + area_b - inter
+      if (u > 0 && u <= 0xffffffffLL && 1000 * v >= (long long)permille * u) { keep = (int)v; uni = (unsigned)u; }
+    }
+    sint[j] = keep;
+    suni[j] = uni;
+  }
+  for (int j = t; j < k; j += 256) { free_p[j] = 1; free_c[j] = 1; smatch[j] = -1; }
+  __syncthreads();
+  const int rounds = rows_p < rows_c ? rows_p : rows_c;
+  for (int round = 0; round < rounds; ++round) {  // block-uniform: every thread sees the same winner
+    int bi = 0, bj = LINK_NONE;
+    unsigned bu = 1;
+    for (int j = t; j < k * k; j += 256) {
+      const int v = sint[j];
+      if (!v) continue;
+      const int a = j / k;
+      if (free_p[a] && free_c[j - a * k] && link_better(v, suni[j], j, bi, bu, bj)) { bi = v; bu = suni[j]; bj = j; }
+    }
+    for (int s = 32; s > 0; s >>= 1) {
+      const int oi = __shfl_xor(bi, s), oj = __shfl_xor(bj, s);
+      const unsigned ou = __shfl_xor(bu, s);
+      if (link_better(oi, ou, oj, bi, bu, bj)) { bi = oi; bu = ou; bj = oj; }
+    }
+    if (lane == 0) { wi[t >> 6] = bi; wu[t >> 6] = bu; wj[t >> 6] = bj; }
+    __syncthreads();
+    bi = wi[0]; bu = wu[0]; bj = wj[0];
+    for (int w = 1; w < 4; ++w)
+      if (link_better(wi[w], wu[w], wj[w], bi, bu, bj)) { bi = wi[w]; bu = wu[w]; bj = wj[w]; }
+    if (bi == 0) break;  // no candidate between free rows is left
+    if (t == 0) {
+      const int a = bj / k, b = bj - a * k;
+      smatch[b] = a; free_p[a] = 0; free_c[b] = 0;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+  for (int b = t; b < k; b += 256) match[(size_t)i * k + b] = smatch[b];
+}
+
+__global__ __launch_bounds__(64) void link_ids_kernel(int n, const long long* __restrict__ counts, int k, LinkCarry carry,
+                                                      const int* __restrict__ linked, const int* __restrict__ match,
+                                                      int* __restrict__ ids, int* __restrict__ seq_tracks, int* __restrict__ next_id_out) {
+  const int s = blockIdx.x, lane = threadIdx.x;
+  if (s > 0 && linked[s]) return;  // wave-uniform: only the wave of a sequence's first frame walks it
+  int c = s, next, prev;
+  if (linked[s]) {  // frame 0 continues the carried frame
+    prev = lane < k ? carry.ids[lane] : -1;
+    next = carry.next_id[0];
+  } else {
+    const int rows = link_rows(counts + 3 * s, k);
+    prev = lane < rows ? lane : -1;
+    next = rows;
+    if (lane < k) ids[(size_t)s * k + lane] = prev;
+    if (lane == 0) seq_tracks[s] = 0;
+    ++c;
+  }
+  for (; c < n && linked[c]; ++c) {  // wave-uniform
+    const int rows = link_rows(counts + 3 * c, k);
+    int m = lane < k ? match[(size_t)c * k + lane] : -1;
+    if (m < 0 || m >= k) m = -1;
+    const int inherited = __shfl(prev, m < 0 ? 0 : m);
+    const bool fresh = lane < rows && m < 0;
+    const unsigned long long mask = __ballot(fresh);
+    int id = -1;
+    if (lane < rows) id = m >= 0 ? inherited : next + __popcll(mask & ((1ull << lane) - 1ull));
+    next += __popcll(mask);
+    if (lane < k) ids[(size_t)c * k + lane] = id;
+    if (lane == 0) seq_tracks[c] = 0;
+    prev = id;
+  }
+  if (lane == 0) {  // c - 1 >= s: the sequence's last frame within the call (the same lane wrote its 0 above)
+    seq_tracks[c - 1] = next;
+    if (c == n) next_id_out[0] = next;
+  }
+}
+
+size_t link_detections_workspace_bytes(size_t total_pixels, int carry_h, int carry_w) {
+  return (total_pixels + (size_t)carry_h * carry_w) * sizeof(int);
+}
+
+int launch_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                  size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                  const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                  const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
+                                  hipStream_t s) {
+  const long nb = ((long)max_h * max_w + 256 * LINK_PPT - 1) / (256 * LINK_PPT);
+  if (nb > 0x7fffffffL) { set_error("link_detections_ragged: frame too large"); return UDET_ERR_SHAPE; }
+  const LinkCarry carry = {carry_labels, carry_dets, carry_counts, carry_ids, carry_next_id, carry_h, carry_w};
+  int* lookup = (int*)workspace;
+  const size_t nz = ((size_t)n * k * k + 255) / 256;
+  const size_t lds_overlap = ((size_t)k * k + 2 * k) * sizeof(int), lds_match = (2 * (size_t)k * k + 3 * k) * sizeof(int);
+  hipLaunchKernelGGL(link_init_kernel, dim3((unsigned)(nz > 65536 ? 65536 : nz)), dim3(256), 0, s, n, offsets, hw, total_pixels, dets,
+                     counts, k, link, carry, (unsigned long long*)inter, linked, lookup);
+  hipLaunchKernelGGL(link_overlap_kernel, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts,
+                     k, carry, linked, lookup, (unsigned long long*)inter);
+  hipLaunchKernelGGL(link_match_kernel, dim3(n), dim3(256), lds_match, s, dets, counts, k, carry, linked, inter, min_iou_permille, match);
+  hipLaunchKernelGGL(link_ids_kernel, dim3(n), dim3(64), 0, s, n, counts, k, carry, linked, match, ids, seq_tracks, next_id);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+// ---- udet_draw_track_boxes_ragged ---------------------------------------------------------------------------------------------------
+// One workgroup per (row of dets, sample), as det_draw_kernel: the four strips of the box's frame in the colour of the row's track.  A
+// pixel that lies on the line of a painted lower-ranked box is skipped, so every pixel is written by the smallest rank that covers it,
+// whatever order the workgroups run in.  Boxes are clipped to their sample's frame and the row count to k.
+struct TrackBox { int y0, x0, y1, x1; };
+
+__device__ __forceinline__ bool track_clip(const long long* __restrict__ d, int H, int W, TrackBox* b) {
+  if (d[0] < 0) return false;
+  const long long ly0 = d[2], lx0 = d[3], ly1 = d[4], lx1 = d[5];
+  b->y0 = (int)(ly0 < 0 ? 0 : ly0 > H ? H : ly0); b->y1 = (int)(ly1 < 0 ? 0 : ly1 > H ? H : ly1);
+  b->x0 = (int)(lx0 < 0 ? 0 : lx0 > W ? W : lx0); b->x1 = (int)(lx1 < 0 ? 0 : lx1 > W ? W : lx1);
+  return b->y1 > b->y0 && b->x1 > b->x0;
+}
+
+__device__ __forceinline__ void track_paint(unsigned char* __restrict__ img, int W, int ya, int yb, int xa, int xb, unsigned rgb, int t,
+                                            const int* __restrict__ lower, int n_lower, int th) {
+  const int w = xb - xa;
+  if (w <= 0 || yb <= ya) return;
+  const long long cells = (long long)(yb - ya) * w;
+  for (long long c = t; c < cells; c += 256) {
+    const int y = ya + (int)(c / w), x = xa + (int)(c % w);
+    bool hidden = false;
+    for (int q = 0; q < n_lower && !hidden; ++q) {
+      const int y0 = lower[4 * q], x0 = lower[4 * q + 1], y1 = lower[4 * q + 2], x1 = lower[4 * q + 3];  // an unpainted row: empty
+      hidden = y >= y0 && y < y1 && x >= x0 && x < x1 && (y < y0 + th || y >= y1 - th || x < x0 + th || x >= x1 - th);
+    }
+    if (hidden) continue;
+    unsigned char* __restrict__ q = img + 3 * ((size_t)y * W + x);
+    q[0] = (unsigned char)(rgb >> 16); q[1] = (unsigned char)(rgb >> 8); q[2] = (unsigned char)rgb;
+  }
+}
+
+__global__ __launch_bounds__(256) void track_draw_kernel(unsigned char* __restrict__ rgb, const long long* __restrict__ offsets,
+                                                         const int* __restrict__ hw, const long long* __restrict__ dets,
+                                                         const long long* __restrict__ counts, int k, const int* __restrict__ ids, int th,
+                                                         const unsigned* __restrict__ palette, int palette_size) {
+  __shared__ int lower[LINK_K * 4];
+  const int i = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
+  if (b >= link_rows(counts + 3 * i, k)) return;  // block-uniform; b < k by the grid
+  const int id = ids[(size_t)i * k + b];
+  if (id < 0) return;
+  const int H = hw[2 * i], W = hw[2 * i + 1];
+  TrackBox own;
+  if (!track_clip(dets + ((size_t)i * k + b) * UDET_DET_FIELDS, H, W, &own)) return;
+  for (int q = t; q < b; q += 256) {
+    TrackBox lo;
+    const bool painted = ids[(size_t)i * k + q] >= 0 && track_clip(dets + ((size_t)i * k + q) * UDET_DET_FIELDS, H, W, &lo);
+    lower[4 * q] = painted ? lo.y0 : 0; lower[4 * q + 1] = painted ? lo.x0 : 0;
+    lower[4 * q + 2] = painted ? lo.y1 : 0; lower[4 * q + 3] = painted ? lo.x1 : 0;
+  }
+  __syncthreads();
+  const unsigned colour = palette[id % palette_size] & 0xffffffu;
+  unsigned char* __restrict__ img = rgb + 3 * (size_t)offsets[i];
+  const int ta = min(own.y0 + th, own.y1), bb = max(own.y1 - th, ta);  // rows [y0, ta) and [bb, y1) are full lines; between them the side strips
+  track_paint(img, W, own.y0, ta, own.x0, own.x1, colour, t, lower, b, th);
+  track_paint(img, W, bb, own.y1, own.x0, own.x1, colour, t, lower, b, th);
+  track_paint(img, W, ta, bb, own.x0, min(own.x0 + th, own.x1), colour, t, lower, b, th);
+  track_paint(img, W, ta, bb, max(own.x1 - th, own.x0), own.x1, colour, t, lower, b, th);
+}
+
+int launch_draw_track_boxes_ragged(unsigned char* rgb, int n, const long long* offsets, const int* hw, const long long* dets,
+                                   const long long* counts, int k, const int* ids, int thickness, const unsigned* palette,
+                                   int palette_size, hipStream_t s) {
+  hipLaunchKernelGGL(track_draw_kernel, dim3(k, n), dim3(256), 0, s, rgb, offsets, hw, dets, counts, k, ids, thickness, palette,
+                     palette_size);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+}  // namespace udet

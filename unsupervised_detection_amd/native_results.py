@@ -15,13 +15,18 @@ post_processing/post_processing.py:32-46:
   component_boxes(selection_or_labels, score, min_area, max_detections)   every component of the labelled masks as a scored box, the
                                                 largest first (csrc/detections.hip, udet_component_boxes_ragged) -> Detections;
                                                 detection_records: the same as plain records (box, area, centroid, score, root)
+  link_detections(selection_or_labels, detections, link, carry, min_iou)   the detections of consecutive frames linked into tracks by
+                                                mask overlap (csrc/tracks.hip, udet_link_detections_ragged) -> Tracks; tail() carries
+                                                the last frame into the next call; track_records / summarise_tracks: the records with
+                                                their tracks, and every track of a sequence
   RestoredMasks / GtBatch / ComponentSelection  buffers of one batch in one ragged.PackedLayout (the packed layout): the
                                                 annotations' layout is built once per batch and handed from call to call
   check_crf_tables / load_images_device / crf_refine_restored   the full-resolution dense CRF of run_crf_original_resolution on the
                                                 restored batch: unary from the restored bytes, the frames read at their own size,
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
-  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections] + J / F +
-                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json [, detections/<sequence>.json]
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections [+ tracks]] + J / F +
+                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json [, detections/<sequence>.json
+                                                [, tracks/<sequence>.json]]
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order; (image, None) for
                                                 a folder of frames without annotations (--dataset FRAMES), which restore_results_dir
                                                 takes in its annotation-free mode; overlay=... draws the final masks on the frames
@@ -30,7 +35,8 @@ post_processing/post_processing.py:32-46:
 scipy.misc.imresize is restated as bytescale + Pillow's 8-bit bilinear resampler.  The "best detection candidate from
 the set of predicted connected masks" the reference only mentions in a comment (post_processing.py:32-35) is select_components
 (DESIGN.md 7.3).  The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...}).  Every component as a box with
-its area, centroid and score -- the detections -- is restore_results_dir(detections={...})."""
+its area, centroid and score -- the detections -- is restore_results_dir(detections={...}); linking them across the
+frames of a sequence is restore_results_dir(tracks={...})."""
 from __future__ import annotations
 
 import ctypes
@@ -445,6 +451,210 @@ def detection_records(detections, amax):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# Detections linked into tracks across consecutive frames (csrc/tracks.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+TRACK_DEFAULTS = {"min_iou": 0.1}
+
+
+def min_iou_permille(min_iou):
+    """round(1000 min_iou) as the kernels take the threshold: an integer in 1..1000 (ValueError otherwise)."""
+    try:
+        p = int(round(1000.0 * float(min_iou)))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("tracks: min_iou must be a number")
+    if isinstance(min_iou, bool) or not 1 <= p <= 1000:
+        raise ValueError("tracks: min_iou must round to a permille in 1..1000: round(1000 min_iou)")
+    return p
+
+
+def track_params(tracks=None):
+    """The `tracks` dict of restore_results_dir ({} or None: the defaults) with the defaults filled in and checked (ValueError)."""
+    p = dict(TRACK_DEFAULTS)
+    if tracks is not None:
+        if not isinstance(tracks, dict) or not set(tracks) <= set(TRACK_DEFAULTS):
+            raise ValueError("tracks must be a dict with keys among {}".format(sorted(TRACK_DEFAULTS)))
+        p.update({k: v for k, v in tracks.items() if v is not None})
+    min_iou_permille(p["min_iou"])
+    p["min_iou"] = float(p["min_iou"])
+    return p
+
+
+def _clone(x):
+    return x.clone() if isinstance(x, torch.Tensor) else np.array(x, copy=True)
+
+
+class TrackTail(object):
+    """The last frame of a link_detections call, as the next call's `carry`: labels (int32 [h * w]), hw = (h, w), dets (int64 [k, 9]),
+    counts (int64 [3]), ids (int32 [k]) and next_id (int32 [1]: the next free id of the frame's sequence) -- copies, on the device."""
+
+    def __init__(self, labels, hw, dets, counts, ids, next_id):
+        self.labels, self.hw, self.dets, self.counts, self.ids, self.next_id = labels, (int(hw[0]), int(hw[1])), dets, counts, ids, next_id
+        self.k = int(dets.shape[0])
+
+
+class Tracks(object):
+    """Result of link_detections for the n frames of `detections`: inter (int64 [n, k, k]), match (int32 [n, k]), ids (int32 [n, k]),
+    linked (int32 [n]), seq_tracks (int32 [n]) and next_id (int32 [1]) as include/udet.h defines them, on the device; labels: the packed
+    labels they were computed from; carry: the TrackTail frame 0 was linked against, or None."""
+
+    def __init__(self, inter, match, ids, linked, seq_tracks, next_id, labels, detections, carry=None):
+        self.inter, self.match, self.ids, self.linked, self.seq_tracks, self.next_id = inter, match, ids, linked, seq_tracks, next_id
+        self.labels, self.detections, self.carry, self.k = labels, detections, carry, int(ids.shape[1])
+        self.layout = getattr(detections, "layout", None)  # (a numpy stand-in of the detections has none: it brings its own tail())
+        self._host = None
+
+    def __len__(self):
+        return int(self.ids.shape[0])
+
+    def host(self):
+        """(inter, match, ids, linked, seq_tracks) as numpy arrays: one copy of each per Tracks, made on first use."""
+        if self._host is None:
+            self._host = tuple(_host(t) for t in (self.inter, self.match, self.ids, self.linked, self.seq_tracks))
+        return self._host
+
+    def rows(self, i):
+        """Host views (ids, match) of the rows written for frame i, in rank order."""
+        _, match, ids, _, _ = self.host()
+        r = len(self.detections.rows(i))
+        return ids[i, :r], match[i, :r]
+
+    def tail(self) -> TrackTail:
+        """The last frame -- its labels, det rows, counts, ids -- and its sequence's next free id, cloned: the next call's `carry`."""
+        i = len(self) - 1
+        o, (h, w) = int(self.layout.offsets[i]), (int(v) for v in self.layout.hw[i])
+        return TrackTail(_clone(self.labels[o:o + h * w]), (h, w), _clone(self.detections.dets[i]), _clone(self.detections.counts[i]),
+                         _clone(self.ids[i]), _clone(self.next_id))
+
+
+def check_link_arguments(layout, detections, link, carry, min_iou):
+    """The host validation of link_detections (ValueError): `layout` (the labels') equals the detections', dets / counts have their shapes, link is None or n values 0 / 1, carry is None or a TrackTail of the same k, min_iou
+    rounds to a permille in 1..1000.  Returns (link as int32 [n] or None when it is a device tensor, permille)."""
+    n, k = detections.layout.n, int(detections.k)
+    if not layout.same_as(detections.layout):
+        raise ValueError("the labels must be packed like the detections' frames (same offsets and sizes)")
+    if tuple(detections.dets.shape) != (n, k, DET_FIELDS) or tuple(detections.counts.shape) != (n, 3) or not 1 <= k <= DET_MAX_K:
+        raise ValueError("detections: dets must be [{}, k, {}] and counts [{}, 3] with k in 1..{}".format(n, DET_FIELDS, n, DET_MAX_K))
+    permille = min_iou_permille(min_iou)
+    if carry is not None:
+        if not isinstance(carry, TrackTail):
+            raise ValueError("carry must be the tail() of the previous call's Tracks")
+        if carry.k != k or tuple(carry.dets.shape) != (k, DET_FIELDS) or int(np.prod(carry.ids.shape)) != k:
+            raise ValueError("carry: the carried frame was linked with k = {}, this call has k = {}".format(carry.k, k))
+        if int(np.prod(carry.labels.shape)) != carry.hw[0] * carry.hw[1] or min(carry.hw) < 1:
+            raise ValueError("carry: labels must hold h * w elements")
+    if link is None:
+        return np.ones(n, np.int32), permille
+    if isinstance(link, torch.Tensor) and link.is_cuda:
+        require_tensor(link, "link (one int32 per frame)", torch.int32, 1, n)
+        return None, permille
+    host = np.asarray(_host(link)).reshape(-1)
+    if len(host) != n or not np.isin(host, (0, 1)).all():
+        raise ValueError("link must hold one 0 / 1 per frame ({} frames)".format(n))
+    return np.ascontiguousarray(host.astype(np.int32)), permille
+
+
+def link_detections(selection_or_labels, detections, link=None, carry=None, min_iou=0.1) -> Tracks:
+    """The detections of n consecutive frames linked into tracks by mask overlap, in one call of udet_link_detections_ragged (four
+    launches whatever n and the number of sequences and components; nothing comes back to the host).  selection_or_labels: the
+    ComponentSelection (with labels) or the 1-D int32 device tensor of labels `detections` (a Detections) was computed from.  link: one
+    0 / 1 per frame, 1: the frame continues the one before it (frame 0: `carry`), 0: it starts a sequence; None: every frame continues.
+    carry: the tail() of the previous call's Tracks, or None (frame 0 then starts a sequence).  A frame whose predecessor has another
+    size starts a sequence too.  Rows a of the predecessor and b of the frame share inter pixels; pairs with IoU = inter / (area_a +
+    area_b - inter) >= min_iou (as the permille round(1000 min_iou), 1..1000) are matched greedily, the largest IoU first (ties to
+    the smaller a, then the smaller b); a matched row inherits its predecessor's track id, the others take the sequence's next free
+    ids in rank order -- exact integers (include/udet.h).  Validated on the host before the device is touched (ValueError)."""
+    if isinstance(selection_or_labels, ComponentSelection):
+        if selection_or_labels.labels is None:
+            raise ValueError("selected without want_labels: no labels")
+        labels, layout = selection_or_labels.labels, selection_or_labels.layout
+    else:
+        labels, layout = selection_or_labels, detections.layout
+    total = int(require_tensor(labels, "labels (packed samples)", torch.int32, 1, cuda=False).numel())
+    as_layout(layout, None, total, max_samples=65535)
+    for t, name, nd in ((detections.dets, "dets", 3), (detections.counts, "counts", 2)):
+        require_tensor(t, "detections." + name, torch.int64, nd, cuda=False)
+    host_link, permille = check_link_arguments(layout, detections, link, carry, min_iou)
+    require_tensor(labels, "labels (packed samples)", torch.int32, 1)
+    dev, n, k = labels.device, layout.n, detections.k
+    require_tensor(detections.dets, "detections.dets", torch.int64, 3, device=dev)
+    require_tensor(detections.counts, "detections.counts", torch.int64, 2, device=dev)
+    if carry is not None:
+        for t, name, dt in ((carry.labels, "labels", torch.int32), (carry.dets, "dets", torch.int64), (carry.counts, "counts", torch.int64),
+                            (carry.ids, "ids", torch.int32), (carry.next_id, "next_id", torch.int32)):
+            require_tensor(t, "carry." + name, dt, device=dev)
+    d_link = link if host_link is None else torch.from_numpy(host_link).to(dev)
+    d_off, d_hw = layout.device_tables(dev)
+    inter = torch.empty((n, k, k), dtype=torch.int64, device=dev)
+    match, ids = (torch.empty((n, k), dtype=torch.int32, device=dev) for _ in range(2))
+    linked, seq_tracks = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(2))
+    next_id = torch.empty(1, dtype=torch.int32, device=dev)
+    ch, cw = carry.hw if carry is not None else (0, 0)
+    ws = workspace(lib.udet_link_detections_workspace_bytes(total, n, k, ch, cw), 4, dev)
+    c_lab, c_det, c_cnt, c_ids, c_next = ([None] * 5 if carry is None else
+                                          [t.data_ptr() for t in (carry.labels, carry.dets, carry.counts, carry.ids, carry.next_id)])
+    check(lib.udet_link_detections_ragged(labels.data_ptr(), n, d_off.data_ptr(), d_hw.data_ptr(), layout.max_h, layout.max_w, total,
+                                          detections.dets.data_ptr(), detections.counts.data_ptr(), k, d_link.data_ptr(), c_lab, ch, cw,
+                                          c_det, c_cnt, c_ids, c_next, permille, inter.data_ptr(), match.data_ptr(), ids.data_ptr(),
+                                          linked.data_ptr(), seq_tracks.data_ptr(), next_id.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          torch.cuda.current_stream(dev).cuda_stream))
+    return Tracks(inter, match, ids, linked, seq_tracks, next_id, labels, detections, carry)
+
+
+def track_records(records, tracks):
+    """The per-frame detection records (detection_records' lists, in the frames' order) with their tracks: every record gains "track"
+    (its id within its sequence), "prev" (the rank of the row it continues in the frame before, or None) and "iou" (inter / (area_a +
+    area_b - inter) of that pair in float64, or None).  tracks: a Tracks (or anything with its host(), detections.dets and carry.dets).  Returns
+    new lists; the records given stay as they are."""
+    inter, match, ids, _, _ = tracks.host()
+    if len(records) != len(ids):
+        raise ValueError("one list of records per frame")
+    dets = _host(tracks.detections.dets)
+    out = []
+    for i, recs in enumerate(records):
+        if len(recs) > ids.shape[1]:
+            raise ValueError("frame {}: more records than rows".format(i))
+        prev = dets[i - 1] if i else (None if tracks.carry is None else _host(tracks.carry.dets))
+        new = []
+        for b, rec in enumerate(recs):
+            a = int(match[i, b])
+            iou = None
+            if a >= 0:
+                it = int(inter[i, a, b])
+                iou = float(np.float64(it) / np.float64(int(prev[a, 1]) + int(dets[i, b, 1]) - it))
+            new.append(dict(rec, track=int(ids[i, b]), prev=a if a >= 0 else None, iou=iou))
+        out.append(new)
+    return out
+
+
+def summarise_tracks(stems, records, starts):
+    """The tracks of a category's frames, per sequence: stems (the frames' names), records (track_records' lists) and starts (per frame,
+    true where a sequence starts: the category's first frame, and every frame that was not linked) -> a list of sequences in the frames'
+    order, each {"first": stem, "frames": count, "tracks": [...]} with one entry per track id, ascending: {"id", "first" / "last" (the
+    stems of the first and last frame it appears in), "frames" (in how many), "area_mean", "score_mean" (over those frames, float64)
+    and "boxes": {stem: [x0, y0, x1, y1]}}."""
+    if not (len(stems) == len(records) == len(starts)):
+        raise ValueError("one stem, one list of records and one start flag per frame")
+    out = []
+    for i, (stem, recs) in enumerate(zip(stems, records)):
+        if i == 0 or starts[i]:
+            out.append({"first": stem, "frames": 0, "tracks": {}})
+        seq = out[-1]
+        seq["frames"] += 1
+        for rec in recs:
+            t = seq["tracks"].setdefault(int(rec["track"]), {"id": int(rec["track"]), "first": stem, "area": [], "score": [], "boxes": {}})
+            t["last"] = stem
+            t["area"].append(rec["area"])
+            t["score"].append(rec["score"])
+            t["boxes"][stem] = list(rec["box"])
+    for seq in out:
+        seq["tracks"] = [{"id": t["id"], "first": t["first"], "last": t["last"], "frames": len(t["area"]),
+                          "area_mean": float(np.mean(np.asarray(t["area"], np.float64))),
+                          "score_mean": float(np.mean(np.asarray(t["score"], np.float64))), "boxes": t["boxes"]}
+                         for _, t in sorted(seq["tracks"].items())]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # The dense CRF at native resolution (csrc/crf.hip, DESIGN.md 7.4)
 # ---------------------------------------------------------------------------------------------------------------------------
 CRF_KEYS = ("sxy", "srgb", "compat", "gauss_k", "iters", "radius")
@@ -515,11 +725,19 @@ def draw_detection_boxes(overlays, detections, boxes):
     return draw_boxes(overlays, detections, **boxes)
 
 
+def draw_track_detection_boxes(overlays, detections, tracks, boxes):
+    """visualize.draw_track_boxes(overlays, detections, tracks, thickness=boxes["thickness"]): the boxes of a batch on its overlays, each in
+    the colour of its track (visualize.TRACK_PALETTE), in place, one launch."""
+    from .visualize import draw_track_boxes
+    return draw_track_boxes(overlays, detections, tracks, thickness=boxes["thickness"])
+
+
 def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop=0.9, threshold=0.5, batch=16, restore=restore_masks,
                         gt_rule="DAVIS2016", load_gt=load_gt_device, score=score_device, bound_th=None, skip_ends=True, verbose=True,
                         component=None, connectivity=8, select=select_components, crf=None, load_images=load_images_device,
                         refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays, detections=None,
-                        detect=component_boxes, draw_boxes=draw_detection_boxes):
+                        detect=component_boxes, draw_boxes=draw_detection_boxes, tracks=None, link=link_detections,
+                        draw_track_boxes=draw_track_detection_boxes):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -558,8 +776,15 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     "detections_mean" (the mean number of records per frame).  With and without annotations.  overlay["boxes"] (needs detections; a dict
     with thickness (2; 1..8) and colour ((255, 255, 0)), {} for the defaults): draw_boxes(overlays, detections, boxes) paints the boxes on
     the batch's overlays after the mask (visualize.draw_boxes, one launch), and the json's "overlay" carries "boxes".
-    restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes are injectable: the host logic
-    runs without a GPU on numpy stand-ins."""
+    tracks (None: off; needs detections): a dict with min_iou (0.1), {} for the default.  A category's batches are consecutive frames, so
+    every batch goes through link(labelled, det, link=[1, ...] with 0 at the category's first frame, carry=the previous batch's
+    tail(), min_iou=...) (link_detections: four launches per batch); a frame of another size than the one before it starts a new
+    sequence inside its category.  The records of detections/<category>.json gain "track", "prev" and "iou" (track_records),
+    <out_dir>/tracks/<category>.json holds summarise_tracks' list, and the json gains "tracks": {min_iou} and per sequence "tracks" (the
+    ids handed out) and "track_len_mean" (the mean number of frames of a track).  With overlay["boxes"] the boxes are painted by
+    draw_track_boxes(overlays, detections, tracks, boxes) in the colour of their track, in the place of the single-colour call.
+    restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes are
+    injectable: the host logic runs without a GPU on numpy stand-ins."""
     import json
     import re
     import scipy.io as sio
@@ -573,6 +798,10 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         raise ValueError("connectivity must be 4 or 8")
     crf = None if crf is None else crf_params(crf)
     detections = None if detections is None else detection_params(detections)
+    if tracks is not None:
+        if detections is None:
+            raise ValueError("tracks links the detections: it needs detections")
+        tracks = track_params(tracks)
     boxes = None
     if overlay is not None:
         from .visualize import box_params, overlay_params
@@ -589,7 +818,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         raise ValueError('component "best_gt" needs annotations: use "largest" or None')
     if not free:
         rule = GT_RULES[gt_rule] if isinstance(gt_rule, str) else gt_rule
-    cat_j, cat_f, cat_nc, cat_fg, cat_nd = {}, {}, {}, {}, {}
+    cat_j, cat_f, cat_nc, cat_fg, cat_nd, cat_nt, cat_tl = {}, {}, {}, {}, {}, {}, {}
     for cat, entries in frame_lists.items():
         d = os.path.join(results_dir, cat)
         ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
@@ -601,6 +830,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             os.makedirs(os.path.join(out_dir, "overlay", cat), exist_ok=True)
         j, f, nc, fg = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries)), np.zeros(len(entries))
         records = {}  # frame stem -> its detections, in the list's order
+        tail, starts = None, []  # tracks: the previous batch's last frame; per frame, whether it starts a sequence
         for s in range(0, len(entries), batch):
             rows = entries[s:s + batch]
             masks = []
@@ -635,8 +865,14 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             det = None
             if detections is not None:
                 det = detect(labelled, score=res, min_area=detections["min_area"], max_detections=detections["max_detections"])
-                for (img, _), recs in zip(rows, detection_records(det, res.amax)):
-                    records[os.path.splitext(os.path.basename(img))[0]] = recs
+                recs = detection_records(det, res.amax)
+                if tracks is not None:
+                    trk = link(labelled, det, link=[0 if s + i == 0 else 1 for i in range(len(rows))], carry=tail, min_iou=tracks["min_iou"])
+                    tail = trk.tail()
+                    recs = track_records(recs, trk)
+                    starts += [not v for v in trk.host()[3]]
+                for (img, _), r in zip(rows, recs):
+                    records[os.path.splitext(os.path.basename(img))[0]] = r
             if not free:
                 shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
                 for shape in sorted(set(shapes)):
@@ -645,7 +881,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                     j[[s + i for i in idx]], f[[s + i for i in idx]] = jj, ff
             drawn = draw(frames, pred, overlay) if overlay is not None else None
             if boxes is not None:
-                drawn = draw_boxes(drawn, det, boxes)
+                drawn = draw_boxes(drawn, det, boxes) if tracks is None else draw_track_boxes(drawn, det, trk, boxes)
             for i, (img, _) in enumerate(rows):
                 stem = os.path.splitext(os.path.basename(img))[0]
                 binm = _host(pred.binary_sample(i)).astype(np.uint8)
@@ -666,6 +902,13 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             with open(os.path.join(out_dir, "detections", cat + ".json"), "w") as fh:
                 json.dump(records, fh, indent=1)
             cat_nd[cat] = float(np.mean([len(r) for r in records.values()])) if records else 0.0
+        if tracks is not None:
+            summary = summarise_tracks(list(records), list(records.values()), starts)
+            os.makedirs(os.path.join(out_dir, "tracks"), exist_ok=True)
+            with open(os.path.join(out_dir, "tracks", cat + ".json"), "w") as fh:
+                json.dump(summary, fh, indent=1)
+            lengths = [t["frames"] for seq in summary for t in seq["tracks"]]
+            cat_nt[cat], cat_tl[cat] = len(lengths), float(np.mean(lengths)) if lengths else 0.0
     if not cat_j:
         raise IOError("no category to restore")
     if free:
@@ -683,6 +926,10 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
             out["detections"] = dict(detections, connectivity=int(connectivity))
             for c in out["sequences"]:
                 out["sequences"][c]["detections_mean"] = cat_nd[c]
+        if tracks is not None:
+            out["tracks"] = tracks
+            for c in out["sequences"]:
+                out["sequences"][c]["tracks"], out["sequences"][c]["track_len_mean"] = cat_nt[c], cat_tl[c]
         if verbose:
             print("Native resolution ({} frames, crop {}, no annotations):".format(sum(len(v) for v in cat_j.values()), crop))
             for c, v in out["sequences"].items():
@@ -707,6 +954,10 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
         out["detections"] = dict(detections, connectivity=int(connectivity))
         for c in out["sequences"]:
             out["sequences"][c]["detections_mean"] = cat_nd[c]
+    if tracks is not None:
+        out["tracks"] = tracks
+        for c in out["sequences"]:
+            out["sequences"][c]["tracks"], out["sequences"][c]["track_len_mean"] = cat_nt[c], cat_tl[c]
     if verbose:
         print("Native resolution ({} frames, crop {}):".format(sum(len(v) for v in cat_j.values()), crop))
         _print_davis_table(per, tot)

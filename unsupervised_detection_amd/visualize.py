@@ -214,6 +214,55 @@ def draw_boxes(overlays, detections, thickness=2, colour=(255, 255, 0)) -> Nativ
     return overlays
 
 
+TRACK_MAX_PALETTE = 64  # UDET_TRACK_MAX_PALETTE
+# twelve distinct colours (the qualitative "Paired" scheme of ColorBrewer): track id t is drawn in TRACK_PALETTE[t mod 12]
+TRACK_PALETTE = [(166, 206, 227), (31, 120, 180), (178, 223, 138), (51, 160, 44), (251, 154, 153), (227, 26, 28),
+                 (253, 191, 111), (255, 127, 0), (202, 178, 214), (106, 61, 154), (255, 255, 153), (177, 89, 40)]
+
+
+def palette_words(palette):
+    """A palette -- 1..TRACK_MAX_PALETTE colours of three integers in 0..255 -- as a tuple of 0xRRGGBB words (ValueError otherwise)."""
+    try:
+        colours = [tuple(c) for c in palette]
+    except TypeError:
+        raise ValueError("palette must be a list of (r, g, b) colours")
+    if not 1 <= len(colours) <= TRACK_MAX_PALETTE:
+        raise ValueError("palette must hold 1..{} colours".format(TRACK_MAX_PALETTE))
+    return tuple(_rgb24(c, "palette colour") for c in colours)
+
+
+def draw_track_boxes(overlays, detections, tracks, thickness=2, palette=TRACK_PALETTE) -> NativeOverlays:
+    """The boxes of a batch's detections painted on its overlays in the colour of their track, in place, in one call of
+    udet_draw_track_boxes_ragged (one launch; dets, counts and ids are read on the device).  overlays / detections / thickness: as for
+    draw_boxes; tracks: the native_results.Tracks of those detections.  Row r of frame i is painted palette[ids[i][r] mod len(palette)]
+    (palette: 1..64 colours, TRACK_PALETTE's twelve by default); a row without an id (-1) is not painted; where the lines of several
+    boxes cover a pixel, the box of the smallest rank wins.  Returns overlays.  Validated on the host before the device is touched
+    (ValueError)."""
+    p = box_params({"thickness": thickness})
+    words = palette_words(palette)
+    frames, layout = overlays.layout, detections.layout
+    if frames.c != 3 or not frames.same_as(layout, scale=3):
+        raise ValueError("the overlays must be rgb and packed like the detections' frames (their sizes, three times their offsets)")
+    as_layout(layout, None, layout.numel, max_samples=65535)
+    for t, name, dt, shape in ((detections.dets, "detections.dets", torch.int64, (layout.n, detections.k, 9)),
+                               (detections.counts, "detections.counts", torch.int64, (layout.n, 3)),
+                               (tracks.ids, "tracks.ids", torch.int32, (layout.n, detections.k))):
+        require_tensor(t, name, dt, len(shape), cuda=False)
+        if tuple(t.shape) != shape:
+            raise ValueError("{} must be {} for {} frames".format(name, list(shape), layout.n))
+    dev = detections.dets.device
+    require_tensor(detections.dets, "detections.dets", torch.int64, 3)
+    require_tensor(detections.counts, "detections.counts", torch.int64, 2, device=dev)
+    require_tensor(tracks.ids, "tracks.ids", torch.int32, 2, device=dev)
+    require_tensor(overlays.data, "overlays (rgb, packed like the detections' frames)", torch.uint8, 1, 3 * layout.numel, dev)
+    d_pal = torch.tensor(words, dtype=torch.int32, device=dev)
+    d_off, d_hw = layout.device_tables(dev)
+    check(lib.udet_draw_track_boxes_ragged(overlays.data.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.numel,
+                                           detections.dets.data_ptr(), detections.counts.data_ptr(), detections.k, tracks.ids.data_ptr(),
+                                           p["thickness"], d_pal.data_ptr(), len(words), torch.cuda.current_stream(dev).cuda_stream))
+    return overlays
+
+
 # ------------------------------------------------------------------------------------------------------- histograms ----
 def bucket_limits() -> np.ndarray:
     """TensorFlow's default histogram bucket limits, as the library builds them: 1551 ascending float64."""
