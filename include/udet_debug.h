@@ -58,6 +58,41 @@ int udet_debug_last_pair(void);
 int udet_debug_conv2d_pair(const float* xa, const float* xb, const float* wa, const float* wb, const float* ba, const float* bb, float* ya, float* yb,
                            int na, int nb, int h, int w, int cin, int cout, int k, int stride, int dilation, int act, float alpha, void* workspace,
                            size_t workspace_bytes, void* stream);
+/* ---- One level of the recover decoder in its low-resolution ("up-conv algebra") form, exactly as a plan runs it --------------------------
+ * y = act(conv4x4_SAME(legacy_bilinear_x2(x), w) + bias) computed as the plan computes levels 1-4: the ringed source x^ (upb_ring), four merged
+ * 3x3 weight sets (pack modes 9 / 10), one 16-segment launch (forward; `split`: the interior as a four-class launch and the 12 border
+ * segments in a second one, legal for cout <= 16 as in a plan) or one 16-segment backward-data launch followed by the ring's adjoint.  The
+ * entries call the plan's own table builder, pack jobs and launch code (csrc/plan_exec.hip upb_forward / upb_dgrad); they only lay out a
+ * workspace.  They synchronise the stream before they return.
+ *   forward:  x [n,h,w,ldx] channels [0,cin) (the weight rows of channels [cin,ldx) are zero: Kc = ldx as in a plan, those values must be
+ *             finite); w HWIO [4,4,cin,cout]; bias [cout] or NULL; y [n,2h,2w,ldy] channels [y_coff, y_coff+cout) written, nothing else;
+ *             xhat [n,h+2,w+2,ldx] receives the ringed source (all ldx channels).
+ *   backward: dy [n,2h,2w,ldy] channels [y_coff, y_coff+kt), kt = cout rounded up to 8 (4 for cout <= 4), read (rows past cout meet zero
+ *             weights: finite values); dxhat [n,h+2,w+2,ldx] channels [0,cin) receive the ringed gradient BEFORE the fold (other channels
+ *             are read by the fold, not written: initialise them); dx [n,h,w,ldx] = ring adjoint of dxhat (all ldx channels written).
+ *             fp16 mode: the gradient operand is scaled by udet_debug_conv_fp16_grad_scale's value (a plan uses 4096).
+ * Every argument is checked before the first HIP call: ldx, ldy, y_coff not multiples of 4 -> UDET_ERR_ALIGN; a channel window outside its
+ * row (cin > ldx, y_coff + cout > ldy, backward y_coff + kt > ldy) -> UDET_ERR_SHAPE; h < 2 or w < 2 -> UDET_ERR_SHAPE (the forward table
+ * has h - 1 interior rows and one last row, the ring fold needs both edges distinct: a 1-pixel-high source is refused, a plan never
+ * builds one); NULL pointers, n / cin / cout < 1, an unknown act, split with cout > 16, a workspace that is NULL, not 64-byte aligned or
+ * smaller than udet_debug_upconv_lowres_workspace_bytes(ldx, cin, cout) -> UDET_ERR_ARG.
+ * Workspace (floats): [0, UDET_DEBUG_UPCONV_WSETS_OFFSET) zero block, ticket counters, device tables; from that offset the four weight
+ * sets [4][36][K][ld] (forward: K = ldx, ld = cout rounded up to 4; backward: K = kt, ld = cin rounded up to 4), valid after the call
+ * (tests read them back); then the split-K slabs. */
+#define UDET_DEBUG_UPCONV_WSETS_OFFSET 6400
+size_t udet_debug_upconv_lowres_workspace_bytes(int ldx, int cin, int cout);
+int udet_debug_upconv_lowres_fwd(const float* x, int ldx, const float* w, const float* bias, int act, float alpha, float* y, int ldy, int y_coff,
+                                 float* xhat, int n, int h, int wd, int cin, int cout, int split, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+int udet_debug_upconv_lowres_bwd(const float* dy, int ldy, int y_coff, const float* w, float* dx, int ldx, float* dxhat, int n, int h, int wd,
+                                 int cin, int cout, void* workspace, size_t workspace_bytes, void* stream);
+/* Host only (no HIP call, works without a device): the segment and tap tables build_upb_launches makes for an h x w source (h, w >= 2,
+ * else UDET_ERR_SHAPE), forward (backward = 0: taps read the ringed source x^ at segment pixel (qy, qx) + (dy, dx), outputs at
+ * (oy + 2 qy, ox + 2 qx)) or backward-data (taps read dU at (2 qy + dy, 2 qx + dx), outputs on the ringed grid at (oy + qy, ox + qx)).
+ * seg [nseg][4] = oy, ox, h, w; seg_tap [nseg + 1]; taps [ntaps][3] = dy, dx, widx with widx = weight set * 36 + class * 9 + 3 a + b.
+ * taps_cap < ntaps: UDET_ERR_ARG with *ntaps set.  udet_debug_max_segs: UDET_MAX_SEGS of the launcher. */
+int udet_debug_upconv_tables(int h, int w, int backward, int* nseg, int* seg, int* seg_tap, int* taps, int taps_cap, int* ntaps);
+int udet_debug_max_segs(void);
 /* (The experiment knobs of earlier rounds -- lane choices and the work-skipping ablation mask -- are no longer reachable from any library
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */

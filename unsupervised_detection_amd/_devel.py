@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from ._ffi import lib as _lib  # libudet.so first: the debug library resolves its internal symbols against it  # noqa: F401
+from ._ffi import check as _check, lib as _lib  # libudet.so first: the debug library resolves its internal symbols against it  # noqa: F401
 
 _PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libudet_debug.so")
 if not os.path.exists(_PATH):
@@ -40,3 +40,29 @@ _p, _i, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 dbg.udet_debug_conv2d_backward_filter_ex.restype = ctypes.c_int
 dbg.udet_debug_conv2d_backward_filter_ex.argtypes = ([_p, _i, _i, _p, _i, _i, _p, _i, _f, _p, _p, _p, _f, _p, _p, _p, _p] + [_i] * 9
                                                      + [_p, ctypes.c_size_t, _p])
+# one level of the recover decoder's low-resolution form as a plan runs it (include/udet_debug.h)
+UPCONV_WSETS_OFFSET = 6400  # UDET_DEBUG_UPCONV_WSETS_OFFSET: floats in front of the packed weight sets in the entries' workspace
+dbg.udet_debug_upconv_lowres_workspace_bytes.restype = ctypes.c_size_t
+dbg.udet_debug_upconv_lowres_workspace_bytes.argtypes = [_i, _i, _i]
+dbg.udet_debug_upconv_lowres_fwd.restype = ctypes.c_int
+dbg.udet_debug_upconv_lowres_fwd.argtypes = [_p, _i, _p, _p, _i, _f, _p, _i, _i, _p] + [_i] * 6 + [_p, ctypes.c_size_t, _p]
+dbg.udet_debug_upconv_lowres_bwd.restype = ctypes.c_int
+dbg.udet_debug_upconv_lowres_bwd.argtypes = [_p, _i, _i, _p, _p, _i, _p] + [_i] * 5 + [_p, ctypes.c_size_t, _p]
+dbg.udet_debug_upconv_tables.restype = ctypes.c_int
+dbg.udet_debug_upconv_tables.argtypes = [_i, _i, _i] + [_p] * 4 + [_i, _p]
+dbg.udet_debug_max_segs.restype = ctypes.c_int
+dbg.udet_debug_max_segs.argtypes = []
+
+
+def upconv_tables(h: int, w: int, backward: bool):
+    """The segment and tap tables of the recover decoder's low-resolution form for an h x w source (host only, no device needed):
+    dict(nseg, seg [nseg][oy, ox, h, w], seg_tap [nseg + 1], taps [ntaps][dy, dx, widx]); a refusal raises ValueError (_ffi.check)."""
+    cap = 1024
+    nseg, ntaps = ctypes.c_int(0), ctypes.c_int(0)
+    seg, seg_tap, taps = (ctypes.c_int * 64)(), (ctypes.c_int * 17)(), (ctypes.c_int * (3 * cap))()
+    st = dbg.udet_debug_upconv_tables(h, w, 1 if backward else 0, ctypes.addressof(nseg), ctypes.addressof(seg), ctypes.addressof(seg_tap),
+                                      ctypes.addressof(taps), cap, ctypes.addressof(ntaps))
+    _check(st)
+    ns, nt = nseg.value, ntaps.value
+    return dict(nseg=ns, seg=[tuple(seg[4 * s:4 * s + 4]) for s in range(ns)], seg_tap=list(seg_tap[:ns + 1]),
+                taps=[tuple(taps[3 * t:3 * t + 3]) for t in range(nt)])

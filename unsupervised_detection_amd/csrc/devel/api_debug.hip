@@ -3,9 +3,11 @@
 // interface (conv_host.h).  Only tests/ and tools/ load it; the product path never does.
 #include <string.h>
 
+#include <vector>
+
 #include "../../../include/udet_debug.h"
 #include "../conv_host.h"
-#include "../plan.h"
+#include "../plan_run.h"
 
 using namespace udet;
 
@@ -103,6 +105,160 @@ int udet_debug_conv2d_pair(const float* xa, const float* xb, const float* wa, co
   }
   return launch_conv_pair(p[0], p[1], stream);
 }
+// ---- one level of the recover decoder's up-conv algebra, exactly as the plan runs it (tests/test_upconv_lowres_gpu.py) -------------------
+// Everything the level does goes through the plan's own functions: build_upb_launches (segments, tap tables), upb_pack_jobs +
+// launch_pack_jobs (weight sets, modes 9 / 10), upb_forward / upb_dgrad (ring, parameter blocks, launches, ring fold).  This file only
+// lays a workspace out and checks arguments.
+}  // extern "C"
+namespace {
+enum { UPC_TICKETS = 64, UPC_JOBS = UPC_TICKETS + UDET_MAX_TICKETS, UPC_JOBS_CAP = 192, UPC_TAB = UPC_JOBS + UPC_JOBS_CAP, UPC_TAB_CAP = 2048,
+       UPC_WSETS = UPC_TAB + UPC_TAB_CAP, UPC_MIN_SLAB = 1 << 20 };
+static_assert(UPC_WSETS == UDET_DEBUG_UPCONV_WSETS_OFFSET && UPC_WSETS % 64 == 0 && 8 * sizeof(PackJob) <= UPC_JOBS_CAP * sizeof(float), "workspace layout");
+size_t upc_align64(size_t v) { return (v + 63) & ~(size_t)63; }
+int upc_kct(int cout) { return round_up(cout, cout <= 4 ? 4 : 8); }
+size_t upc_floats(int kc, int ldw) { return UPC_WSETS + upc_align64((size_t)4 * 36 * kc * ldw) + UPC_MIN_SLAB; }
+// checks shared by the two directions; 0 or the error code (message set)
+int upc_check(const char* who, const void* a, const void* b, const void* c, const void* d, int n, int h, int wd, int cin, int cout, void* workspace,
+              size_t workspace_bytes, size_t need_floats) {
+  if (!a || !b || !c || !d || n < 1 || cin < 1 || cout < 1) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  if (h < 2 || wd < 2) { set_error("%s: the source grid %d x %d must be at least 2 x 2 (one interior row / column and the last one)", who, h, wd); return UDET_ERR_SHAPE; }
+  if ((long)n * (2 * h) * (2 * wd) >= (1L << 28)) { set_error("%s: grid too large", who); return UDET_ERR_SHAPE; }
+  if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 63) || workspace_bytes < need_floats * sizeof(float)) {
+    set_error("%s: workspace must be 64-byte aligned and hold %zu bytes", who, need_floats * sizeof(float));
+    return UDET_ERR_ARG;
+  }
+  return UDET_OK;
+}
+// device copies of the pack jobs and of one tap table, the weight sets packed; the host vectors must outlive the stream's copies
+int upc_stage(const Layer::SegLaunch& tab, const std::vector<PackJob>& jobs, const float* w, float* ws, hipStream_t stream) {
+  if (tab.taps.size() * sizeof(ConvTap) > UPC_TAB_CAP * sizeof(float) || jobs.size() * sizeof(PackJob) > UPC_JOBS_CAP * sizeof(float)) {
+    set_error("debug_upconv_lowres: table larger than its workspace slot");
+    return UDET_ERR_ARG;
+  }
+  UDET_HIP(hipMemsetAsync(ws, 0, UPC_JOBS * sizeof(float), stream));  // zero block + ticket counters
+  UDET_HIP(hipMemcpyAsync(ws + UPC_JOBS, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice, stream));
+  UDET_HIP(hipMemcpyAsync(ws + UPC_TAB, tab.taps.data(), tab.taps.size() * sizeof(ConvTap), hipMemcpyHostToDevice, stream));
+  return launch_pack_jobs(reinterpret_cast<const PackJob*>(ws + UPC_JOBS), (int)jobs.size(), w, ws, BN_C, stream);
+}
+UpbLane upc_lane(float* ws, size_t ws_floats, size_t sets_floats) {
+  const size_t off = UPC_WSETS + upc_align64(sets_floats);
+  return UpbLane{ws + off, ws_floats - off, ws, reinterpret_cast<int*>(ws + UPC_TICKETS), 0};  // (f16: the udet_debug_conv_fp16 hook, conv_prepare)
+}
+}  // namespace
+extern "C" {
+
+size_t udet_debug_upconv_lowres_workspace_bytes(int ldx, int cin, int cout) {
+  if (ldx < 1 || cin < 1 || cout < 1) return 0;
+  const size_t f = upc_floats(ldx, round_up(cout, 4)), b = upc_floats(upc_kct(cout), round_up(cin, 4));
+  return (f > b ? f : b) * sizeof(float);
+}
+int udet_debug_max_segs(void) { return UDET_MAX_SEGS; }
+
+int udet_debug_upconv_lowres_fwd(const float* x, int ldx, const float* w, const float* bias, int act, float alpha, float* y, int ldy, int y_coff,
+                                 float* xhat, int n, int h, int wd, int cin, int cout, int split, void* workspace, size_t workspace_bytes,
+                                 void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "debug_upconv_lowres_fwd";
+  if (act != UDET_ACT_NONE && act != UDET_ACT_LEAKY && act != UDET_ACT_ELU) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  if (ldx % 4 || ldy % 4 || y_coff % 4) { set_error("%s: ldx=%d ldy=%d y_coff=%d must be multiples of 4", who, ldx, ldy, y_coff); return UDET_ERR_ALIGN; }
+  if (ldx < 4 || ldy < 4 || cin > ldx || y_coff < 0 || (cout >= 1 && y_coff + cout > ldy)) {
+    set_error("%s: channel window outside the buffer (x %d of %d, y %d+%d of %d)", who, cin, ldx, y_coff, cout, ldy);
+    return UDET_ERR_SHAPE;
+  }
+  if (split && cout > 16) { set_error("%s: the split form is the plan's for cout <= 16 only", who); return UDET_ERR_ARG; }
+  Layer L;
+  L.cin = cin; L.cout = cout;
+  L.Kc = ldx; L.ldw = round_up(cout, 4);  // (the plan: L.Kc = the source slab's channel stride)
+  L.k_split = round_up(cin, cin <= 4 ? 4 : 8); L.k_gap = 0;
+  L.upb = true; L.upb_bwd = false; L.upb_split = split != 0;
+  L.wupb_off = UPC_WSETS;
+  const size_t sets = (size_t)4 * 36 * L.Kc * L.ldw;
+  UDET_TRY(upc_check(who, x, w, y, xhat, n, h, wd, cin, cout, workspace, workspace_bytes, upc_floats(L.Kc, L.ldw)));
+  float* ws = reinterpret_cast<float*>(workspace);
+  build_upb_launches(L, h, wd);
+  std::vector<PackJob> jobs;
+  PackJob base;
+  memset(&base, 0, sizeof(base));
+  base.gamma_off = base.beta_off = -1;
+  upb_pack_jobs(L, base, jobs);
+  int st = upc_stage(L.upb_f, jobs, w, ws, stream);
+  if (st == UDET_OK) {
+    UpbFwd a;
+    a.N = n; a.h = h; a.w = wd;
+    a.src = x; a.xhat = xhat; a.ld = ldx;
+    a.wsets = ws + L.wupb_off; a.Kc = L.Kc; a.ldw = L.ldw; a.bias = bias;
+    a.y = y; a.ldy = ldy; a.y_coff = y_coff; a.cout = cout; a.act = act; a.alpha = alpha;
+    a.tab = &L.upb_f; a.tab_dev = reinterpret_cast<const ConvTap*>(ws + UPC_TAB); a.split = L.upb_split;
+    a.lane = upc_lane(ws, workspace_bytes / sizeof(float), sets);
+    st = upb_forward(a, stream);
+  }
+  (void)hipStreamSynchronize(stream);  // `jobs` and the tap table are host temporaries
+  return st;
+}
+
+int udet_debug_upconv_lowres_bwd(const float* dy, int ldy, int y_coff, const float* w, float* dx, int ldx, float* dxhat, int n, int h, int wd,
+                                 int cin, int cout, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "debug_upconv_lowres_bwd";
+  if (ldx % 4 || ldy % 4 || y_coff % 4) { set_error("%s: ldx=%d ldy=%d y_coff=%d must be multiples of 4", who, ldx, ldy, y_coff); return UDET_ERR_ALIGN; }
+  const int kct = cout >= 1 ? upc_kct(cout) : 0;  // the launch reads whole padded channel blocks of the dy window
+  if (ldx < 4 || ldy < 4 || cin > ldx || y_coff < 0 || y_coff + kct > ldy) {
+    set_error("%s: channel window outside the buffer (dy %d+%d of %d, dx %d of %d)", who, y_coff, kct, ldy, cin, ldx);
+    return UDET_ERR_SHAPE;
+  }
+  Layer L;
+  L.cin = cin; L.cout = cout;
+  L.Kc = ldx; L.ldw = round_up(cout, 4);
+  L.k_split = round_up(cin, cin <= 4 ? 4 : 8); L.k_gap = 0;
+  L.KcT = kct; L.ldwT = round_up(cin, 4);
+  L.upb = true; L.upb_bwd = true;
+  L.wupbT_off = UPC_WSETS;
+  const size_t sets = (size_t)4 * 36 * L.KcT * L.ldwT;
+  UDET_TRY(upc_check(who, dy, w, dx, dxhat, n, h, wd, cin, cout, workspace, workspace_bytes, upc_floats(L.KcT, L.ldwT)));
+  float* ws = reinterpret_cast<float*>(workspace);
+  build_upb_launches(L, h, wd);
+  std::vector<PackJob> all, jobs;
+  PackJob base;
+  memset(&base, 0, sizeof(base));
+  base.gamma_off = base.beta_off = -1;
+  upb_pack_jobs(L, base, all);
+  for (const PackJob& j : all)  // (the forward sets have no room in this call's workspace: the four mode-10 jobs only)
+    if (j.mode == 10) jobs.push_back(j);
+  int st = upc_stage(L.upb_b, jobs, w, ws, stream);
+  if (st == UDET_OK) {
+    UpbBwd a;
+    a.N = n; a.h = h; a.w = wd;
+    a.du = dy; a.lddu = ldy; a.du_coff = y_coff;
+    a.wsetsT = ws + L.wupbT_off; a.KcT = L.KcT; a.ldwT = L.ldwT; a.cout = cout;
+    a.dxhat = dxhat; a.dsrc = dx; a.ld = ldx; a.cin = cin;
+    a.tab = &L.upb_b; a.tab_dev = reinterpret_cast<const ConvTap*>(ws + UPC_TAB);
+    a.lane = upc_lane(ws, workspace_bytes / sizeof(float), sets);
+    a.f16_xscale = conv_debug_f16_grad_scale_now();  // (udet_debug_conv_fp16_grad_scale; 0: none -- a plan passes 4096)
+    st = upb_dgrad(a, stream);
+  }
+  (void)hipStreamSynchronize(stream);
+  return st;
+}
+
+// host only: no HIP call.  seg [nseg][4] = oy, ox, h, w; seg_tap [nseg + 1]; taps [ntaps][3] = dy, dx, widx
+int udet_debug_upconv_tables(int h, int w, int backward, int* nseg, int* seg, int* seg_tap, int* taps, int taps_cap, int* ntaps) {
+  if (!nseg || !seg || !seg_tap || !taps || !ntaps || taps_cap < 0) { set_error("debug_upconv_tables: bad argument"); return UDET_ERR_ARG; }
+  if (h < 2 || w < 2) { set_error("debug_upconv_tables: the source grid %d x %d must be at least 2 x 2", h, w); return UDET_ERR_SHAPE; }
+  Layer L;
+  build_upb_launches(L, h, w);
+  const Layer::SegLaunch& g = backward ? L.upb_b : L.upb_f;
+  *nseg = g.nseg;
+  *ntaps = (int)g.taps.size();
+  if (*ntaps > taps_cap) { set_error("debug_upconv_tables: %d taps, room for %d", *ntaps, taps_cap); return UDET_ERR_ARG; }
+  for (int s = 0; s < g.nseg; ++s) {
+    seg[4 * s] = g.seg[s].oy; seg[4 * s + 1] = g.seg[s].ox; seg[4 * s + 2] = g.seg[s].h; seg[4 * s + 3] = g.seg[s].w;
+    seg_tap[s] = g.seg_tap[s];
+  }
+  seg_tap[g.nseg] = g.seg_tap[g.nseg];
+  for (int t = 0; t < *ntaps; ++t) { taps[3 * t] = g.taps[t].dy; taps[3 * t + 1] = g.taps[t].dx; taps[3 * t + 2] = g.taps[t].widx; }
+  return UDET_OK;
+}
+
 void udet_debug_set_tuning(int on) {
   conv_set_tuning(on);
   wgrad_set_tuning(on);

@@ -203,6 +203,11 @@ struct Plan {
 #define UDET_SMALL_SUMS 1024   // loss_sums
 Plan* plan_build(const Config& cfg);
 void plan_debug_upb_min_pixels(long v);  // (libudet_debug)
+// Segments and tap tables (L.upb_f, L.upb_b) of the up-conv algebra for a low-resolution source of h x w, h, w >= 2 (plan_build.hip; host only)
+void build_upb_launches(Layer& L, int h, int w);
+// The weight re-layout jobs of an upb layer appended to `jobs`: four mode-9 sets at L.wupb_off and, with L.upb_bwd, four mode-10 sets at
+// L.wupbT_off; `base` carries the source offset of the layer's HWIO weights (plan_pack.hip)
+void upb_pack_jobs(const Layer& L, const PackJob& base, std::vector<PackJob>& jobs);
 // Experiment knobs (tools/knob_bench.py; every knob's 0 is the shipped behaviour).  They exist ONLY in libudet_exp.so, the build of these
 // sources with -DUDET_EXPERIMENT (`make exp`): in the release library plan_knob() is a constant 0, every branch that reads a knob folds
 // away at compile time -- the work-skipping ablation mask (UDET_KNOB_SKIP) included -- and there is no setter to export.

@@ -197,7 +197,7 @@ extern "C" void udet_exp_knob(int id, long v) { plan_debug_knob(id, v); }
 // Segments and tap tables of the recover decoder's up-conv algebra for a low-resolution source of h x w (plan_exec.hip has the algebra).
 // Merge rows that are all zero in a variant (0 interior, 1 last row / column) carry no tap.
 static inline bool upb_used(int parity, int last, int a) { return !last || (parity == 0 ? a < 2 : a < 1); }
-static void build_upb_launches(Layer& L, int h, int w) {
+void build_upb_launches(Layer& L, int h, int w) {
   // forward: 4 output regions {interior, last row, last column, corner} x 4 parity classes; class (py, px), merged tap (a, b) of the
   // quotient pixel q reads x^[q + p + (a, b)] (ring coordinates) with weight set = region
   Layer::SegLaunch& F = L.upb_f;

@@ -94,11 +94,65 @@ static void setup_up_dgrad(ConvParams& p, int N, int H, int W) {
 // {R < H - 1}, H - 1, H, H + 1 times the same for columns -- followed by the adjoint of the ring (upb_ring_fold), which replaces the
 // resize adjoint.  The filter gradient keeps the up-sampled operand.
 // ------------------------------------------------------------------------------------------------------------------------------
-static void fill_segments(ConvParams& p, const Layer::SegLaunch& g, float* ws, int first = 0) {  // segments [first, nseg)
+static void fill_segments(ConvParams& p, const Layer::SegLaunch& g, const ConvTap* tab_dev, int first = 0) {  // segments [first, nseg)
   p.nseg = g.nseg - first;
   memcpy(p.seg, g.seg + first, sizeof(ConvSeg) * p.nseg);
   memcpy(p.seg_tap, g.seg_tap + first, sizeof(int) * (p.nseg + 1));  // (offsets into the whole table)
-  p.tap_tab = reinterpret_cast<const ConvTap*>(ws + g.tab_off);
+  p.tap_tab = tab_dev;
+}
+static void fill_lane(ConvParams& p, const UpbLane& ln, float f16_xscale) {
+  p.partial = ln.partial; p.partial_cap = ln.partial_cap;
+  p.zero16 = ln.zero16; p.tickets = ln.tickets;
+  p.f16 = ln.f16; p.f16_xscale = f16_xscale;
+}
+// The two passes on OPERANDS (plan_run.h): what run_fwd_upb / run_dgrad_upb below launch for a level of the plan, and what
+// libudet_debug's single-layer entry launches for tests/test_upconv_lowres_gpu.py -- one body, so the tests exercise the step's own code.
+int upb_forward(const UpbFwd& a, hipStream_t s) {
+  const int h = a.h, w = a.w;
+  UDET_TRY(launch_upb_ring(a.src, a.ld, a.N, h, w, a.xhat, s));
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = a.N; p.H = h + 2; p.W = w + 2;
+  p.OH = 2 * h; p.OW = 2 * w;
+  p.osy = p.osx = 2; p.isy = p.isx = 1;
+  p.x = a.xhat; p.ldx = a.ld; p.x_coff = 0;
+  p.wp = a.wsets; p.Kc = a.Kc; p.ldw = a.ldw; p.bias = a.bias;
+  p.y = a.y; p.ldy = a.ldy; p.y_coff = a.y_coff; p.Cout = a.cout;
+  p.act = a.act; p.alpha = a.alpha;
+  fill_lane(p, a.lane, 1.f);
+  const Layer::SegLaunch& F = *a.tab;
+  if (a.split) {
+    // <= 16 output channels: the tile-resident kernel (conv_tile.hip) is the fast family and takes no segments -- the interior as an
+    // ordinary four-class launch (segments 0-3 of the table: weight set 0), the twelve border segments in a second, short launch
+    ConvParams q = p;
+    q.OHq = h - 1; q.OWq = w - 1;
+    q.ncls = 4;
+    for (int c = 0; c < 4; ++c) {
+      q.cls_tap[c] = q.ntaps;
+      for (int t = F.seg_tap[c]; t < F.seg_tap[c + 1]; ++t) q.taps[q.ntaps++] = F.taps[t];
+    }
+    q.cls_tap[4] = q.ntaps;
+    UDET_TRY(launch_conv(q, s));
+    fill_segments(p, F, a.tab_dev, 4);
+  } else {
+    fill_segments(p, F, a.tab_dev);
+  }
+  return launch_conv(p, s);
+}
+int upb_dgrad(const UpbBwd& a, hipStream_t s) {
+  const int h = a.h, w = a.w;
+  ConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = a.N; p.H = 2 * h; p.W = 2 * w;
+  p.OH = h + 2; p.OW = w + 2;
+  p.osy = p.osx = 1; p.isy = p.isx = 2;
+  fill_segments(p, *a.tab, a.tab_dev);
+  p.x = a.du; p.ldx = a.lddu; p.x_coff = a.du_coff;
+  p.wp = a.wsetsT; p.Kc = a.KcT; p.ldw = a.ldwT; p.kreal = a.cout;
+  p.y = a.dxhat; p.ldy = a.ld; p.y_coff = 0; p.Cout = a.cin;
+  fill_lane(p, a.lane, a.f16_xscale);
+  UDET_TRY(launch_conv(p, s));
+  return launch_upb_ring_fold(a.dxhat, a.ld, a.N, h, w, a.dsrc, s);
 }
 
 // fp16 mode: gradient operands are multiplied by this power of two before the fp16 conversion (and the fp32 accumulators divided by it)
@@ -126,39 +180,26 @@ static void bind_emit(Plan* P, ConvParams& p, const Emit& em, int coff, float* w
   p.uact = em.act; p.ualpha = em.alpha; p.u_c0 = em.c0; p.u_c1 = em.c1;
 }
 
+// the lane-private scratch of fill_common as upb_forward / upb_dgrad take it
+static UpbLane upb_lane(Plan* P, float* ws, int slot) {
+  ConvParams c;
+  fill_common(P, c, ws, slot);
+  return UpbLane{c.partial, c.partial_cap, c.zero16, c.tickets, c.f16};
+}
+
 static int run_fwd_upb(Plan* P, const Layer& L, int N, float* ws, const Lane& ln) {
   hipStream_t s = ln.s;
-  const Buf &bs = P->buf(L.src), &bp = P->buf(L.xhat);
-  const int h = bs.h, w = bs.w;
+  const Buf &bs = P->buf(L.src), &bp = P->buf(L.xhat), &by = P->buf(L.y);
   prof_begin(P, PROF_CONV_FWD, layer_flops(L, N) * 9.0 / 16.0, layer_bytes(L, N), s, L.name.c_str());
-  UDET_TRY(launch_upb_ring(ws + bs.off, bs.ld, N, h, w, ws + bp.off, s));
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.N = N; p.H = h + 2; p.W = w + 2;
-  p.OH = 2 * h; p.OW = 2 * w;
-  p.osy = p.osx = 2; p.isy = p.isx = 1;
-  bind_x(p, bp, 0, ws);
-  bind_w(p, L.wupb_off, L.Kc, L.ldw, ws); p.bias = ws + L.bias_f_off;
-  bind_y(p, P->buf(L.y), L.y_coff, L.cout, ws);
-  p.act = L.act; p.alpha = L.alpha;
-  fill_common(P, p, ws, ln.slot);
-  if (L.upb_split) {
-    // <= 16 output channels: the tile-resident kernel (conv_tile.hip) is the fast family and takes no segments -- the interior as an
-    // ordinary four-class launch (segments 0-3 of the table: weight set 0), the twelve border segments in a second, short launch
-    ConvParams q = p;
-    q.OHq = h - 1; q.OWq = w - 1;
-    q.ncls = 4;
-    for (int c = 0; c < 4; ++c) {
-      q.cls_tap[c] = q.ntaps;
-      for (int t = L.upb_f.seg_tap[c]; t < L.upb_f.seg_tap[c + 1]; ++t) q.taps[q.ntaps++] = L.upb_f.taps[t];
-    }
-    q.cls_tap[4] = q.ntaps;
-    UDET_TRY(launch_conv(q, s));
-    fill_segments(p, L.upb_f, ws, 4);
-  } else {
-    fill_segments(p, L.upb_f, ws);
-  }
-  UDET_TRY(launch_conv(p, s));
+  UpbFwd a;
+  a.N = N; a.h = bs.h; a.w = bs.w;
+  a.src = ws + bs.off; a.xhat = ws + bp.off; a.ld = bp.ld;
+  a.wsets = ws + L.wupb_off; a.Kc = L.Kc; a.ldw = L.ldw; a.bias = ws + L.bias_f_off;
+  a.y = ws + by.off; a.ldy = by.ld; a.y_coff = L.y_coff; a.cout = L.cout;
+  a.act = L.act; a.alpha = L.alpha;
+  a.tab = &L.upb_f; a.tab_dev = reinterpret_cast<const ConvTap*>(ws + L.upb_f.tab_off); a.split = L.upb_split;
+  a.lane = upb_lane(P, ws, ln.slot);
+  UDET_TRY(upb_forward(a, s));
   prof_end(P, s);
   return UDET_OK;
 }
@@ -166,22 +207,17 @@ static int run_fwd_upb(Plan* P, const Layer& L, int N, float* ws, const Lane& ln
 int run_dgrad_upb(Plan* P, const Layer& L, int N, int du, int dxhat, int dsrc, float* ws, const Lane& ln) {
   hipStream_t s = ln.s;
   if (skip_launch(1, L.net)) return UDET_OK;
-  const Buf &bp = P->buf(dxhat), &bd = P->buf(dsrc);
-  const int h = bd.h, w = bd.w;
+  const Buf &bu = P->buf(du), &bp = P->buf(dxhat), &bd = P->buf(dsrc);
   prof_begin(P, PROF_CONV_DGRAD, layer_flops(L, N) * 9.0 / 16.0, layer_bytes(L, N), s, L.name.c_str());
-  ConvParams p;
-  memset(&p, 0, sizeof(p));
-  p.N = N; p.H = 2 * h; p.W = 2 * w;
-  p.OH = h + 2; p.OW = w + 2;
-  p.osy = p.osx = 1; p.isy = p.isx = 2;
-  fill_segments(p, L.upb_b, ws);
-  bind_x(p, P->buf(du), L.y_coff, ws);
-  bind_w(p, L.wupbT_off, L.KcT, L.ldwT, ws); p.kreal = L.cout;
-  bind_y(p, bp, 0, L.cin, ws);
-  fill_common(P, p, ws, ln.slot);
-  p.f16_xscale = UDET_F16_GRAD_SCALE;
-  UDET_TRY(launch_conv(p, s));
-  UDET_TRY(launch_upb_ring_fold(ws + bp.off, bp.ld, N, h, w, ws + bd.off, s));
+  UpbBwd a;
+  a.N = N; a.h = bd.h; a.w = bd.w;
+  a.du = ws + bu.off; a.lddu = bu.ld; a.du_coff = L.y_coff;
+  a.wsetsT = ws + L.wupbT_off; a.KcT = L.KcT; a.ldwT = L.ldwT; a.cout = L.cout;
+  a.dxhat = ws + bp.off; a.dsrc = ws + bd.off; a.ld = bp.ld; a.cin = L.cin;
+  a.tab = &L.upb_b; a.tab_dev = reinterpret_cast<const ConvTap*>(ws + L.upb_b.tab_off);
+  a.lane = upb_lane(P, ws, ln.slot);
+  a.f16_xscale = UDET_F16_GRAD_SCALE;
+  UDET_TRY(upb_dgrad(a, s));
   prof_end(P, s);
   return UDET_OK;
 }

@@ -8,6 +8,23 @@
 namespace udet {
 
 // ------------------------------------------------------- init / packing ----
+// up-conv algebra of the recover decoder: four forward and four backward-data weight sets (pack modes 9 / 10), set
+// r = (last row) + 2 (last column) -> job variant (row, column) in {interior, last}
+void upb_pack_jobs(const Layer& L, const PackJob& base, std::vector<PackJob>& jobs) {
+  PackJob j = base;
+  for (int r = 0; r < 4; ++r) {
+    j.T = 36; j.gamma_off = -1;
+    j.dst_off = (long)(L.wupb_off + (size_t)r * 36 * L.Kc * L.ldw); j.R = L.cin; j.C = L.cout; j.Kc = L.Kc; j.ldw = L.ldw; j.k_split = L.k_split; j.k_gap = L.k_gap;
+    j.mode = 9; j.beta_off = (long)((r & 1) * 3 + (r >> 1)); j.total = (long)L.Kc * L.ldw;  // (one work item per (k, n))
+    jobs.push_back(j);
+    if (L.upb_bwd) {  // (a level that keeps the up-sampled form for backward-data never reads these)
+      j.dst_off = (long)(L.wupbT_off + (size_t)r * 36 * L.KcT * L.ldwT); j.Kc = L.KcT; j.ldw = L.ldwT; j.k_split = L.KcT; j.k_gap = 0;
+      j.mode = 10; j.total = (long)L.KcT * L.ldwT;
+      jobs.push_back(j);
+    }
+  }
+}
+
 int plan_init_workspace(Plan* P, float* ws, hipStream_t s) {
   UDET_HIP(hipMemsetAsync(ws, 0, P->arena_floats * sizeof(float), s));
   for (int net = 1; net <= 2; ++net) {
@@ -55,19 +72,7 @@ int plan_init_workspace(Plan* P, float* ws, hipStream_t s) {
         jobs.push_back(j);
         j.T = T;
       }
-      if (L.upb)  // up-conv algebra of the recover decoder: four forward and four backward-data weight sets (pack modes 9 / 10), set
-        for (int r = 0; r < 4; ++r) {  // r = (last row) + 2 (last column) -> job variant (row, column) in {interior, last}
-          j.T = 36; j.gamma_off = -1;
-          j.dst_off = (long)(L.wupb_off + (size_t)r * 36 * L.Kc * L.ldw); j.R = L.cin; j.C = L.cout; j.Kc = L.Kc; j.ldw = L.ldw; j.k_split = L.k_split; j.k_gap = L.k_gap;
-          j.mode = 9; j.beta_off = (long)((r & 1) * 3 + (r >> 1)); j.total = (long)L.Kc * L.ldw;  // (one work item per (k, n))
-          jobs.push_back(j);
-          if (L.upb_bwd) {  // (a level that keeps the up-sampled form for backward-data never reads these)
-            j.dst_off = (long)(L.wupbT_off + (size_t)r * 36 * L.KcT * L.ldwT); j.Kc = L.KcT; j.ldw = L.ldwT; j.k_split = L.KcT; j.k_gap = 0;
-            j.mode = 10; j.total = (long)L.KcT * L.ldwT;
-            jobs.push_back(j);
-          }
-          j.T = T; j.beta_off = beoff;
-        }
+      if (L.upb) upb_pack_jobs(L, j, jobs);
       if (L.wino_off) {  // Winograd operand of the forward pass: K = input channels with the slab's gap map, N = output channels
         j.dst_off = (long)L.wino_off; j.R = L.cin; j.C = L.cout; j.Kc = L.Kc; j.ldw = L.wino_np; j.k_split = L.k_split; j.k_gap = L.k_gap;
         j.mode = 7; j.total = (long)(L.Kc / 8) * 2 * L.wino_np;  // work items (wino_pack.h)

@@ -49,5 +49,46 @@ int run_dgrad_pair(Plan* P, const DgradJob& ja, const DgradJob& jb, float* ws, c
 // gradient w.r.t. the low-resolution source of an upb level: dsrc (written) from dU (`du` buffer, channels [0, KcT))
 int run_dgrad_upb(Plan* P, const Layer& L, int N, int du, int dxhat, int dsrc, float* ws, const Lane& ln);
 int run_wgrad(Plan* P, const Layer& L, int N, int dy, bool dy_is_du, const float* w_flat, float* g_flat, float* ws, const Lane& ln);
+// The up-conv algebra's two passes on operands instead of plan buffers: run_fwd_upb / run_dgrad_upb fill these from the plan, the
+// single-layer entry of libudet_debug (udet_debug_upconv_lowres_*) from its arguments.
+struct UpbLane {  // what fill_common gives a launch: split-K slabs, the zero block, the ticket counters, the fp16 switch
+  float* partial;
+  size_t partial_cap;
+  const float* zero16;
+  int* tickets;
+  int f16;
+};
+struct UpbFwd {
+  int N, h, w;                       // low-resolution source grid
+  const float* src;                  // [N, h, w, ld]
+  float* xhat;                       // ringed source [N, h + 2, w + 2, ld] (written)
+  int ld;
+  const float* wsets;                // four weight sets [4][36][Kc][ldw] (pack mode 9)
+  int Kc, ldw;
+  const float* bias;
+  float* y;                          // [N, 2h, 2w, ldy], channels [y_coff, y_coff + cout)
+  int ldy, y_coff, cout, act;
+  float alpha;
+  const Layer::SegLaunch* tab;       // build_upb_launches' forward table and its device copy
+  const ConvTap* tab_dev;
+  bool split;                        // interior as a four-class launch + the twelve border segments (Layer::upb_split)
+  UpbLane lane;
+};
+struct UpbBwd {
+  int N, h, w;
+  const float* du;                   // [N, 2h, 2w, lddu], channels [du_coff, du_coff + KcT)
+  int lddu, du_coff;
+  const float* wsetsT;               // [4][36][KcT][ldwT] (pack mode 10)
+  int KcT, ldwT, cout;
+  float* dxhat;                      // ringed gradient [N, h + 2, w + 2, ld], channels [0, cin) (written)
+  float* dsrc;                       // [N, h, w, ld]: the ring's adjoint of dxhat (written)
+  int ld, cin;
+  const Layer::SegLaunch* tab;       // the backward-data table and its device copy
+  const ConvTap* tab_dev;
+  float f16_xscale;                  // fp16 mode: scale of the gradient operand
+  UpbLane lane;
+};
+int upb_forward(const UpbFwd& a, hipStream_t s);
+int upb_dgrad(const UpbBwd& a, hipStream_t s);
 
 }  // namespace udet
