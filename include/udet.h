@@ -246,6 +246,50 @@ int udet_link_detections_ragged(const int* labels, int n, const long long* offse
                                 long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
                                 size_t workspace_bytes, void* stream);
 
+/* udet_link_detections_ragged with gap bridging: a row that found no predecessor in the frame before it may continue a
+ * track that ended up to max_gap frames earlier (max_gap in 1..UDET_TRACK_MAX_GAP).  labels .. link, min_iou_permille, inter, match, ids,
+ * linked, seq_tracks, next_id: as above.  In the place of the carried frame stands a history: the last m <= max_gap + 1 frames of the
+ * sequence frame 0 may continue, oldest first, every one hist_h x hist_w -- hist_labels (device int32 [m][hist_h * hist_w]), hist_dets
+ * (int64 [m][k][UDET_DET_FIELDS]), hist_counts (int64 [m][3]), hist_ids (int32 [m][k]), hist_open (int32 [m][k], in / out: the `open` the
+ * earlier calls wrote for these frames) and hist_next_id (int32 [1]); absent: every pointer NULL and m = hist_h = hist_w = 0.  Frame 0's
+ * predecessor is history frame m - 1; a history of another size than frame 0 means frame 0 starts a sequence.
+ * Stage 1 is udet_link_detections_ragged's link, unchanged: linked, inter and match are equal to it entry for entry.  Stage 2 runs per
+ * sequence, in frame order, for a linked frame c, in exact integers:
+ *  - a row a of an earlier frame f of the same sequence is open while no row of any later frame continues it, through stage 1
+ *    (match[f + 1][b] = a) or through a bridge; an orphan is a row b < rows_c with match[c][b] = -1.
+ *  - gap_inter[c][d - 2][a][b] (device int64 [n][max_gap][k][k]), d = 2 .. max_gap + 1 with frame c - d in c's sequence (no link = 0,
+ *    no size change and no sequence start in between; the sequence may reach back into the history) = the number of positions where
+ *    labels_{c-d} = root_a + 1 and labels_c = root_b + 1, a < rows_{c-d}, b < rows_c; 0 everywhere else.  The ranks are looked up and
+ *    the labels' range is taken as for inter.
+ *  - (d, a, b) is a candidate when b is an orphan, (c - d, a) is open, gap_inter > 0 and 1000 gap_inter >= min_iou_permille (area_a +
+ *    area_b - gap_inter).  Greedy choice: repeatedly the candidate with the largest gap_inter / union among orphans still free and rows
+ *    still open, compared by 64-bit cross-multiplication, ties to the smaller d, then the smaller a, then the smaller b.  The winner
+ *    gets back[c][b] = d, prev[c][b] = a, ids[c][b] = ids[c - d][a], and (c - d, a) is closed.
+ *  - rows matched in stage 1 have back = 1, prev = match: a stage-1 match is never undone by a better bridge.  The remaining orphans take
+ *    the sequence's next free ids in rank order, back = 0, prev = -1, as every row of a sequence's first frame; rows past rows_c get
+ *    ids = -1, back = 0, prev = -1 (back, prev: device int32 [n][k]).  Within a frame no id occurs twice.
+ *  - open (device int32 [n][k]): 1 for a < rows_c without a successor so far, else 0 -- with ids the state the next call needs.  A
+ *    history row that this call continues, by stage 1 or by a bridge, is closed in hist_open in place.
+ * Six launches whatever n, the sequences, the components and max_gap: the four phases above with the id walk replaced, the zeroing of
+ * gap_inter with the older history frames' ranks, and the gap-overlap pass (the overlap pass once per distance, d on a grid axis).  One
+ * workgroup per sequence walks its frames with the open flags, ids and areas of the last max_gap + 1 frames in LDS: per frame at most
+ * `orphans` rounds of a block arg-max over the candidates, then the fresh ids by a ballot prefix.  No host round trip, no workgroup
+ * waits for another, integer atomics only: identical from run to run and for a sequence alone or inside a batch.
+ * workspace: udet_link_detections_gap_workspace_bytes(total_pixels, n, k, max_gap, m, hist_h, hist_w) bytes (4 per pixel of the batch
+ * and of the history), 4-byte aligned.  UDET_ERR_ARG, nothing enqueued: everything udet_link_detections_ragged refuses, a NULL gap_inter
+ * / back / prev / open, max_gap outside 1..UDET_TRACK_MAX_GAP, m outside 0..max_gap + 1, a history that is neither absent nor whole, a
+ * short or misaligned workspace, an int32 buffer not 4-byte or gap_inter / hist_dets / hist_counts not 8-byte aligned.  Every index a
+ * kernel forms is bounded whatever labels, dets, counts, ids, open, the history and the workspace hold. */
+#define UDET_TRACK_MAX_GAP 8
+size_t udet_link_detections_gap_workspace_bytes(size_t total_pixels, int n, int k, int max_gap, int m, int hist_h, int hist_w);
+int udet_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                    size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                    int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                    const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                    int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                    int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+
 /* The boxes of the written detections painted in the colour of their track, in place: the contract of udet_draw_boxes_ragged with two
  * differences.  The colour of row r of sample i is palette[ids[i][r] mod palette_size] (ids: device int32 [n][k], what
  * udet_link_detections_ragged wrote; palette: device uint32 [palette_size], 0xRRGGBB, palette_size in 1..UDET_TRACK_MAX_PALETTE), and a

@@ -8,6 +8,13 @@ synchronise) and the loop.  They alternate over `--rounds` rounds after a warm-u
 figures are the per-batch median and the min .. max over the rounds.
 
     python tools/tracks_bench.py [--n 16 --h 480 --w 854 --k 16 --min_area 64 --blobs 12 --iters 10 --rounds 5]
+
+--max_gap G [G ...] measures the link with gap bridging (udet_link_detections_gap_ragged: six launches) as well: every
+blob is then blanked on one or two frames inside its span, and each G is timed through the wrapper in the same rounds as G = 0 (the
+old entry) and next to .cpu() + the numpy restatement with that G (tests/test_track_gaps.py, bridge_np), with which it must be equal in
+every entry first.  The JSON line gains "max_gap": per G the two timings, the rows bridged and the tracks that remain.
+
+    python tools/tracks_bench.py --max_gap 1 2 8
 """
 import argparse
 import json
@@ -24,9 +31,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 LAUNCHES = 4  # csrc/tracks.hip: init, overlap, match, ids
 
 
-def moving_blobs(n, h, w, blobs, rng):
+def moving_blobs(n, h, w, blobs, rng, blank=False):
     """n binary frames [h, w]: `blobs` discs that drift a few pixels per frame and change their radius, each present over its own span of
-    frames, plus a few single-pixel specks per frame."""
+    frames, plus a few single-pixel specks per frame.  blank: every blob is also missing from one or two consecutive frames inside its
+    span (drawn after everything else, so that the frames without it are what they were)."""
     y, x = np.mgrid[:h, :w]
     cy, cx = rng.uniform(0.1 * h, 0.9 * h, blobs), rng.uniform(0.1 * w, 0.9 * w, blobs)
     vy, vx = rng.uniform(-4, 4, blobs), rng.uniform(-6, 6, blobs)
@@ -40,6 +48,17 @@ def moving_blobs(n, h, w, blobs, rng):
                 m[(y - cy[b] - vy[b] * t) ** 2 + (x - cx[b] - vx[b] * t) ** 2 <= (r0[b] + dr[b] * t) ** 2] = 1
         m[rng.integers(0, h, 200), rng.integers(0, w, 200)] = 1
         frames.append(m)
+    if blank:
+        at, length = rng.integers(first + 1, np.maximum(first + 2, last - 2)), rng.integers(1, 3, blobs)
+        for t in range(n):
+            gone = [b for b in range(blobs) if at[b] <= t < at[b] + length[b]]
+            if gone:
+                m = np.zeros((h, w), np.uint8)
+                for b in range(blobs):
+                    if first[b] <= t < last[b] and b not in gone:
+                        m[(y - cy[b] - vy[b] * t) ** 2 + (x - cx[b] - vx[b] * t) ** 2 <= (r0[b] + dr[b] * t) ** 2] = 1
+                frames[t] = m | (frames[t] & (np.add.reduce([(y - cy[b] - vy[b] * t) ** 2 + (x - cx[b] - vx[b] * t) ** 2 <= (r0[b] + dr[b] * t) ** 2
+                                                             for b in gone]) == 0))  # the specks outside the blanked discs stay
     return frames
 
 
@@ -92,11 +111,12 @@ def main():
     for name, default in (("n", 16), ("h", 480), ("w", 854), ("k", 16), ("min_area", 64), ("blobs", 12), ("iters", 10), ("rounds", 5)):
         ap.add_argument("--" + name, type=int, default=default)
     ap.add_argument("--min_iou", type=float, default=0.1)
+    ap.add_argument("--max_gap", type=int, nargs="*", default=[], help="also measure the link with gap bridging for these G (1..8)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from unsupervised_detection_amd.native_results import component_boxes, link_detections, min_iou_permille, select_components
     from unsupervised_detection_amd.ragged import PackedLayout
-    frames = moving_blobs(a.n, a.h, a.w, a.blobs, np.random.default_rng(0))
+    frames = moving_blobs(a.n, a.h, a.w, a.blobs, np.random.default_rng(0), blank=bool(a.max_gap))
     hw = [(a.h, a.w)] * a.n
     layout = PackedLayout.packed(hw)
     binary = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).cuda()
@@ -116,8 +136,33 @@ def main():
         assert g.dtype == w.dtype and np.array_equal(g, w)
     assert int(got.next_id.cpu()[0]) == want[5]
     torch.cuda.synchronize()
+    gaps = {}
+    if a.max_gap:  # the restatement of the tests is the alternative: .cpu() of the same three buffers, then numpy and Python
+        sys.path.append(os.path.join(ROOT, "tests"))
+        from test_track_gaps import GAP_FIELDS, bridge_np
+
+        def host_gap(g):
+            lab = sel.labels.cpu().numpy().reshape(a.n, a.h, a.w)
+            return bridge_np(list(lab), det.dets.cpu().numpy(), det.counts.cpu().numpy(), link, permille, g)
+        for g in a.max_gap:
+            got_g, want_g = link_detections(sel, det, link=d_link, min_iou=a.min_iou, max_gap=g), host_gap(g)
+            for f, v in zip(GAP_FIELDS, got_g.host() + got_g.host_gaps()):
+                assert np.array_equal(v, getattr(want_g, f)), (g, f)
+            gaps[g] = {"bridged": int((want_g.back >= 2).sum()), "tracks": int(want_g.next_id), "device": [], "host": []}
+        torch.cuda.synchronize()
     t = {"device": [], "host": []}
     for _ in range(a.rounds):
+        for g, rec in gaps.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                link_detections(sel, det, link=d_link, min_iou=a.min_iou, max_gap=g)
+            e1.record()
+            torch.cuda.synchronize()
+            rec["device"].append(e0.elapsed_time(e1) / a.iters)
+            t0 = time.perf_counter()
+            host_gap(g)
+            rec["host"].append((time.perf_counter() - t0) * 1e3)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(a.iters):
@@ -133,7 +178,9 @@ def main():
     print(json.dumps({"shape": [a.n, a.h, a.w], "k": a.k, "min_area": a.min_area, "min_iou": a.min_iou, "iters": a.iters, "rounds": a.rounds,
                       "device": torch.cuda.get_device_name(0), "launches": LAUNCHES, "rows_mean": float(counts[:, 2].mean()),
                       "matched": int((want[1] >= 0).sum()), "tracks": int(want[5]), "link_detections": stat(t["device"]),
-                      "host": stat(t["host"]), "ratio_host_over_link_detections": float(np.median(t["host"]) / np.median(t["device"]))}))
+                      "host": stat(t["host"]), "ratio_host_over_link_detections": float(np.median(t["host"]) / np.median(t["device"])),
+                      **({"max_gap": {str(g): {"launches": 6, "bridged": r["bridged"], "tracks": r["tracks"], "link_detections": stat(r["device"]),
+                                               "host": stat(r["host"])} for g, r in gaps.items()}} if gaps else {})}))
 
 
 if __name__ == "__main__":

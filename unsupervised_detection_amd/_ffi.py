@@ -84,6 +84,9 @@ sig("udet_draw_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_i,
 sig("udet_link_detections_workspace_bytes", c_sz, c_sz, c_i, c_i, c_i, c_i)
 sig("udet_link_detections_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i,
     c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_link_detections_gap_workspace_bytes", c_sz, c_sz, c_i, c_i, c_i, c_i, c_i, c_i)
+sig("udet_link_detections_gap_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p,
+    c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
 sig("udet_draw_track_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p)
 sig("udet_histogram_limits", c_i, c_p, c_i)
 sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)

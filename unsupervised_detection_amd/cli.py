@@ -69,7 +69,10 @@ area, centroid, score (the mean restored soft mask over the component) and root,
 detections of consecutive frames of a sequence by mask overlap -- a box continues the box of the frame before it with which its component
 shares the largest IoU, at least --track_min_iou (0.1) -- and numbers the tracks per sequence: the records gain track / prev / iou,
 <out>/tracks/<sequence>.json lists every track, and --overlay_boxes paints each box in its track's colour
-(native_results.link_detections, visualize.draw_track_boxes).  Like the
+(native_results.link_detections, visualize.draw_track_boxes).  --track_max_gap G (needs --tracks; 0..8, default 0: off) lets a box
+without a predecessor in the frame before it continue a track whose component was missing for up to G frames, by the same IoU rule
+against that track's last-seen component: the object keeps its id and its colour, the records gain back, the tracks span / gaps and
+the sequences bridged.  Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
 runs)."""
@@ -171,6 +174,8 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--overlay_box_colour", default="255,255,0", help="r,g,b of the boxes")
     ap.add_argument("--tracks", action="store_true", help="with --detections: link the boxes of consecutive frames: <out>/tracks/<sequence>.json")
     ap.add_argument("--track_min_iou", type=float, default=0.1, help="the smallest mask IoU that links two boxes")
+    ap.add_argument("--track_max_gap", type=int, default=0,
+                    help="with --tracks: a box may continue a track whose component was missing for up to this many frames (0..8; 0: none)")
 
 
 def _overlay(flags):
@@ -211,15 +216,18 @@ def _detections(flags):
 def _tracks(flags):
     """--tracks and its parameter as restore_results_dir takes them: None without --tracks.  --tracks without --detections, or a bad
     value, is a SystemExit."""
+    gap = getattr(flags, "track_max_gap", 0)
     if not getattr(flags, "tracks", False):
+        if gap:
+            raise SystemExit("--track_max_gap bridges the frames in which a track's component is missing: it needs --tracks")
         return None
     if not getattr(flags, "detections", False):
         raise SystemExit("--tracks links the detections of consecutive frames: it needs --detections")
     from .native_results import track_params
     try:
-        return track_params({"min_iou": flags.track_min_iou})
+        return track_params({"min_iou": flags.track_min_iou, "max_gap": gap})
     except ValueError as e:
-        raise SystemExit("--tracks: {} (--track_min_iou)".format(e))
+        raise SystemExit("--tracks: {} (--track_min_iou / --track_max_gap)".format(e))
 
 
 def check_frames_component(flags):

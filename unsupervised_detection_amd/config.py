@@ -68,6 +68,8 @@ _DEFS = [
     # at least track_min_iou) into D/native/tracks/<sequence>.json (native_results.link_detections)
     ("tracks", bool, False),
     ("track_min_iou", float, 0.1),
+    # ... and a box may continue a track whose component was missing for up to track_max_gap frames (0..8, 0: off)
+    ("track_max_gap", int, 0),
 ]
 
 

@@ -257,6 +257,64 @@ int udet_link_detections_ragged(const int* labels, int n, const long long* offse
                                        linked, seq_tracks, next_id, workspace, (hipStream_t)stream);
 }
 
+// the history of udet_link_detections_gap_ragged: absent (no pointer, m = 0, 0 x 0) or whole (every pointer, 1..max_gap + 1 frames of at
+// least 1 x 1 and below 2^31 pixels each)
+static bool link_history_ok(int max_gap, int m, const void* labels, int h, int w, const void* dets, const void* counts, const void* ids,
+                            const void* open, const void* next_id) {
+  if (!labels && !dets && !counts && !ids && !open && !next_id) return m == 0 && h == 0 && w == 0;
+  return labels && dets && counts && ids && open && next_id && m >= 1 && m <= max_gap + 1 && h >= 1 && w >= 1 &&
+         (long)h * w <= 0x7fffffffL;
+}
+size_t udet_link_detections_gap_workspace_bytes(size_t total_pixels, int n, int k, int max_gap, int m, int hist_h, int hist_w) {
+  if (n < 1 || total_pixels < 1 || k < 1 || k > UDET_DET_MAX_K || max_gap < 1 || max_gap > UDET_TRACK_MAX_GAP) return 0;
+  if (m == 0 ? (hist_h != 0 || hist_w != 0) : (m < 1 || m > max_gap + 1 || hist_h < 1 || hist_w < 1 || (long)hist_h * hist_w > 0x7fffffffL))
+    return 0;
+  return link_detections_gap_workspace_bytes(total_pixels, m, hist_h, hist_w);
+}
+int udet_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                    size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                    int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                    const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                    int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                    int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  if (bad_batch("link_detections_gap_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (!labels || !offsets || !hw || !dets || !counts || !link || !inter || !match || !ids || !linked || !seq_tracks || !next_id ||
+      !gap_inter || !back || !prev || !open) {
+    set_error("link_detections_gap_ragged: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)");
+    return UDET_ERR_ARG;
+  }
+  if (k < 1 || k > UDET_DET_MAX_K || min_iou_permille < 1 || min_iou_permille > 1000 || max_gap < 1 || max_gap > UDET_TRACK_MAX_GAP) {
+    set_error("link_detections_gap_ragged: k = %d in 1..UDET_DET_MAX_K = %d, min_iou_permille = %d in 1..1000 and max_gap = %d in "
+              "1..UDET_TRACK_MAX_GAP = %d are required", k, UDET_DET_MAX_K, min_iou_permille, max_gap, UDET_TRACK_MAX_GAP);
+    return UDET_ERR_ARG;
+  }
+  if (!link_history_ok(max_gap, m, hist_labels, hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id)) {
+    set_error("link_detections_gap_ragged: the history is either absent (no pointer, m = 0, 0 x 0) or whole (labels, dets, counts, ids, "
+              "open and next id; m = %d in 1..max_gap + 1 = %d frames of %d x %d, at least 1 x 1 and below 2^31 pixels)", m, max_gap + 1,
+              hist_h, hist_w);
+    return UDET_ERR_ARG;
+  }
+  if (bad_workspace("link_detections_gap_ragged", workspace, workspace_bytes,
+                    link_detections_gap_workspace_bytes(total_pixels, m, hist_h, hist_w), 4))
+    return UDET_ERR_ARG;
+  const uintptr_t a4 = reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(link) | reinterpret_cast<uintptr_t>(hist_labels) |
+                       reinterpret_cast<uintptr_t>(hist_ids) | reinterpret_cast<uintptr_t>(hist_open) |
+                       reinterpret_cast<uintptr_t>(hist_next_id) | reinterpret_cast<uintptr_t>(match) | reinterpret_cast<uintptr_t>(ids) |
+                       reinterpret_cast<uintptr_t>(linked) | reinterpret_cast<uintptr_t>(seq_tracks) | reinterpret_cast<uintptr_t>(next_id) |
+                       reinterpret_cast<uintptr_t>(back) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(open);
+  const uintptr_t a8 = reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(hist_dets) |
+                       reinterpret_cast<uintptr_t>(hist_counts) | reinterpret_cast<uintptr_t>(inter) | reinterpret_cast<uintptr_t>(gap_inter);
+  if ((a4 & 3) || (a8 & 7)) {
+    set_error("link_detections_gap_ragged: the int32 buffers must be 4-byte aligned, dets, counts, inter and gap_inter 8-byte aligned");
+    return UDET_ERR_ARG;
+  }
+  return launch_link_detections_gap_ragged(labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k, link, max_gap, m, hist_labels,
+                                           hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id, min_iou_permille, inter,
+                                           match, ids, linked, seq_tracks, next_id, gap_inter, back, prev, open, workspace,
+                                           (hipStream_t)stream);
+}
+
 int udet_draw_track_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
                                  const long long* dets, const long long* counts, int k, const int* ids, int thickness,
                                  const unsigned* palette, int palette_size, void* stream) {

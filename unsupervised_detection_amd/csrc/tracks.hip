@@ -16,7 +16,8 @@
 // Integer work only, no workgroup waits for another: the outputs are exact, identical from run to run and for a sequence alone or inside
 // a batch.  A label outside 1..H_i*W_i is background and a root outside 0..H_i*W_i-1 is not entered, so nothing indexes outside its own
 // sample whatever labels and dets hold; every other index comes from offsets / hw, which the caller validates on the host
-// (native_results.link_detections), and from ranks clamped to k.
+// (native_results.link_detections), and from ranks clamped to k.  udet_link_detections_gap_ragged (below the four
+// kernels) adds the bridge across frames in which a component is missing: six launches, the same properties.
 #include "common.h"
 #include "elementwise.h"
 #include "wave_runs.h"
@@ -75,29 +76,29 @@ __global__ __launch_bounds__(256) void link_init_kernel(int n, const long long* 
   }
 }
 
-__global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict__ labels, const long long* __restrict__ offsets,
-                                                           const int* __restrict__ hw, size_t total_pixels,
-                                                           const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
-                                                           LinkCarry carry, const int* __restrict__ linked, const int* __restrict__ lookup,
-                                                           unsigned long long* __restrict__ inter) {
-  extern __shared__ int link_lds[];  // hist [k * k], root_p [k], root_c [k]
-  const int i = blockIdx.y, t = threadIdx.x, lane = t & 63;
-  if (!linked[i]) return;  // block-uniform; a linked frame 0 has a carried frame of its size
-  int* __restrict__ hist = link_lds;
-  int* __restrict__ root_p = link_lds + k * k;
+// The rows of one frame of a sequence against the rows of an earlier one of its size: the workgroup's share of the pixels into its k x k
+// histogram, then one 64-bit atomic per non-zero entry into out [k][k].  at_p / at_c: where the two frames' ranks lie in the lookup.
+struct LinkSide {
+  const int* labels;
+  const long long* dets;
+  int rows;
+  size_t at;
+};
+
+__device__ __forceinline__ void link_overlap_pass(LinkSide fp, LinkSide fc, int W, long long HW, int k, const int* __restrict__ lookup,
+                                                  unsigned long long* __restrict__ out, int* __restrict__ lds) {
+  const int t = threadIdx.x, lane = t & 63;
+  int* __restrict__ hist = lds;  // hist [k * k], root_p [k], root_c [k]
+  int* __restrict__ root_p = lds + k * k;
   int* __restrict__ root_c = root_p + k;
-  const int W = hw[2 * i + 1];
-  const long long HW = (long long)hw[2 * i] * W;  // the predecessor's too
-  const size_t oc = (size_t)offsets[i], op = i ? (size_t)offsets[i - 1] : total_pixels;
-  const int* __restrict__ lab_c = labels + oc;
-  const int* __restrict__ lab_p = i ? labels + op : carry.labels;
-  const long long* __restrict__ dets_c = dets + (size_t)i * k * UDET_DET_FIELDS;
-  const long long* __restrict__ dets_p = i ? dets_c - (size_t)k * UDET_DET_FIELDS : carry.dets;
-  const int rows_c = link_rows(counts + 3 * i, k), rows_p = link_rows(i ? counts + 3 * i - 3 : carry.counts, k);
+  const int* __restrict__ lab_p = fp.labels;
+  const int* __restrict__ lab_c = fc.labels;
+  const int rows_p = fp.rows, rows_c = fc.rows;
+  const size_t op = fp.at, oc = fc.at;
   for (int j = t; j < k * k; j += 256) hist[j] = 0;
   for (int j = t; j < k; j += 256) {
-    root_p[j] = j < rows_p ? (int)dets_p[(size_t)j * UDET_DET_FIELDS] : -1;  // a root >= 2^31 matches no label
-    root_c[j] = j < rows_c ? (int)dets_c[(size_t)j * UDET_DET_FIELDS] : -1;
+    root_p[j] = j < rows_p ? (int)fp.dets[(size_t)j * UDET_DET_FIELDS] : -1;  // a root >= 2^31 matches no label
+    root_c[j] = j < rows_c ? (int)fc.dets[(size_t)j * UDET_DET_FIELDS] : -1;
   }
   __syncthreads();
   for (long long base = (long long)blockIdx.x * 256; base < HW; base += (long long)gridDim.x * 256) {  // block-uniform bounds
@@ -116,7 +117,25 @@ __global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict
   }
   __syncthreads();
   for (int j = t; j < k * k; j += 256)
-    if (hist[j]) atomicAdd(inter + (size_t)i * k * k + j, (unsigned long long)hist[j]);
+    if (hist[j]) atomicAdd(out + j, (unsigned long long)hist[j]);
+}
+
+__global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict__ labels, const long long* __restrict__ offsets,
+                                                           const int* __restrict__ hw, size_t total_pixels,
+                                                           const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
+                                                           LinkCarry carry, const int* __restrict__ linked, const int* __restrict__ lookup,
+                                                           unsigned long long* __restrict__ inter) {
+  extern __shared__ int link_lds[];
+  const int i = blockIdx.y;
+  if (!linked[i]) return;  // block-uniform; a linked frame 0 has a carried frame of its size
+  const int W = hw[2 * i + 1];
+  const long long HW = (long long)hw[2 * i] * W;  // the predecessor's too
+  const long long* __restrict__ dets_c = dets + (size_t)i * k * UDET_DET_FIELDS;
+  const LinkSide fc = {labels + offsets[i], dets_c, link_rows(counts + 3 * i, k), (size_t)offsets[i]};
+  const LinkSide fp = i ? LinkSide{labels + offsets[i - 1], dets_c - (size_t)k * UDET_DET_FIELDS, link_rows(counts + 3 * i - 3, k),
+                                   (size_t)offsets[i - 1]}
+                        : LinkSide{carry.labels, carry.dets, link_rows(carry.counts, k), total_pixels};
+  link_overlap_pass(fp, fc, W, HW, k, lookup, inter + (size_t)i * k * k, link_lds);
 }
 
 // (inter, union, entry) of the better of two candidates: the larger inter / union by 64-bit cross-multiplication (inter < 2^31, union <
@@ -126,13 +145,29 @@ __device__ __forceinline__ bool link_better(int i1, unsigned u1, int j1, int i2,
   return p1 > p2 || (p1 == p2 && j1 < j2);
 }
 
+// The best of the 256 threads' candidates, in every thread: shuffles inside a wave, then the four waves' winners through LDS (wi, wu,
+// wj: [4]).  Holds one __syncthreads; the caller's next barrier separates this round's reads of wi / wu / wj from the next round's writes.
+__device__ __forceinline__ void link_block_best(int& bi, unsigned& bu, int& bj, int* wi, unsigned* wu, int* wj) {
+  const int t = threadIdx.x;
+  for (int s = 32; s > 0; s >>= 1) {
+    const int oi = __shfl_xor(bi, s), oj = __shfl_xor(bj, s);
+    const unsigned ou = __shfl_xor(bu, s);
+    if (link_better(oi, ou, oj, bi, bu, bj)) { bi = oi; bu = ou; bj = oj; }
+  }
+  if ((t & 63) == 0) { wi[t >> 6] = bi; wu[t >> 6] = bu; wj[t >> 6] = bj; }
+  __syncthreads();
+  bi = wi[0]; bu = wu[0]; bj = wj[0];
+  for (int w = 1; w < 4; ++w)
+    if (link_better(wi[w], wu[w], wj[w], bi, bu, bj)) { bi = wi[w]; bu = wu[w]; bj = wj[w]; }
+}
+
 __global__ __launch_bounds__(256) void link_match_kernel(const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
                                                          LinkCarry carry, const int* __restrict__ linked,
                                                          const long long* __restrict__ inter, int permille, int* __restrict__ match) {
   extern __shared__ int link_lds[];  // inter of the candidates [k * k] (0: none), their unions [k * k], free_p [k], free_c [k], match [k]
   __shared__ int wi[4], wj[4];
   __shared__ unsigned wu[4];
-  const int i = blockIdx.x, t = threadIdx.x, lane = t & 63;
+  const int i = blockIdx.x, t = threadIdx.x;
   int* __restrict__ sint = link_lds;
   unsigned* __restrict__ suni = (unsigned*)(link_lds + k * k);
   int* __restrict__ free_p = link_lds + 2 * k * k;
@@ -169,16 +204,7 @@ __global__ __launch_bounds__(256) void link_match_kernel(const long long* __rest
       const int a = j / k;
       if (free_p[a] && free_c[j - a * k] && link_better(v, suni[j], j, bi, bu, bj)) { bi = v; bu = suni[j]; bj = j; }
     }
-    for (int s = 32; s > 0; s >>= 1) {
-      const int oi = __shfl_xor(bi, s), oj = __shfl_xor(bj, s);
-      const unsigned ou = __shfl_xor(bu, s);
-      if (link_better(oi, ou, oj, bi, bu, bj)) { bi = oi; bu = ou; bj = oj; }
-    }
-    if (lane == 0) { wi[t >> 6] = bi; wu[t >> 6] = bu; wj[t >> 6] = bj; }
-    __syncthreads();
-    bi = wi[0]; bu = wu[0]; bj = wj[0];
-    for (int w = 1; w < 4; ++w)
-      if (link_better(wi[w], wu[w], wj[w], bi, bu, bj)) { bi = wi[w]; bu = wu[w]; bj = wj[w]; }
+    link_block_best(bi, bu, bj, wi, wu, wj);
     if (bi == 0) break;  // no candidate between free rows is left
     if (t == 0) {
       const int a = bj / k, b = bj - a * k;
@@ -249,6 +275,214 @@ int launch_link_detections_ragged(const int* labels, int n, const long long* off
                      k, carry, linked, lookup, (unsigned long long*)inter);
   hipLaunchKernelGGL(link_match_kernel, dim3(n), dim3(256), lds_match, s, dets, counts, k, carry, linked, inter, min_iou_permille, match);
   hipLaunchKernelGGL(link_ids_kernel, dim3(n), dim3(64), 0, s, n, counts, k, carry, linked, match, ids, seq_tracks, next_id);
+  UDET_HIP(hipGetLastError());
+  return UDET_OK;
+}
+
+// ---- udet_link_detections_gap_ragged --------------------------------------------------------------------------------
+// A row without a predecessor in the frame before it may continue a track that ended up to max_gap frames earlier.  Stage 1 is the three
+// launches above, unchanged (the carried frame is the history's last one); then
+//   gap_init_kernel     zeroes gap_inter and enters the rows of the older history frames in the lookup
+//   gap_overlap_kernel  link_overlap_pass for (frame c, distance d) with d on the grid's z axis: frame c against frame c - d
+//   gap_walk_kernel     one workgroup per sequence (that of its first frame in the call; the others leave at once) walks the frames in
+//                       order with the open flags, ids and areas of the last max_gap + 1 frames in a ring in LDS: stage-1 rows inherit,
+//                       then at most `orphans` rounds of a block arg-max over the thresholded gap candidates between free orphans and
+//                       open rows, then the fresh ids by a ballot prefix
+// Six launches whatever n, the sequences, the components and max_gap.  Frame c - d with c - d < 0 is history frame m + c - d; the
+// history's ranks lie behind the batch's in the lookup, newest first (frame j at total_pixels + (m - 1 - j) h w), so that the carried
+// frame is where the stage-1 kernels look for it.
+#define GAP_RING (UDET_TRACK_MAX_GAP + 2)  // frames c - max_gap - 1 .. c
+
+struct LinkHistory {
+  const int* labels;        // [m][h * w], or nullptr: no history
+  const long long* dets;    // [m][k][UDET_DET_FIELDS]
+  const long long* counts;  // [m][3]
+  const int* ids;           // [m][k]
+  int* open;                // [m][k], in / out
+  const int* next_id;       // [1]
+  int m, h, w;
+};
+
+// Whether frame c - d belongs to frame c's sequence: the frames c - d + 1 .. c of the call are linked, and below frame 0 (reached only
+// through a linked frame 0, so the history has its size) the history's m frames follow.
+__device__ __forceinline__ bool gap_reaches(const int* __restrict__ linked, int c, int d, int m) {
+  for (int j = 0; j < d && c - j >= 0; ++j)
+    if (!linked[c - j]) return false;
+  return c - d >= -m;
+}
+
+__device__ __forceinline__ int gap_slot(int f) { return (f + GAP_RING) % GAP_RING; }  // f >= -GAP_RING
+
+__global__ __launch_bounds__(256) void gap_init_kernel(int n, int k, int max_gap, size_t total_pixels, LinkHistory hist,
+                                                       unsigned long long* __restrict__ gap_inter, int* __restrict__ lookup) {
+  const size_t stride = (size_t)gridDim.x * 256, g = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t cells = (size_t)n * max_gap * k * k, frame = (size_t)hist.h * hist.w;
+  for (size_t j = g; j < cells; j += stride) gap_inter[j] = 0;
+  for (size_t j = g; j + k < (size_t)hist.m * k; j += stride) {  // the frames 0 .. m - 2: link_init_kernel entered the carried one
+    const int f = (int)(j / k), r = (int)(j - (size_t)f * k);
+    link_enter_roots(hist.dets + (size_t)f * k * UDET_DET_FIELDS, link_rows(hist.counts + 3 * f, k), (long long)frame,
+                     lookup + total_pixels + (size_t)(hist.m - 1 - f) * frame, r);
+  }
+}
+
+__global__ __launch_bounds__(256) void gap_overlap_kernel(const int* __restrict__ labels, const long long* __restrict__ offsets,
+                                                          const int* __restrict__ hw, size_t total_pixels,
+                                                          const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
+                                                          int max_gap, LinkHistory hist, const int* __restrict__ linked,
+                                                          const int* __restrict__ lookup, unsigned long long* __restrict__ gap_inter) {
+  extern __shared__ int link_lds[];
+  const int c = blockIdx.y, d = blockIdx.z + 2, f = c - d;
+  if (!gap_reaches(linked, c, d, hist.m)) return;  // block-uniform
+  const int W = hw[2 * c + 1];
+  const long long HW = (long long)hw[2 * c] * W;  // frame f's too
+  const LinkSide fc = {labels + offsets[c], dets + (size_t)c * k * UDET_DET_FIELDS, link_rows(counts + 3 * c, k), (size_t)offsets[c]};
+  const int j = hist.m + f;  // f < 0: the history's frame j, 0 <= j < m
+  const LinkSide fp = f >= 0 ? LinkSide{labels + offsets[f], dets + (size_t)f * k * UDET_DET_FIELDS, link_rows(counts + 3 * f, k),
+                                        (size_t)offsets[f]}
+                             : LinkSide{hist.labels + (size_t)j * HW, hist.dets + (size_t)j * k * UDET_DET_FIELDS,
+                                        link_rows(hist.counts + 3 * j, k), total_pixels + (size_t)(hist.m - 1 - j) * HW};
+  link_overlap_pass(fp, fc, W, HW, k, lookup, gap_inter + ((size_t)c * max_gap + (d - 2)) * k * k, link_lds);
+}
+
+// A row of frame f (f < 0: of the history) has found its successor.
+__device__ __forceinline__ void gap_close(int f, int a, int k, LinkHistory hist, int* __restrict__ open) {
+  if (f >= 0) open[(size_t)f * k + a] = 0;
+  else hist.open[(size_t)(hist.m + f) * k + a] = 0;
+}
+
+__global__ __launch_bounds__(256) void gap_walk_kernel(int n, const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
+                                                       int max_gap, LinkHistory hist, const int* __restrict__ linked,
+                                                       const int* __restrict__ match, const long long* __restrict__ gap_inter, int permille,
+                                                       int* __restrict__ ids, int* __restrict__ back, int* __restrict__ prev,
+                                                       int* __restrict__ open, int* __restrict__ seq_tracks, int* __restrict__ next_id_out) {
+  __shared__ int sopen[GAP_RING][LINK_K], sid[GAP_RING][LINK_K];  // per frame of the ring and row: still open, its track id
+  __shared__ long long sarea[GAP_RING][LINK_K];
+  __shared__ int sorph[LINK_K], sback[LINK_K], sprev[LINK_K];     // per row of the frame: a free orphan, the bridge it took (0: none)
+  __shared__ int wi[4], wj[4];
+  __shared__ unsigned wu[4];
+  const int s = blockIdx.x, t = threadIdx.x, b = t & 63;
+  if (s > 0 && linked[s]) return;  // block-uniform: only the workgroup of a sequence's first frame walks it
+  // Every wave does the per-row work on lane = row and so holds the same `next`; wave 0 (t = b) writes.
+  int c = s, next, avail;  // avail: the frames of the sequence before frame c, the history's included
+  if (linked[s]) {         // frame 0 continues the history
+    for (int j = 0; j < hist.m; ++j) {
+      const int rows = link_rows(hist.counts + 3 * j, k), sl = gap_slot(j - hist.m);
+      if (t < k) {
+        sopen[sl][t] = t < rows && hist.open[(size_t)j * k + t] != 0;
+        sid[sl][t] = hist.ids[(size_t)j * k + t];
+        sarea[sl][t] = t < rows ? hist.dets[((size_t)j * k + t) * UDET_DET_FIELDS + 1] : 0;
+      }
+    }
+    next = hist.next_id[0];
+    avail = hist.m;
+  } else {
+    const int rows = link_rows(counts + 3 * s, k), sl = gap_slot(s);
+    if (t < k) {
+      const int id = t < rows ? t : -1;
+      sopen[sl][t] = t < rows;
+      sid[sl][t] = id;
+      sarea[sl][t] = t < rows ? dets[((size_t)s * k + t) * UDET_DET_FIELDS + 1] : 0;
+      ids[(size_t)s * k + t] = id; back[(size_t)s * k + t] = 0; prev[(size_t)s * k + t] = -1; open[(size_t)s * k + t] = t < rows;
+    }
+    if (t == 0) seq_tracks[s] = 0;
+    next = rows;
+    avail = 1;
+    ++c;
+  }
+  __syncthreads();
+  for (; c < n && linked[c]; ++c, ++avail) {  // block-uniform
+    const int rows = link_rows(counts + 3 * c, k), sc = gap_slot(c), sp = gap_slot(c - 1);
+    int m = b < rows ? match[(size_t)c * k + b] : -1;
+    if (m < 0 || m >= k) m = -1;
+    const bool orphan = b < rows && m < 0;
+    const int orphans = __popcll(__ballot(orphan));
+    int id = m >= 0 ? sid[sp][m] : -1, bk = m >= 0 ? 1 : 0;
+    if (t < k) {
+      sopen[sc][t] = t < rows;
+      sarea[sc][t] = t < rows ? dets[((size_t)c * k + t) * UDET_DET_FIELDS + 1] : 0;
+      sorph[t] = orphan; sback[t] = 0; sprev[t] = -1;
+      open[(size_t)c * k + t] = t < rows;
+      if (m >= 0) { sopen[sp][m] = 0; gap_close(c - 1, m, k, hist, open); }  // stage 1 comes first: a bridge never undoes it
+    }
+    __syncthreads();
+    const int dmax = avail < max_gap + 1 ? avail : max_gap + 1;
+    for (int round = 0; round < orphans && dmax >= 2; ++round) {  // block-uniform: every thread sees the same winner
+      int bi = 0, bj = LINK_NONE;
+      unsigned bu = 1;
+      for (int d = 2; d <= dmax; ++d) {
+        const int sa = gap_slot(c - d);
+        const long long* __restrict__ g = gap_inter + ((size_t)c * max_gap + (d - 2)) * k * k;
+        for (int j = t; j < k * k; j += 256) {
+          const int a = j / k, bb = j - a * k;
+          if (!sorph[bb] || !sopen[sa][a]) continue;
+          const long long v = g[j];
+          if (v <= 0 || v > 0x7fffffffLL) continue;
+          const long long u = sarea[sa][a] + sarea[sc][bb] - v;  // area_a + area_b - gap_inter
+          const int key = (d - 2) * k * k + j;                   // ties: the smaller d, then the smaller a, then the smaller b
+          if (u > 0 && u <= 0xffffffffLL && 1000 * v >= (long long)permille * u && link_better((int)v, (unsigned)u, key, bi, bu, bj)) {
+            bi = (int)v; bu = (unsigned)u; bj = key;
+          }
+        }
+      }
+      link_block_best(bi, bu, bj, wi, wu, wj);
+      if (bi == 0) break;  // no candidate between a free orphan and an open row is left
+      if (t == 0) {
+        const int d = bj / (k * k) + 2, j = bj - (d - 2) * k * k, a = j / k, bb = j - a * k;
+        sorph[bb] = 0; sback[bb] = d; sprev[bb] = a;
+        sopen[gap_slot(c - d)][a] = 0;
+        gap_close(c - d, a, k, hist, open);
+      }
+      __syncthreads();
+    }
+    if (orphan && sback[b]) { bk = sback[b]; m = sprev[b]; id = sid[gap_slot(c - bk)][m]; }
+    const bool fresh = orphan && bk == 0;
+    const unsigned long long mask = __ballot(fresh);
+    if (fresh) id = next + __popcll(mask & ((1ull << b) - 1ull));
+    next += __popcll(mask);
+    if (t < k) {
+      ids[(size_t)c * k + t] = id; back[(size_t)c * k + t] = bk; prev[(size_t)c * k + t] = m;
+      sid[sc][t] = id;
+    }
+    if (t == 0) seq_tracks[c] = 0;
+    __syncthreads();
+  }
+  if (t == 0) {  // c - 1 >= s: the sequence's last frame within the call (the same thread wrote its 0 above)
+    seq_tracks[c - 1] = next;
+    if (c == n) next_id_out[0] = next;
+  }
+}
+
+size_t link_detections_gap_workspace_bytes(size_t total_pixels, int m, int hist_h, int hist_w) {
+  return (total_pixels + (size_t)m * hist_h * hist_w) * sizeof(int);
+}
+
+int launch_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                      size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                      int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                      const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                      int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                      int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
+                                      hipStream_t s) {
+  const long nb = ((long)max_h * max_w + 256 * LINK_PPT - 1) / (256 * LINK_PPT);
+  if (nb > 0x7fffffffL) { set_error("link_detections_gap_ragged: frame too large"); return UDET_ERR_SHAPE; }
+  const LinkHistory hist = {hist_labels, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id, m, hist_h, hist_w};
+  const size_t last = m ? (size_t)(m - 1) : 0, frame = (size_t)hist_h * hist_w;  // stage 1 is linked against the history's last frame
+  const LinkCarry carry = {m ? hist_labels + last * frame : nullptr, m ? hist_dets + last * k * UDET_DET_FIELDS : nullptr,
+                           m ? hist_counts + 3 * last : nullptr, m ? hist_ids + last * k : nullptr, hist_next_id, hist_h, hist_w};
+  int* lookup = (int*)workspace;
+  const size_t nz = ((size_t)n * k * k + 255) / 256, ngz = nz * max_gap;
+  const size_t lds_overlap = ((size_t)k * k + 2 * k) * sizeof(int), lds_match = (2 * (size_t)k * k + 3 * k) * sizeof(int);
+  hipLaunchKernelGGL(link_init_kernel, dim3((unsigned)(nz > 65536 ? 65536 : nz)), dim3(256), 0, s, n, offsets, hw, total_pixels, dets,
+                     counts, k, link, carry, (unsigned long long*)inter, linked, lookup);
+  hipLaunchKernelGGL(gap_init_kernel, dim3((unsigned)(ngz > 65536 ? 65536 : ngz)), dim3(256), 0, s, n, k, max_gap, total_pixels, hist,
+                     (unsigned long long*)gap_inter, lookup);
+  hipLaunchKernelGGL(link_overlap_kernel, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts,
+                     k, carry, linked, lookup, (unsigned long long*)inter);
+  hipLaunchKernelGGL(gap_overlap_kernel, dim3((unsigned)nb, n, max_gap), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets,
+                     counts, k, max_gap, hist, linked, lookup, (unsigned long long*)gap_inter);
+  hipLaunchKernelGGL(link_match_kernel, dim3(n), dim3(256), lds_match, s, dets, counts, k, carry, linked, inter, min_iou_permille, match);
+  hipLaunchKernelGGL(gap_walk_kernel, dim3(n), dim3(256), 0, s, n, dets, counts, k, max_gap, hist, linked, match, gap_inter,
+                     min_iou_permille, ids, back, prev, open, seq_tracks, next_id);
   UDET_HIP(hipGetLastError());
   return UDET_OK;
 }
