@@ -202,9 +202,9 @@ def test_chain_by_layout_equals_chain_by_raw_tables(gpu, monkeypatch):
     layout along and once passing raw offsets / hw to every call: the same bytes everywhere, the guards untouched, and in the first form
     one upload of the layout's tables for the whole chain."""
     from test_crf_native import COMPAT, scene
-    from unsupervised_detection_amd import native_results
+    from unsupervised_detection_amd import native_restore
     from unsupervised_detection_amd.native_results import RestoredMasks, restore_masks, select_components
-    monkeypatch.setattr(native_results, "_restore_tables", {})  # the counts below start from a cold restore cache
+    monkeypatch.setattr(native_restore, "_restore_tables", {})  # the counts below start from a cold restore cache
     from unsupervised_detection_amd.post_processing import dense_crf_ragged, unary_from_restored
     masks = np.stack([scene(12, 24, 500 + k)[1] for k in range(3)])
     masks[1] = 0.25  # constant: restores to zeros, amax = 0

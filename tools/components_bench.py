@@ -73,7 +73,9 @@ def main():
         ap.add_argument("--" + name, type=int, default=default)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    from unsupervised_detection_amd.native_results import GtBatch, restore_masks, select_components
+    from unsupervised_detection_amd.native_components import select_components
+    from unsupervised_detection_amd.native_restore import restore_masks
+    from unsupervised_detection_amd.native_results import GtBatch
     rng = np.random.default_rng(0)
     sizes = [(a.h, a.w)] * a.n
     gtm = np.zeros((a.n, a.h, a.w), np.uint8)

@@ -64,7 +64,9 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from components_bench import soft_masks
-    from unsupervised_detection_amd.native_results import component_boxes, restore_masks, select_components
+    from unsupervised_detection_amd.native_components import select_components
+    from unsupervised_detection_amd.native_detections import component_boxes
+    from unsupervised_detection_amd.native_restore import restore_masks
     rng = np.random.default_rng(0)
     sizes = [(a.h, a.w)] * a.n
     stat = lambda v: {"median_ms": float(np.median(v)), "min_ms": float(min(v)), "max_ms": float(max(v))}

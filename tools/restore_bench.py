@@ -25,7 +25,7 @@ def main():
     ap.add_argument("--crop", type=float, default=0.9)
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    from unsupervised_detection_amd.native_results import restore_box, restore_masks
+    from unsupervised_detection_amd.native_restore import restore_box, restore_masks
     from unsupervised_detection_amd.post_processing import _imresize_window, _stream, check, lib
     rng = np.random.default_rng(0)
     masks = torch.from_numpy(rng.random((a.n, a.mh, a.mw), dtype=np.float32)).cuda()

@@ -114,7 +114,9 @@ def main():
     ap.add_argument("--max_gap", type=int, nargs="*", default=[], help="also measure the link with gap bridging for these G (1..8)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
-    from unsupervised_detection_amd.native_results import component_boxes, link_detections, min_iou_permille, select_components
+    from unsupervised_detection_amd.native_components import select_components
+    from unsupervised_detection_amd.native_detections import component_boxes
+    from unsupervised_detection_amd.native_tracks import link_detections, min_iou_permille
     from unsupervised_detection_amd.ragged import PackedLayout
     frames = moving_blobs(a.n, a.h, a.w, a.blobs, np.random.default_rng(0), blank=bool(a.max_gap))
     hw = [(a.h, a.w)] * a.n

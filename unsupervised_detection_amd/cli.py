@@ -206,7 +206,7 @@ def _detections(flags):
     """--detections and its parameters as restore_results_dir takes them: None without --detections.  A bad value is a SystemExit."""
     if not getattr(flags, "detections", False):
         return None
-    from .native_results import detection_params
+    from .native_detections import detection_params
     try:
         return detection_params({"min_area": flags.det_min_area, "max_detections": flags.det_max})
     except ValueError as e:
@@ -223,7 +223,7 @@ def _tracks(flags):
         return None
     if not getattr(flags, "detections", False):
         raise SystemExit("--tracks links the detections of consecutive frames: it needs --detections")
-    from .native_results import track_params
+    from .native_tracks import track_params
     try:
         return track_params({"min_iou": flags.track_min_iou, "max_gap": gap})
     except ValueError as e:
