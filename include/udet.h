@@ -733,6 +733,63 @@ int udet_plan_lane_queues(udet_plan* plan, void* stream, int* queue);
  * a deployment that cannot tolerate that heuristic pins. */
 int udet_plan_pin_lanes(udet_plan* plan, void* stream, void* const* side_streams, int n);
 
+/* Per-track instance maps (csrc/instances.hip): after the link, every pixel of every frame learns which track it belongs
+ * to.  labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts and k are what udet_link_detections_ragged takes; ids: device
+ * int32 [n][k], as either link call wrote them; gt: optional (NULL: none) device uint8 packed like labels, the buffer
+ * udet_select_components_ragged takes, foreground where != 0.  map: device uint8 packed like labels; row_gt: device int64 [n][k];
+ * frame_stats: device int64 [n][3].  With rows_i = counts[i][2] clamped to 0..k, for pixel p of sample i and L = labels[offsets[i] + p]:
+ *   L outside 1..H_i*W_i                                       map = 0 (outside the range is background, as for the other calls);
+ *   else, root = L - 1: some row r < rows_i has dets[i][r][0] == root and ids[i][r] >= 0
+ *                                                              map = 1 + (ids[i][r] mod UDET_INSTANCE_WRAP), a value in 1..252;
+ *   else                                                       map = UDET_INSTANCE_UNASSIGNED: foreground of a component that has no row
+ *                                                              (below min_area, past k) or whose row has no id.
+ * row_gt[i][r] is the number of pixels of row r's component with gt != 0 (0 for r >= rows_i; every entry is 0 when gt is NULL);
+ * frame_stats[i] = {pixels with map in 1..252, pixels with map = 255, pixels with gt != 0} (the last is 0 without gt).  Bytes of map
+ * between the samples are not written.  The wrap is 252 and not 254 because 252 is a multiple of the twelve colours of the default
+ * track palette: palette[(map - 1) mod 12] == palette[id mod 12] for every id, so a filled instance and the rectangle
+ * udet_draw_track_boxes_ragged paints for it share a colour; the values 253 and 254 stay unused.
+ * Two launches whatever n, k, the components and the sequences are, no host round trip, no workgroup waits for another, integer atomics
+ * only: the outputs are exact, identical from run to run and for a sample alone or inside a batch.  The first launch zeroes row_gt and
+ * frame_stats and enters every row's rank at its root in the workspace (the lookup of the link: one int32 per pixel, never zeroed, a
+ * lookup counts only when the row it names holds that root); the second takes one pixel per lane, 64 consecutive pixels of one sample
+ * per wave: the pixels of a row under gt are counted by one LDS atomic per horizontal run of a wave, k partials per workgroup, then one
+ * 64-bit integer atomic per non-zero partial; the map is written as aligned 32-bit words of four pixels (the pixels of a sample are
+ * contiguous, so a word may span a row end), the bytes of a sample's head and tail that share a word with its neighbours one by one.
+ * workspace: udet_track_instance_maps_workspace_bytes(total_pixels, n, k) bytes (4 per pixel), 4-byte aligned; 0 for bad arguments.
+ * UDET_ERR_ARG, nothing enqueued: a NULL labels, offsets, hw, dets, counts, ids, map, row_gt or frame_stats, n outside 1..65535, k
+ * outside 1..UDET_DET_MAX_K, max_h or max_w < 1, total_pixels < 1, a short or misaligned workspace, labels / ids not 4-byte or dets /
+ * counts / row_gt / frame_stats not 8-byte aligned.  Every index a kernel forms is bounded, whatever labels, dets, counts, ids and the
+ * workspace hold; the tables are device memory: the host caller validates them (native_instances.instance_maps). */
+#define UDET_INSTANCE_WRAP 252
+#define UDET_INSTANCE_UNASSIGNED 255
+size_t udet_track_instance_maps_workspace_bytes(size_t total_pixels, int n, int k);
+int udet_track_instance_maps_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                    size_t total_pixels, const long long* dets, const long long* counts, int k, const int* ids,
+                                    const unsigned char* gt, unsigned char* map, long long* row_gt, long long* frame_stats,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* The instance map drawn on the untouched frames, every instance in the colour of its track: udet_overlay_native_ragged with `map` in
+ * the place of `mask` and a colour per value.  image_rgb, out_rgb, offsets, hw, max_h, max_w, total_pixels, alpha, beta and edge are what
+ * that call takes; palette: device uint32 [palette_size], 0xRRGGBB, palette_size in 1..UDET_TRACK_MAX_PALETTE; other_rgb: the colour of
+ * the value 255.  The colour of a pixel with value v is none for v = 0, palette[(v - 1) mod palette_size] for v in 1..252 and other_rgb
+ * for 253..255.  The blend is that call's, unchanged: t = rint(fl32(fl32(img_c) * alpha) + fl32(fl32(m_c) * beta)) with m_c the pixel's
+ * own colour channel, or 0 on background -- two float32 products and one sum, each rounded on its own (no FMA), rint to even, saturated
+ * to 0..255.  edge >= 1: a pixel with v != 0 is a contour pixel when some position (y + dy, x + dx), |dy|, |dx| <= edge, INSIDE the frame
+ * holds a value different from v (positions outside the frame never count) -- (v != 0) & ((minimum_filter(v, 2 edge + 1,
+ * mode="nearest") != v) | (maximum_filter(v, 2 edge + 1, mode="nearest") != v)); a contour pixel is written in its own colour,
+ * unblended.  So two touching instances are separated by a line of each one's colour, and an object cut by the frame border gets no
+ * line along the border.  edge = 0: no contour, no neighbour is read.  Bytes of out_rgb between the samples are not written; out_rgb
+ * must not overlap the inputs.
+ * One launch, no workspace, no atomics: the grid is the 32 x 64 tiles of (max_h, max_w) times n, workgroups beyond a smaller sample's
+ * tiles leave at once; the tile's bytes and an edge-wide halo are held in LDS, read with their coordinates clamped into the frame; the
+ * windowed minimum and maximum are separable, rows then columns; the colour bytes go through the aligned three-word groups of
+ * udet_overlay_native_ragged (csrc/rgb_groups.h).  UDET_ERR_ARG, nothing enqueued: everything udet_overlay_native_ragged refuses, a NULL
+ * or misaligned palette, palette_size outside 1..64, other_rgb above 0xffffff.  UDET_ERR_UNSUPPORTED: edge > UDET_OVERLAY_MAX_EDGE.
+ * UDET_ERR_SHAPE: more than 2^23 tiles per sample. */
+int udet_overlay_instances_ragged(const unsigned char* image_rgb, const unsigned char* map, int n, const long long* offsets, const int* hw,
+                                  int max_h, int max_w, size_t total_pixels, float alpha, float beta, const unsigned* palette,
+                                  int palette_size, unsigned other_rgb, int edge, unsigned char* out_rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

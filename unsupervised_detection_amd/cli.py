@@ -15,11 +15,14 @@
                                                       [--overlay_colour 0,255,0] [--overlay_edge_colour 255,255,255]   (test_generator.py:101-106)
                                                       [--detections] [--det_min_area 64] [--det_max 16]     (no reference script)
                                                       [--overlay_boxes] [--overlay_box_thickness 2] [--overlay_box_colour 255,255,0]
+                                                      [--tracks] [--track_min_iou 0.1] [--track_max_gap 0]
+                                                      [--instances] [--overlay_instances]
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
                                                       [--sxy 25] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_batch 16] [--flow_batch 8]
                                                       [--score_batch 0]
                                                       [--benchmark --dataset ... --root_dir ... [--native_sxy 60] [--component best_gt]
-                                                       [--overlay ...] [--detections ...] [--overlay_boxes ...]]
+                                                       [--overlay ...] [--detections ...] [--overlay_boxes ...] [--tracks ...]
+                                                       [--instances] [--overlay_instances]]
                                                                                                             (post_processing.py)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
@@ -72,7 +75,14 @@ shares the largest IoU, at least --track_min_iou (0.1) -- and numbers the tracks
 (native_results.link_detections, visualize.draw_track_boxes).  --track_max_gap G (needs --tracks; 0..8, default 0: off) lets a box
 without a predecessor in the frame before it continue a track whose component was missing for up to G frames, by the same IoU rule
 against that track's last-seen component: the object keeps its id and its colour, the records gain back, the tracks span / gaps and
-the sequences bridged.  Like the
+the sequences bridged.  --instances (needs --tracks) hands the tracks to the pixels: <out>/instances/<sequence>/<frame>.png is an indexed
+PNG at the frame's own size in which a pixel's value names its track (0 background, 1 + id mod 252 a tracked component in its track's
+colour, 255 foreground without a track), the tracks of <out>/tracks/<sequence>.json gain gt_j_mean -- the mean J of that one track
+against the annotation over all frames of its sequence -- and the sequences best_track, and native_eval.json reports unassigned_mean,
+best_track_j and best_track_J (native_results.instance_maps).  --overlay_instances (needs --overlay and --instances) draws the
+instance map on the overlays in the place of the single mask: every tracked component in its track's colour, also those --component
+removed from the exported binary mask, touching instances separated by a line of each one's colour (visualize.overlay_instances).
+Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
 runs)."""
@@ -176,6 +186,11 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--track_min_iou", type=float, default=0.1, help="the smallest mask IoU that links two boxes")
     ap.add_argument("--track_max_gap", type=int, default=0,
                     help="with --tracks: a box may continue a track whose component was missing for up to this many frames (0..8; 0: none)")
+    ap.add_argument("--instances", action="store_true",
+                    help="with --tracks: write every frame's instance map, <out>/instances/<sequence>/<frame>.png, and score every track")
+    ap.add_argument("--overlay_instances", action="store_true",
+                    help="with --overlay and --instances: draw every tracked component in its track's colour on the overlays, in the place of "
+                         "the single mask -- the components --component removed from the exported binary mask too")
 
 
 def _overlay(flags):
@@ -228,6 +243,20 @@ def _tracks(flags):
         return track_params({"min_iou": flags.track_min_iou, "max_gap": gap})
     except ValueError as e:
         raise SystemExit("--tracks: {} (--track_min_iou / --track_max_gap)".format(e))
+
+
+def _instances(flags):
+    """--instances and --overlay_instances as restore_results_dir takes them: None without --instances.  --instances without --tracks, or
+    --overlay_instances without --overlay and --instances, is a SystemExit."""
+    drawn = getattr(flags, "overlay_instances", False)
+    if drawn and not (getattr(flags, "overlay", False) and getattr(flags, "instances", False)):
+        raise SystemExit("--overlay_instances draws the instance maps on the overlays: it needs --overlay and --instances")
+    if not getattr(flags, "instances", False):
+        return None
+    if not getattr(flags, "tracks", False):
+        raise SystemExit("--instances paints the tracks into per-frame instance maps: it needs --tracks")
+    from .native_instances import instance_params
+    return instance_params({"overlay": bool(drawn)})
 
 
 def check_frames_component(flags):
@@ -283,6 +312,7 @@ def parse_restore_results_args(argv):
     _overlay(flags)
     _detections(flags)
     _tracks(flags)
+    _instances(flags)
     return flags
 
 
@@ -324,6 +354,7 @@ def parse_post_process_args(argv):
         _overlay(flags)
         _detections(flags)
         _tracks(flags)
+        _instances(flags)
     return flags
 
 
@@ -374,6 +405,8 @@ def post_process(a):
             more.update(detections=detections, connectivity=a.connectivity)
         if _tracks(a) is not None:
             more.update(tracks=_tracks(a))
+        if _instances(a) is not None:
+            more.update(instances=_instances(a))
         report["benchmark"] = pp.run_crf_original_resolution(resized, frame_lists_from_reader(a), a.native_sxy, a.srgb, a.scomp, a.gauss_k,
                                                              out_path=original, component=_component(a), gt_rule=a.dataset, **more)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -409,6 +442,7 @@ def check_native_flags(flags):
         _overlay(flags)
         _detections(flags)
         _tracks(flags)
+        _instances(flags)
 
 
 def main(argv=None):
@@ -424,7 +458,7 @@ def main(argv=None):
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
                             batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
-                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a))
+                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a), instances=_instances(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -453,7 +487,7 @@ def main(argv=None):
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
                                 connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags),
-                                detections=_detections(flags), tracks=_tracks(flags))
+                                detections=_detections(flags), tracks=_tracks(flags), instances=_instances(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

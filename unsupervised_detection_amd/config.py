@@ -70,6 +70,11 @@ _DEFS = [
     ("track_min_iou", float, 0.1),
     # ... and a box may continue a track whose component was missing for up to track_max_gap frames (0..8, 0: off)
     ("track_max_gap", int, 0),
+    # not reference flags: with --tracks, --instances writes every frame's instance map (an indexed PNG, a pixel's value names its track) into
+    # D/native/instances/<sequence>/ and scores every track against the annotation; --overlay_instances (with --overlay) draws the maps, every
+    # track in its colour, in the place of the single mask (native_results.instance_maps, visualize.overlay_instances)
+    ("instances", bool, False),
+    ("overlay_instances", bool, False),
 ]
 
 

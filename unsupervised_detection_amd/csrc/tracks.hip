@@ -20,6 +20,7 @@
 // kernels) adds the bridge across frames in which a component is missing: six launches, the same properties.
 #include "common.h"
 #include "elementwise.h"
+#include "track_rows.h"  // link_rows, link_enter_roots: shared with instances.hip
 #include "wave_runs.h"
 
 namespace udet {
@@ -30,12 +31,6 @@ namespace udet {
 
 static_assert(LINK_K <= 64, "one lane per row in link_ids_kernel");
 
-// rows written for a frame, whatever its counts hold: 0..k
-__device__ __forceinline__ int link_rows(const long long* __restrict__ counts3, int k) {
-  const long long r = counts3[2];
-  return r < 0 ? 0 : r > k ? k : (int)r;
-}
-
 // What a frame is linked against: the frame before it in the call, or the carried frame for the call's first one.
 struct LinkCarry {
   const int* labels;        // carry_h x carry_w, or nullptr: no carried frame
@@ -45,13 +40,6 @@ struct LinkCarry {
   const int* next_id;       // [1]
   int h, w;
 };
-
-__device__ __forceinline__ void link_enter_roots(const long long* __restrict__ dets, int rows, long long HW, int* __restrict__ lookup,
-                                                 int r) {
-  if (r >= rows) return;
-  const long long root = dets[(size_t)r * UDET_DET_FIELDS];
-  if (root >= 0 && root < HW) lookup[root] = r;
-}
 
 __global__ __launch_bounds__(256) void link_init_kernel(int n, const long long* __restrict__ offsets, const int* __restrict__ hw,
                                                         size_t total_pixels, const long long* __restrict__ dets,

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "host_checks.h"
+#include "rgb_groups.h"  // native_blend, rgb_group4: shared with instances.hip
 
 namespace udet {
 
@@ -187,11 +188,6 @@ static_assert(ON_LEFT + ON_TW + UDET_OVERLAY_MAX_EDGE <= 128, "a packed row is t
 __device__ __forceinline__ unsigned row_bits4(unsigned long long lo, unsigned long long hi, int pos) {
   return (unsigned)(pos < 64 ? (lo >> pos) | (hi << (64 - pos)) : hi >> (pos - 64)) & 15u;
 }
-// cv2.addWeighted of one byte: v * alpha and the mask's term mb = m * beta are float32 products, their sum a float32 sum (no FMA: the
-// file is compiled with -ffp-contract=off), rounded half to even and saturated (both terms are >= 0)
-__device__ __forceinline__ unsigned native_blend(unsigned v, float alpha, float mb) {
-  return (unsigned)fminf(rintf((float)v * alpha + mb), 255.f);
-}
 __global__ __launch_bounds__(256) void overlay_native_kernel(const unsigned char* __restrict__ image, const unsigned char* __restrict__ mask,
                                                              const long long* __restrict__ offsets, const int* __restrict__ hw, int tiles_x,
                                                              float alpha, float beta, unsigned mask_rgb, int edge, unsigned edge_rgb,
@@ -270,36 +266,10 @@ __global__ __launch_bounds__(256) void overlay_native_kernel(const unsigned char
     const int pos = ON_LEFT - s + 4 * k;
     const unsigned fg = row_bits4(F[ry + edge][0], F[ry + edge][1], pos);
     const unsigned ct = edge > 0 ? fg & ~row_bits4(E[ry][0], E[ry][1], pos) : 0u;
-    if (wide && xf >= 0 && xf + 3 < W) {
-      const long w0 = 3 * ((b + xf) >> 2);  // 32-bit word index of the group's first byte
-      const unsigned* p = reinterpret_cast<const unsigned*>(image) + w0;
-      const unsigned src0 = p[0], src1 = p[1], src2 = p[2];
-      unsigned dst[3] = {0u, 0u, 0u};
-#pragma unroll
-      for (int i = 0; i < 12; ++i) {
-        const int j = i / 3, c = i % 3;
-        const unsigned v = ((i < 4 ? src0 : (i < 8 ? src1 : src2)) >> (8 * (i & 3))) & 255u;
-        const float mb = ((fg >> j) & 1u) ? (c == 0 ? mb0 : (c == 1 ? mb1 : mb2)) : 0.f;
-        const unsigned r = ((ct >> j) & 1u) ? (c == 0 ? e0 : (c == 1 ? e1 : e2)) : native_blend(v, alpha, mb);
-        dst[i >> 2] |= r << (8 * (i & 3));
-      }
-      unsigned* q = reinterpret_cast<unsigned*>(out) + w0;
-      q[0] = dst[0];
-      q[1] = dst[1];
-      q[2] = dst[2];
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int x = xf + j;
-        if (x < 0 || x >= W) continue;
-        const long at = 3 * (b + x);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float mb = ((fg >> j) & 1u) ? (c == 0 ? mb0 : (c == 1 ? mb1 : mb2)) : 0.f;
-          out[at + c] = (unsigned char)(((ct >> j) & 1u) ? (c == 0 ? e0 : (c == 1 ? e1 : e2)) : native_blend(image[at + c], alpha, mb));
-        }
-      }
-    }
+    rgb_group4(image, out, b, xf, W, wide, [&](int j, int c, unsigned v) -> unsigned {
+      const float mb = ((fg >> j) & 1u) ? (c == 0 ? mb0 : (c == 1 ? mb1 : mb2)) : 0.f;
+      return ((ct >> j) & 1u) ? (c == 0 ? e0 : (c == 1 ? e1 : e2)) : native_blend(v, alpha, mb);
+    });
   }
 }
 

@@ -10,9 +10,9 @@ importable from here as well.
   check_crf_tables / load_images_device / crf_refine_restored   the full-resolution dense CRF of run_crf_original_resolution on the
                                                 restored batch: unary from the restored bytes, the frames read at their own size,
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
-  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections [+ tracks]] + J / F +
-                                                <sequence>/<frame>.png, result_<k>.mat, native_eval.json [, detections/<sequence>.json
-                                                [, tracks/<sequence>.json]]
+  restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections [+ tracks
+                                                [+ instances]]] + J / F + <sequence>/<frame>.png, result_<k>.mat, native_eval.json
+                                                [, detections/<sequence>.json [, tracks/<sequence>.json [, instances/<sequence>/<frame>.png]]]
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order; (image, None) for
                                                 a folder of frames without annotations (--dataset FRAMES), which restore_results_dir
                                                 takes in its annotation-free mode; overlay=... draws the final masks on the frames
@@ -21,7 +21,8 @@ importable from here as well.
 The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...}).  Every component as a box with its area, centroid
 and score -- the detections -- is restore_results_dir(detections={...}); linking them across the frames of a sequence
 is restore_results_dir(tracks={...}) (DESIGN.md 7.8), across frames in which a component is missing with tracks={"max_gap": G}
-(DESIGN.md 7.9)."""
+(DESIGN.md 7.9); the tracks as per-frame instance maps, their picture and a track's J against the annotation is
+restore_results_dir(instances={...})."""
 import functools
 import os
 from types import SimpleNamespace
@@ -32,6 +33,8 @@ import torch
 from .native_components import COMPONENT_MODES, COMPONENT_TILE, ComponentSelection, check_component_tables, select_components  # noqa: F401
 from .native_detections import (DET_FIELDS, DET_MAX_K, DETECTION_DEFAULTS, Detections, _host, component_boxes,  # noqa: F401
                                 detection_params, detection_records)
+from .native_instances import (INSTANCE_PALETTE_BYTES, INSTANCE_UNASSIGNED, INSTANCE_WRAP, InstanceMaps, check_instance_arguments,  # noqa: F401
+                               instance_maps, instance_params, track_gt_scores)
 from .native_restore import TAB, RestoredMasks, build_restore_tables, check_restore_tables, restore_box, restore_masks  # noqa: F401
 from .native_tracks import (TRACK_DEFAULTS, TRACK_MAX_GAP, TrackHistory, Tracks, TrackTail, check_link_arguments,  # noqa: F401
                             link_detections, min_iou_permille, summarise_tracks, track_max_gap, track_params, track_records)
@@ -174,12 +177,19 @@ def draw_track_detection_boxes(overlays, detections, tracks, boxes):
     return draw_track_boxes(overlays, detections, tracks, thickness=boxes["thickness"])
 
 
+def draw_instance_overlays(frames, maps, overlay):
+    """visualize.overlay_instances(frames, maps, alpha, beta, edge of `overlay`): the instance maps of a batch on their frames, every
+    track in its colour (visualize.TRACK_PALETTE), one launch."""
+    from .visualize import overlay_instances
+    return overlay_instances(frames, maps, alpha=overlay["alpha"], beta=overlay["beta"], edge=overlay["edge"])
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # The driver: options -> every category through the injected callables -> native_eval.json
 # ---------------------------------------------------------------------------------------------------------------------------
 def _resolve_options(o):
     """The options of restore_results_dir (`o`: its arguments by their names) checked in this order (ValueError) and filled in, in place:
-    batch and bound_th, the dicts through crf_params / detection_params / track_params / visualize.overlay_params; o gains `boxes`
+    batch and bound_th, the dicts through crf_params / detection_params / track_params / visualize.overlay_params / instance_params; o gains `boxes`
     (overlay["boxes"] through visualize.box_params, None: no boxes), `free` (no frame has an annotation) and `rule` (the GtRule)."""
     from .evaluation import BOUND_TH
     o.bound_th = BOUND_TH if o.bound_th is None else o.bound_th
@@ -202,6 +212,12 @@ def _resolve_options(o):
                 raise ValueError('overlay["boxes"] draws the detections: it needs detections')
             o.boxes = box_params(o.overlay["boxes"])
         o.overlay = overlay_params({k: v for k, v in o.overlay.items() if k != "boxes"} if isinstance(o.overlay, dict) else o.overlay)
+    if o.instances is not None:
+        if o.tracks is None:
+            raise ValueError("instances paints the tracks: it needs tracks")
+        o.instances = instance_params(o.instances)
+        if o.instances["overlay"] and o.overlay is None:
+            raise ValueError('instances["overlay"] draws the maps on the overlays: it needs overlay')
     missing = [a is None for entries in o.frame_lists.values() for _, a in entries]
     o.free = bool(missing) and all(missing)  # annotation-free: sizes from the frames, nothing to score against
     if any(missing) and not o.free:
@@ -220,9 +236,9 @@ def _dump_json(content, *path):
 
 def _restore_category(cat, entries, o):
     """One category of restore_results_dir under the resolved options `o`: its batches through the injected callables in the order load
-    gt or sizes, restore, load frames, refine, select, detect, link, score, draw, draw boxes, write.  Writes the category's files and
+    gt or sizes, restore, load frames, refine, select, detect, link, paint, score, draw, draw boxes, write.  Writes the category's files and
     returns its record for the summary: frames, components_mean, foreground_mean; annotated: j and f (per frame); with detections:
-    detections_mean; with tracks: tracks and track_len_mean."""
+    detections_mean; with tracks: tracks and track_len_mean; with instances: unassigned_mean and, annotated, best_track_j."""
     import re
     import scipy.io as sio
     from PIL import Image
@@ -234,9 +250,12 @@ def _restore_category(cat, entries, o):
     os.makedirs(od, exist_ok=True)
     if o.overlay is not None:
         os.makedirs(os.path.join(o.out_dir, "overlay", cat), exist_ok=True)
+    if o.instances is not None:
+        os.makedirs(os.path.join(o.out_dir, "instances", cat), exist_ok=True)
     j, f, nc, fg = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries)), np.zeros(len(entries))
     records = {}  # frame stem -> its detections, in the list's order
     tail, starts = None, []  # tracks: the previous batch's last frame; per frame, whether it starts a sequence
+    row_gts, gt_area, unassigned = [], [], []  # instances, per frame: row_gt of its records, its annotated pixels, the share of value 255
     for s in range(0, len(entries), o.batch):
         rows = entries[s:s + o.batch]
         images = [img for img, _ in rows]
@@ -265,7 +284,7 @@ def _restore_category(cat, entries, o):
             nc[s:s + len(rows)] = _host(pred.info)[:, 0]
         elif o.detections is not None:
             labelled = o.select(pred, mode="label", connectivity=o.connectivity, want_labels=True)
-        det = trk = None
+        det = trk = inst = None
         if o.detections is not None:
             det = o.detect(labelled, score=res, min_area=o.detections["min_area"], max_detections=o.detections["max_detections"])
             recs = detection_records(det, res.amax)
@@ -275,13 +294,21 @@ def _restore_category(cat, entries, o):
                 tail = trk.tail()
                 recs = track_records(recs, trk)
                 starts += [not v for v in trk.host()[3]]
+                if o.instances is not None:
+                    inst = o.paint(labelled, det, trk, gt=None if o.free else gt)
+                    row_gt, stats = inst.host()
+                    row_gts += [[int(v) for v in row_gt[i][:len(r)]] for i, r in enumerate(recs)]
+                    gt_area += [int(v) for v in stats[:, 2]]
+                    unassigned += [int(u) / (int(a) + int(u)) if int(a) + int(u) else 0.0 for a, u in stats[:, :2]]
             records.update(zip(stems, recs))
         if not o.free:
             shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
             for shape in sorted(set(shapes)):
                 idx = [i for i, sh in enumerate(shapes) if sh == shape]
                 j[[s + i for i in idx]], f[[s + i for i in idx]] = o.score(gt.stack(idx), pred.stack(idx), o.bound_th)
-        drawn = o.draw(frames, pred, o.overlay) if o.overlay is not None else None
+        drawn = None
+        if o.overlay is not None:  # every tracked component in its track's colour, or the final mask
+            drawn = o.draw_instances(frames, inst, o.overlay) if inst is not None and o.instances["overlay"] else o.draw(frames, pred, o.overlay)
         if o.boxes is not None:
             drawn = o.draw_boxes(drawn, det, o.boxes) if trk is None else o.draw_track_boxes(drawn, det, trk, o.boxes)
         for i, stem in enumerate(stems):
@@ -293,6 +320,10 @@ def _restore_category(cat, entries, o):
             else:
                 mat["gt_mask"] = _host(gt.sample(i)).astype(np.uint8)
             sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)), mat)
+            if inst is not None:
+                im = Image.fromarray(np.ascontiguousarray(_host(inst.sample(i)), dtype=np.uint8), "P")
+                im.putpalette(INSTANCE_PALETTE_BYTES)
+                im.save(os.path.join(o.out_dir, "instances", cat, stem + ".png"))
             if drawn is not None:
                 Image.fromarray(np.ascontiguousarray(_host(drawn.sample(i)), dtype=np.uint8), "RGB").save(
                     os.path.join(o.out_dir, "overlay", cat, stem + ".png"))
@@ -304,6 +335,18 @@ def _restore_category(cat, entries, o):
         rec["detections_mean"] = float(np.mean([len(r) for r in records.values()])) if records else 0.0
     if o.tracks is not None:
         summary = summarise_tracks(list(records), list(records.values()), starts, gaps=True if "max_gap" in o.tracks else None)
+        if o.instances is not None:
+            rec["unassigned_mean"] = float(np.mean(unassigned)) if unassigned else 0.0
+            for seq in summary:
+                if any(t["id"] >= INSTANCE_WRAP for t in seq["tracks"]):
+                    seq["wrapped"] = True  # two of its tracks share a value of the map
+            if not o.free:
+                scores = track_gt_scores(list(records.values()), row_gts, gt_area, starts)
+                for seq, sc in zip(summary, scores):
+                    for t in seq["tracks"]:
+                        t["gt_j_mean"] = sc["gt_j_mean"][t["id"]]
+                    seq["best_track"] = sc["best_track"]
+                rec["best_track_j"] = float(sum(sc["frames"] * sc["best_j"] for sc in scores) / sum(sc["frames"] for sc in scores)) if scores else 0.0
         _dump_json(summary, o.out_dir, "tracks", cat + ".json")
         lengths = [t["frames"] for seq in summary for t in seq["tracks"]]
         rec["tracks"], rec["track_len_mean"] = len(lengths), float(np.mean(lengths)) if lengths else 0.0
@@ -344,8 +387,13 @@ def _summary(cats, o):
     if o.tracks is not None:
         out["tracks"] = o.tracks
         per_sequence += ["tracks", "track_len_mean"]
+    if o.instances is not None:
+        out["instances"] = o.instances
+        per_sequence += ["unassigned_mean"] + ([] if o.free else ["best_track_j"])
     for c, seq in out["sequences"].items():
         seq.update((k, cats[c][k]) for k in per_sequence)
+    if o.instances is not None and not o.free:
+        out["best_track_J"] = _nanmean([r["best_track_j"] for r in cats.values()])
     return out
 
 
@@ -354,7 +402,8 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                         component=None, connectivity=8, select=select_components, crf=None, load_images=load_images_device,
                         refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays, detections=None,
                         detect=component_boxes, draw_boxes=draw_detection_boxes, tracks=None, link=link_detections,
-                        draw_track_boxes=draw_track_detection_boxes):
+                        draw_track_boxes=draw_track_detection_boxes, instances=None, paint=instance_maps,
+                        draw_instances=draw_instance_overlays):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -403,8 +452,20 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     tracks["max_gap"] (0; 1..8: DESIGN.md 7.9) lets a row continue a track that ended up to max_gap frames earlier: link is then called
     with max_gap= as well and the tail() it carries is the history of the last max_gap + 1 frames; the records gain "back", the tracks
     "span" and "gaps", the sequences "bridged", and the json's "tracks" carries max_gap.  With 0 or without the key nothing changes.
-    restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes are
-    injectable: the host logic runs without a GPU on numpy stand-ins."""
+    instances (None: off; needs tracks): {} or {"overlay": bool}.  After the link every batch goes through paint(labelled, det, tracks,
+    gt=the batch's annotations or None) (instance_maps: two launches per batch) and every frame's map is written to
+    <out_dir>/instances/<category>/<frame stem>.png, an indexed PNG (Pillow mode "P", INSTANCE_PALETTE_BYTES) whose bytes are the map's: 0
+    background, 1 + (track id mod 252) a tracked component, 255 foreground without a track -- the layout multi-object tools read.  The
+    tracks of tracks/<category>.json gain "gt_j_mean" and its sequences "best_track" (track_gt_scores; annotated data only), and a
+    sequence whose ids reached 252 is flagged "wrapped": true; the json gains "instances" with the parameters used, per sequence
+    "unassigned_mean" (the mean over its frames of the share of foreground pixels with value 255) and, on annotated data, "best_track_j"
+    (the frames-weighted mean of its sequences' best gt_j_mean) and at top level "best_track_J", the mean over the categories.  With
+    instances["overlay"] (needs overlay) the overlay picture comes from draw_instances(frames, maps, overlay) in the place of draw: every
+    tracked component in its track's colour (visualize.overlay_instances with the overlay's alpha, beta and edge) -- those the component
+    selection removed from the exported binary mask too; the boxes are still painted on top when asked.  With None nothing of this
+    runs and every file is byte for byte what it is without the argument.
+    restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes / paint /
+    draw_instances are injectable: the host logic runs without a GPU on numpy stand-ins."""
     o = SimpleNamespace(**locals())  # every argument under its own name: the options and the injected callables
     _resolve_options(o)
     cats = {cat: _restore_category(cat, entries, o) for cat, entries in frame_lists.items()}

@@ -263,6 +263,43 @@ def draw_track_boxes(overlays, detections, tracks, thickness=2, palette=TRACK_PA
     return overlays
 
 
+def overlay_instances(images, maps, alpha=0.5, beta=0.4, edge=2, palette=TRACK_PALETTE, other_colour=(128, 128, 128), out=None) -> NativeOverlays:
+    """The instance maps of a ragged batch drawn on their frames at the frames' own size, in one call of udet_overlay_instances_ragged
+    (one launch whatever the batch): overlay_native's blend with a colour per pixel -- value v in 1..252 in palette[(v - 1) mod
+    len(palette)] (so a track's pixels take the colour draw_track_boxes gives its box), 253..255 in other_colour, 0 the frame alone --
+    and, for edge >= 1, a contour in the pixel's own colour, unblended, wherever another value lies within `edge` columns and rows
+    inside the frame: two touching instances are separated by a line of each one's colour.  images: as for overlay_native; maps: a
+    native_results.InstanceMaps (or anything that holds the packed bytes as `map` or `data` with their `layout`).  out: as for
+    overlay_native.  Everything is validated on the host before the device is touched (ValueError)."""
+    p = overlay_params({"alpha": alpha, "beta": beta, "edge": edge})
+    words, other = palette_words(palette), _rgb24(other_colour, "other_colour")
+    frames = images.layout if hasattr(images, "layout") else PackedLayout(images.offsets, images.hw, images.data.numel(), 3, overlap_ok=True)
+    buf = next((b for b in (getattr(maps, k, None) for k in ("map", "data")) if b is not None), None)
+    if buf is None:
+        raise ValueError("maps holds no packed instance map (map or data)")
+    total = int(require_tensor(buf, "maps (packed samples)", torch.uint8, 1, cuda=False).numel())
+    layout = maps.layout if hasattr(maps, "layout") else as_layout(maps.offsets, maps.hw, total)
+    if frames.c != 3 or not frames.same_as(layout, scale=3):
+        raise ValueError("the frames must be rgb and packed like the maps (their sizes, three times their offsets)")
+    as_layout(layout, None, total, max_samples=65535)
+    dev = buf.device
+    require_tensor(buf, "maps (packed samples)", torch.uint8, 1)
+    require_tensor(images.data, "images (rgb, packed like the maps)", torch.uint8, 1, 3 * total, dev)
+    if out is None:
+        out = torch.zeros(3 * total, dtype=torch.uint8, device=dev)
+    else:
+        require_tensor(out, "out", torch.uint8, 1, 3 * total, dev)
+        for t in (images.data, buf):
+            if out.data_ptr() < t.data_ptr() + t.numel() and t.data_ptr() < out.data_ptr() + out.numel():
+                raise ValueError("out must not overlap the frames or the maps")
+    d_pal = torch.tensor(words, dtype=torch.int32, device=dev)
+    d_off, d_hw = layout.device_tables(dev)
+    check(lib.udet_overlay_instances_ragged(images.data.data_ptr(), buf.data_ptr(), layout.n, d_off.data_ptr(), d_hw.data_ptr(), layout.max_h,
+                                            layout.max_w, total, p["alpha"], p["beta"], d_pal.data_ptr(), len(words), other, p["edge"],
+                                            out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return NativeOverlays(out, frames)
+
+
 # ------------------------------------------------------------------------------------------------------- histograms ----
 def bucket_limits() -> np.ndarray:
     """TensorFlow's default histogram bucket limits, as the library builds them: 1551 ascending float64."""
