@@ -790,6 +790,35 @@ int udet_overlay_instances_ragged(const unsigned char* image_rgb, const unsigned
                                   int max_h, int max_w, size_t total_pixels, float alpha, float beta, const unsigned* palette,
                                   int palette_size, unsigned other_rgb, int edge, unsigned char* out_rgb, void* stream);
 
+/* The masks of whole tracks (csrc/follow.hip): a choice of rows per frame -- made on the host once a sequence is known,
+ * native_follow.choose_tracks -- turned back into binary masks on the device.  labels, n, offsets, hw, max_h, max_w, total_pixels, dets,
+ * counts and k are what udet_track_instance_maps_ragged takes; keep: device uint64 [n], bit r of keep[i] = keep row r of frame i; gt:
+ * optional (NULL: none) device uint8 packed like labels, foreground where != 0.  selected: device uint8 packed like labels; stats: device
+ * int64 [n][4].  With rows_i = min(counts[i][2], k) (clamped to 0..k), for pixel p of sample i and L = labels[offsets[i] + p]:
+ *   selected = 1 exactly when L lies in 1..H_i*W_i, L - 1 is the root dets[i][r][0] of a row r < rows_i and bit r of keep[i] is set;
+ *   selected = 0 otherwise (outside the range is background, as for the other calls).
+ * Bits of keep[i] at or above rows_i are ignored.  stats[i] = {kept pixels, dropped foreground pixels, kept pixels with gt != 0, pixels
+ * with gt != 0}: dropped foreground is a label in range that is not kept; the last two are 0 when gt is NULL.  Bytes of selected between
+ * the samples are not written.
+ * Two launches whatever n, k, the components and the sequences are, no host round trip, no workgroup waits for another, integer atomics
+ * only: the outputs are exact, identical from run to run and for a sample alone or inside a batch.  The first launch zeroes stats and
+ * enters every row's rank at its root in the workspace (the lookup of the link: one int32 per pixel, never zeroed, a lookup counts only
+ * when the row it names holds that root); the second takes one pixel per lane, 64 consecutive pixels of one sample per wave, 4096 pixels
+ * per workgroup: the keep word is uniform over a sample, one scalar load and a bit test, not a table lookup per pixel; the four counts
+ * are ballots summed per wave, reduced in LDS, then one 64-bit integer atomic per non-zero partial per workgroup; selected is written as
+ * aligned 32-bit words of four pixels whatever the sample's offset and the buffer's alignment, the bytes of a sample's head and tail
+ * that share a word with its neighbours one by one (csrc/packed_bytes.h, the instance map's store).
+ * workspace: udet_follow_tracks_workspace_bytes(total_pixels, n, k) bytes (4 per pixel), 4-byte aligned; 0 for bad arguments.
+ * UDET_ERR_ARG, nothing enqueued: a NULL labels, offsets, hw, dets, counts, keep, selected or stats, n outside 1..65535, k outside
+ * 1..UDET_DET_MAX_K, max_h or max_w < 1, total_pixels < 1, a short or misaligned workspace, labels not 4-byte or dets / counts / keep /
+ * stats not 8-byte aligned.  Every index a kernel forms is bounded, whatever labels, dets, counts, keep and the workspace hold; the
+ * tables are device memory: the host caller validates them (native_follow.follow_tracks). */
+size_t udet_follow_tracks_workspace_bytes(size_t total_pixels, int n, int k);
+int udet_follow_tracks_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                              long long total_pixels, const long long* dets, const long long* counts, int k,
+                              const unsigned long long* keep, const unsigned char* gt, unsigned char* selected, long long* stats,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,12 +17,13 @@
                                                       [--overlay_boxes] [--overlay_box_thickness 2] [--overlay_box_colour 255,255,0]
                                                       [--tracks] [--track_min_iou 0.1] [--track_max_gap 0]
                                                       [--instances] [--overlay_instances]
+                                                      [--follow none|mass|area|length|best_gt|all] [--track_min_frames 1]
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
                                                       [--sxy 25] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_batch 16] [--flow_batch 8]
                                                       [--score_batch 0]
                                                       [--benchmark --dataset ... --root_dir ... [--native_sxy 60] [--component best_gt]
                                                        [--overlay ...] [--detections ...] [--overlay_boxes ...] [--tracks ...]
-                                                       [--instances] [--overlay_instances]]
+                                                       [--instances] [--overlay_instances] [--follow ...] [--track_min_frames N]]
                                                                                                             (post_processing.py)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
@@ -82,6 +83,14 @@ against the annotation over all frames of its sequence -- and the sequences best
 best_track_j and best_track_J (native_results.instance_maps).  --overlay_instances (needs --overlay and --instances) draws the
 instance map on the overlays in the place of the single mask: every tracked component in its track's colour, also those --component
 removed from the exported binary mask, touching instances separated by a line of each one's colour (visualize.overlay_instances).
+--follow mass|area|length|best_gt|all (needs --tracks; default none; not together with a --component mode, so post_process --benchmark
+takes it with --component none) makes the exported and scored binary mask that of whole tracks, chosen without the annotation once a
+sequence is known: among the tracks with boxes in at least --track_min_frames (1) frames of their sequence, the one with the largest
+summed score (mass), the largest summed area, the most frames (length) or -- with --instances, on annotated data -- the largest mean J
+against the annotation (best_gt), ties to the longer track, then the smaller id; all keeps every such track.  The stage then runs every
+sequence in two passes, a frame in which the followed track has no box exports an empty mask, the J / F table is that of one consistently
+followed object, native_eval.json gains follow and per sequence kept_mean, and the sequences of <out>/tracks/<sequence>.json gain followed
+(native_results.follow_tracks).
 Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
@@ -191,6 +200,10 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--overlay_instances", action="store_true",
                     help="with --overlay and --instances: draw every tracked component in its track's colour on the overlays, in the place of "
                          "the single mask -- the components --component removed from the exported binary mask too")
+    ap.add_argument("--follow", default="none", choices=("none", "mass", "area", "length", "best_gt", "all"),
+                    help="with --tracks: export and score the masks of whole tracks, one per sequence by its summed score (mass), summed "
+                         "area, length or mean J against the annotation (best_gt), or all of them; not together with --component")
+    ap.add_argument("--track_min_frames", type=int, default=1, help="with --follow: only tracks with boxes in at least this many frames")
 
 
 def _overlay(flags):
@@ -259,6 +272,30 @@ def _instances(flags):
     return instance_params({"overlay": bool(drawn)})
 
 
+def _follow(flags):
+    """--follow and --track_min_frames as restore_results_dir takes them: None for "none".  --follow without --tracks, together with a
+    --component mode, best_gt without --instances or on --dataset FRAMES, --track_min_frames without --follow, or a bad value, is a
+    SystemExit."""
+    rule, frames = getattr(flags, "follow", "none"), getattr(flags, "track_min_frames", 1)
+    if rule in (None, "none"):
+        if frames != 1:
+            raise SystemExit("--track_min_frames drops the short tracks from what --follow keeps: it needs --follow")
+        return None
+    if not getattr(flags, "tracks", False):
+        raise SystemExit("--follow exports the masks of whole tracks: it needs --tracks")
+    if _component(flags) is not None:
+        raise SystemExit("--follow and --component are alternative answers to which component is the mask: pass --component none")
+    if rule == "best_gt" and not getattr(flags, "instances", False):
+        raise SystemExit("--follow best_gt scores the tracks against the annotation: it needs --instances")
+    if rule == "best_gt" and getattr(flags, "dataset", None) == "FRAMES":
+        raise SystemExit("--dataset FRAMES has no annotations: pass --follow mass|area|length|all (best_gt needs them)")
+    from .native_follow import follow_params
+    try:
+        return follow_params({"rule": rule, "min_frames": frames})
+    except ValueError as e:
+        raise SystemExit("--follow: {} (--track_min_frames)".format(e))
+
+
 def check_frames_component(flags):
     """A folder of frames has no annotation to pick the best component by."""
     if getattr(flags, "dataset", None) == "FRAMES" and getattr(flags, "component", "none") == "best_gt":
@@ -313,6 +350,7 @@ def parse_restore_results_args(argv):
     _detections(flags)
     _tracks(flags)
     _instances(flags)
+    _follow(flags)
     return flags
 
 
@@ -355,6 +393,7 @@ def parse_post_process_args(argv):
         _detections(flags)
         _tracks(flags)
         _instances(flags)
+        _follow(flags)
     return flags
 
 
@@ -407,6 +446,8 @@ def post_process(a):
             more.update(tracks=_tracks(a))
         if _instances(a) is not None:
             more.update(instances=_instances(a))
+        if _follow(a) is not None:
+            more.update(follow=_follow(a))
         report["benchmark"] = pp.run_crf_original_resolution(resized, frame_lists_from_reader(a), a.native_sxy, a.srgb, a.scomp, a.gauss_k,
                                                              out_path=original, component=_component(a), gt_rule=a.dataset, **more)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -443,6 +484,7 @@ def check_native_flags(flags):
         _detections(flags)
         _tracks(flags)
         _instances(flags)
+        _follow(flags)
 
 
 def main(argv=None):
@@ -458,7 +500,7 @@ def main(argv=None):
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
                             batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
-                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a), instances=_instances(a))
+                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a), instances=_instances(a), follow=_follow(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -487,7 +529,8 @@ def main(argv=None):
             restore_results_dir(flags.test_save_dir, frame_lists_from_reader(flags), os.path.join(flags.test_save_dir, "native"),
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
                                 connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags),
-                                detections=_detections(flags), tracks=_tracks(flags), instances=_instances(flags))
+                                detections=_detections(flags), tracks=_tracks(flags), instances=_instances(flags),
+                                follow=_follow(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

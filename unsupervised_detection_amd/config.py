@@ -75,6 +75,10 @@ _DEFS = [
     # track in its colour, in the place of the single mask (native_results.instance_maps, visualize.overlay_instances)
     ("instances", bool, False),
     ("overlay_instances", bool, False),
+    # not reference flags: with --tracks, --follow mass|area|length|best_gt|all exports and scores the masks of whole tracks, chosen per
+    # sequence among those with rows in at least track_min_frames frames (native_results.follow_tracks); none: off
+    ("follow", str, "none"),
+    ("track_min_frames", int, 1),
 ]
 
 

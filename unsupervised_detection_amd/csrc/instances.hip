@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "host_checks.h"
+#include "packed_bytes.h"
 #include "rgb_groups.h"
 #include "track_rows.h"
 #include "wave_runs.h"
@@ -90,15 +91,7 @@ __global__ __launch_bounds__(256) void inst_paint_kernel(const int* __restrict__
     n_assigned += __popcll(__ballot(v >= 1 && v <= UDET_INSTANCE_WRAP));
     n_other += __popcll(__ballot(v == UDET_INSTANCE_UNASSIGNED));
     n_gt += __popcll(__ballot(g));
-    // the four bytes of an aligned word sit in four neighbouring lanes: its first lane stores them when all four are the sample's
-    const unsigned word = v | ((unsigned)__shfl_down((int)v, 1) << 8) | ((unsigned)__shfl_down((int)v, 2) << 16) |
-                          ((unsigned)__shfl_down((int)v, 3) << 24);
-    const long long p0 = p - (lane & 3);
-    if (p0 >= 0 && p0 + 3 < HW) {
-      if ((lane & 3) == 0) *reinterpret_cast<unsigned*>(mp + p0) = word;
-    } else if (valid) {
-      mp[p] = (unsigned char)v;  // the sample's head and tail
-    }
+    store_packed_byte(mp, p, HW, lane, valid, v);  // aligned words of four pixels, the sample's head and tail byte by byte
   }
   if (lane == 0) {
     if (n_assigned) atomicAdd(st + 0, n_assigned);

@@ -1,7 +1,7 @@
 """Output stage at native resolution: restore a batch of masks to each frame's own size, score them there and export them.
 
 The steps live in one module each -- native_restore (restore_masks), native_components (select_components), native_detections
-(component_boxes) and native_tracks (link_detections) -- and this module drives them over a folder of results.  Their public names are
+(component_boxes), native_tracks (link_detections), native_instances (instance_maps) and native_follow (follow_tracks) -- and this module drives them over a folder of results.  Their public names are
 importable from here as well.
 
   GtRule / GT_RULES / GtBatch / load_gt_device  a dataset's annotations binarised at native size, in one ragged.PackedLayout per batch
@@ -22,7 +22,8 @@ The full-resolution CRF (sxy = 60) is restore_results_dir(crf={...}) (DESIGN.md 
 and score -- the detections -- is restore_results_dir(detections={...}); linking them across the frames of a sequence
 is restore_results_dir(tracks={...}) (DESIGN.md 7.8), across frames in which a component is missing with tracks={"max_gap": G}
 (DESIGN.md 7.9); the tracks as per-frame instance maps, their picture and a track's J against the annotation is
-restore_results_dir(instances={...})."""
+restore_results_dir(instances={...}); exporting and scoring the masks of whole tracks, chosen without the annotation, is
+restore_results_dir(follow={...}) (native_follow)."""
 import functools
 import os
 from types import SimpleNamespace
@@ -33,6 +34,8 @@ import torch
 from .native_components import COMPONENT_MODES, COMPONENT_TILE, ComponentSelection, check_component_tables, select_components  # noqa: F401
 from .native_detections import (DET_FIELDS, DET_MAX_K, DETECTION_DEFAULTS, Detections, _host, component_boxes,  # noqa: F401
                                 detection_params, detection_records)
+from .native_follow import (FOLLOW_DEFAULTS, FOLLOW_RULES, FollowedMasks, check_follow_arguments, choose_tracks, follow_params,  # noqa: F401
+                            follow_tracks, keep_words)
 from .native_instances import (INSTANCE_PALETTE_BYTES, INSTANCE_UNASSIGNED, INSTANCE_WRAP, InstanceMaps, check_instance_arguments,  # noqa: F401
                                instance_maps, instance_params, track_gt_scores)
 from .native_restore import TAB, RestoredMasks, build_restore_tables, check_restore_tables, restore_box, restore_masks  # noqa: F401
@@ -189,7 +192,7 @@ def draw_instance_overlays(frames, maps, overlay):
 # ---------------------------------------------------------------------------------------------------------------------------
 def _resolve_options(o):
     """The options of restore_results_dir (`o`: its arguments by their names) checked in this order (ValueError) and filled in, in place:
-    batch and bound_th, the dicts through crf_params / detection_params / track_params / visualize.overlay_params / instance_params; o gains `boxes`
+    batch and bound_th, the dicts through crf_params / detection_params / track_params / visualize.overlay_params / instance_params / follow_params; o gains `boxes`
     (overlay["boxes"] through visualize.box_params, None: no boxes), `free` (no frame has an annotation) and `rule` (the GtRule)."""
     from .evaluation import BOUND_TH
     o.bound_th = BOUND_TH if o.bound_th is None else o.bound_th
@@ -224,6 +227,14 @@ def _resolve_options(o):
         raise ValueError("frame_lists mixes frames with and without an annotation")
     if o.free and o.component == "best_gt":
         raise ValueError('component "best_gt" needs annotations: use "largest" or None')
+    if o.follow is not None:
+        if o.tracks is None:
+            raise ValueError("follow chooses among the tracks: it needs tracks")
+        if o.component is not None:
+            raise ValueError("follow and component are alternative answers to which component is the mask: pass one of them")
+        o.follow = follow_params(o.follow)
+        if o.follow["rule"] == "best_gt" and (o.instances is None or o.free):
+            raise ValueError('follow rule "best_gt" scores the tracks against the annotation: it needs instances and annotations')
     o.rule = None if o.free else (GT_RULES[o.gt_rule] if isinstance(o.gt_rule, str) else o.gt_rule)
 
 
@@ -234,14 +245,90 @@ def _dump_json(content, *path):
         json.dump(content, fh, indent=1)
 
 
+def _score_batch(o, s, gt, pred, j, f):
+    """J / F of the batch whose first frame is the category's frame s, per distinct frame shape, into j / f."""
+    shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
+    for shape in sorted(set(shapes)):
+        idx = [i for i, sh in enumerate(shapes) if sh == shape]
+        j[[s + i for i in idx]], f[[s + i for i in idx]] = o.score(gt.stack(idx), pred.stack(idx), o.bound_th)
+
+
+def _draw_batch(o, frames, pred, inst, det, trk):
+    """The batch's overlays: every tracked component in its track's colour (inst given and instances["overlay"]), or the final mask
+    `pred`; then the boxes, when asked."""
+    drawn = o.draw_instances(frames, inst, o.overlay) if inst is not None and o.instances["overlay"] else o.draw(frames, pred, o.overlay)
+    if o.boxes is not None:
+        drawn = o.draw_boxes(drawn, det, o.boxes) if trk is None else o.draw_track_boxes(drawn, det, trk, o.boxes)
+    return drawn
+
+
+def _write_batch(o, cat, s, stems, gt, res, pred, inst, drawn, fg):
+    """The files of a batch's frames: with pred, <stem>.png and result_<k>.mat (and, annotation-free, the frame's share of foreground
+    into fg); with inst, the instance map; with drawn, the overlay."""
+    import scipy.io as sio
+    from PIL import Image
+    od = os.path.join(o.out_dir, cat)
+    for i, stem in enumerate(stems):
+        if pred is not None:
+            binm = _host(pred.binary_sample(i)).astype(np.uint8)
+            Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, stem + ".png"))
+            mat = {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32)}
+            if o.free:
+                fg[s + i] = int(np.count_nonzero(binm)) / int(binm.size)
+            else:
+                mat["gt_mask"] = _host(gt.sample(i)).astype(np.uint8)
+            sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)), mat)
+        if inst is not None:
+            im = Image.fromarray(np.ascontiguousarray(_host(inst.sample(i)), dtype=np.uint8), "P")
+            im.putpalette(INSTANCE_PALETTE_BYTES)
+            im.save(os.path.join(o.out_dir, "instances", cat, stem + ".png"))
+        if drawn is not None:
+            Image.fromarray(np.ascontiguousarray(_host(drawn.sample(i)), dtype=np.uint8), "RGB").save(
+                os.path.join(o.out_dir, "overlay", cat, stem + ".png"))
+
+
+HELD_TRACK_DROPS = ("carry", "hist_open", "inter", "gap_inter")  # of a batch's Tracks: pass 2 reads its ids alone
+HELD_RESTORED_DROPS = ("binary",)                               # of a batch's RestoredMasks: pass 2 reads its soft bytes and amax
+
+
+def _held(obj, drops):
+    """A shallow copy of obj with the attributes `drops` set to None where it has them: what pass 2 of `follow` does not read is not
+    kept alive between the passes -- the carried frames' labels a Tracks references above all (4 bytes per pixel of up to max_gap + 1
+    frames per batch).  obj itself stays as it is."""
+    import copy
+    c = copy.copy(obj)
+    for name in drops:
+        if getattr(c, name, None) is not None:
+            setattr(c, name, None)
+    return c
+
+
+def _follow_category(cat, held, words, o, j, f, fg):
+    """Pass 2 of a category under `follow`: per held batch, in this order, load gt, keep (the kept rows' masks), score, draw, draw boxes,
+    write.  The frames of the overlay are read again, not held.  Returns per frame kept / (kept + dropped), 0 without foreground."""
+    kept = []
+    for s, rows, stems, labelled, det, trk, res in held:
+        gt = None if o.free else o.load_gt([a for _, a in rows], o.rule)
+        pred = o.keep(labelled, det, words[s:s + len(rows)], gt=gt)
+        kept += [int(a) / (int(a) + int(b)) if int(a) + int(b) else 0.0 for a, b in pred.host()[:, :2]]
+        if not o.free:
+            _score_batch(o, s, gt, pred, j, f)
+        drawn = None
+        if o.overlay is not None and not (o.instances is not None and o.instances["overlay"]):  # (that picture was pass 1's)
+            drawn = _draw_batch(o, o.load_images([img for img, _ in rows]), pred, None, det, trk)
+        _write_batch(o, cat, s, stems, gt, res, pred, None, drawn, fg)
+    return kept
+
+
 def _restore_category(cat, entries, o):
     """One category of restore_results_dir under the resolved options `o`: its batches through the injected callables in the order load
     gt or sizes, restore, load frames, refine, select, detect, link, paint, score, draw, draw boxes, write.  Writes the category's files and
     returns its record for the summary: frames, components_mean, foreground_mean; annotated: j and f (per frame); with detections:
-    detections_mean; with tracks: tracks and track_len_mean; with instances: unassigned_mean and, annotated, best_track_j."""
+    detections_mean; with tracks: tracks and track_len_mean; with instances: unassigned_mean and, annotated, best_track_j.  With follow
+    the loop stops after paint (pass 1: the batch's labels, detections, track ids and restored soft bytes stay on the device), choose_tracks runs
+    once, and _follow_category (pass 2) scores, draws and writes the kept tracks' masks; the record gains kept_mean."""
     import re
     import scipy.io as sio
-    from PIL import Image
     d = os.path.join(o.results_dir, cat)
     ks = sorted(int(m.group(1)) for m in (re.fullmatch(r"result_(\d+)\.mat", f) for f in (os.listdir(d) if os.path.isdir(d) else [])) if m)
     if ks != list(range(1, len(entries) + 1)):
@@ -256,6 +343,8 @@ def _restore_category(cat, entries, o):
     records = {}  # frame stem -> its detections, in the list's order
     tail, starts = None, []  # tracks: the previous batch's last frame; per frame, whether it starts a sequence
     row_gts, gt_area, unassigned = [], [], []  # instances, per frame: row_gt of its records, its annotated pixels, the share of value 255
+    held, score_sums = [], []  # follow: per batch what pass 2 reads, held on the device; per frame the score_sum of its rows
+    own_overlay = o.overlay is not None and (o.follow is None or (o.instances is not None and o.instances["overlay"]))  # drawn in this loop
     for s in range(0, len(entries), o.batch):
         rows = entries[s:s + o.batch]
         images = [img for img, _ in rows]
@@ -275,7 +364,7 @@ def _restore_category(cat, entries, o):
             raise ValueError("load_sizes must return one (H, W) per path")
         res = o.restore(np.stack(masks), sizes, o.crop, o.threshold)
         pred = res  # what is scored and exported as the binary mask
-        frames = o.load_images(images) if o.crf is not None or o.overlay is not None else None  # read once for both
+        frames = o.load_images(images) if o.crf is not None or own_overlay else None  # read once for both
         if o.crf is not None:
             pred = o.refine(res, frames, o.crf)
         if o.component is not None:  # with detections: the batch's labels as well -- what the CRF left, labelled once
@@ -301,32 +390,22 @@ def _restore_category(cat, entries, o):
                     gt_area += [int(v) for v in stats[:, 2]]
                     unassigned += [int(u) / (int(a) + int(u)) if int(a) + int(u) else 0.0 for a, u in stats[:, :2]]
             records.update(zip(stems, recs))
+        if o.follow is not None:  # pass 1 of 2: what depends on the final binary mask waits until the category's tracks are known
+            held.append((s, rows, stems, labelled, det, _held(trk, HELD_TRACK_DROPS), _held(res, HELD_RESTORED_DROPS)))
+            score_sums += [[int(v) for v in det.rows(i)[:, DET_FIELDS - 1]] for i in range(len(rows))]
+            drawn = _draw_batch(o, frames, None, inst, det, trk) if own_overlay else None
+            _write_batch(o, cat, s, stems, None, None, None, inst, drawn, fg)
+            continue
         if not o.free:
-            shapes = [tuple(int(v) for v in hw) for hw in gt.hw]
-            for shape in sorted(set(shapes)):
-                idx = [i for i, sh in enumerate(shapes) if sh == shape]
-                j[[s + i for i in idx]], f[[s + i for i in idx]] = o.score(gt.stack(idx), pred.stack(idx), o.bound_th)
-        drawn = None
-        if o.overlay is not None:  # every tracked component in its track's colour, or the final mask
-            drawn = o.draw_instances(frames, inst, o.overlay) if inst is not None and o.instances["overlay"] else o.draw(frames, pred, o.overlay)
-        if o.boxes is not None:
-            drawn = o.draw_boxes(drawn, det, o.boxes) if trk is None else o.draw_track_boxes(drawn, det, trk, o.boxes)
-        for i, stem in enumerate(stems):
-            binm = _host(pred.binary_sample(i)).astype(np.uint8)
-            Image.fromarray(binm * np.uint8(255), "L").save(os.path.join(od, stem + ".png"))
-            mat = {"mask": binm, "soft_mask": _host(res.soft(i)).astype(np.float32)}
-            if o.free:
-                fg[s + i] = int(np.count_nonzero(binm)) / int(binm.size)
-            else:
-                mat["gt_mask"] = _host(gt.sample(i)).astype(np.uint8)
-            sio.savemat(os.path.join(od, "result_{}.mat".format(s + i + 1)), mat)
-            if inst is not None:
-                im = Image.fromarray(np.ascontiguousarray(_host(inst.sample(i)), dtype=np.uint8), "P")
-                im.putpalette(INSTANCE_PALETTE_BYTES)
-                im.save(os.path.join(o.out_dir, "instances", cat, stem + ".png"))
-            if drawn is not None:
-                Image.fromarray(np.ascontiguousarray(_host(drawn.sample(i)), dtype=np.uint8), "RGB").save(
-                    os.path.join(o.out_dir, "overlay", cat, stem + ".png"))
+            _score_batch(o, s, gt, pred, j, f)
+        drawn = None if o.overlay is None else _draw_batch(o, frames, pred, inst, det, trk)
+        _write_batch(o, cat, s, stems, gt, res, pred, inst, drawn, fg)
+    scores = track_gt_scores(list(records.values()), row_gts, gt_area, starts) if o.instances is not None and not o.free else None
+    if o.follow is not None:  # the category's tracks are known: choose once, then pass 2 over the held batches
+        gt = res = pred = frames = labelled = det = trk = inst = tail = None  # (the last batch's own objects are let go as well)
+        means = [sc["gt_j_mean"] for sc in scores] if o.follow["rule"] == "best_gt" else None
+        kept_ranks, followed = choose_tracks(list(records.values()), score_sums, starts, o.follow["rule"], o.follow["min_frames"], means)
+        kept = _follow_category(cat, held, keep_words(kept_ranks, len(entries)), o, j, f, fg)
     rec = {"frames": len(entries), "components_mean": float(nc.mean()) if len(nc) else 0.0, "foreground_mean": float(fg.mean()) if len(fg) else 0.0}
     if not o.free:
         rec["j"], rec["f"] = j.tolist(), f.tolist()
@@ -341,12 +420,15 @@ def _restore_category(cat, entries, o):
                 if any(t["id"] >= INSTANCE_WRAP for t in seq["tracks"]):
                     seq["wrapped"] = True  # two of its tracks share a value of the map
             if not o.free:
-                scores = track_gt_scores(list(records.values()), row_gts, gt_area, starts)
                 for seq, sc in zip(summary, scores):
                     for t in seq["tracks"]:
                         t["gt_j_mean"] = sc["gt_j_mean"][t["id"]]
                     seq["best_track"] = sc["best_track"]
                 rec["best_track_j"] = float(sum(sc["frames"] * sc["best_j"] for sc in scores) / sum(sc["frames"] for sc in scores)) if scores else 0.0
+        if o.follow is not None:
+            rec["kept_mean"] = float(np.mean(kept)) if kept else 0.0
+            for seq, ids in zip(summary, followed):
+                seq["followed"] = ids
         _dump_json(summary, o.out_dir, "tracks", cat + ".json")
         lengths = [t["frames"] for seq in summary for t in seq["tracks"]]
         rec["tracks"], rec["track_len_mean"] = len(lengths), float(np.mean(lengths)) if lengths else 0.0
@@ -394,6 +476,10 @@ def _summary(cats, o):
         seq.update((k, cats[c][k]) for k in per_sequence)
     if o.instances is not None and not o.free:
         out["best_track_J"] = _nanmean([r["best_track_j"] for r in cats.values()])
+    if o.follow is not None:
+        out["follow"] = o.follow
+        for c, seq in out["sequences"].items():
+            seq["kept_mean"] = cats[c]["kept_mean"]
     return out
 
 
@@ -403,7 +489,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                         refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays, detections=None,
                         detect=component_boxes, draw_boxes=draw_detection_boxes, tracks=None, link=link_detections,
                         draw_track_boxes=draw_track_detection_boxes, instances=None, paint=instance_maps,
-                        draw_instances=draw_instance_overlays):
+                        draw_instances=draw_instance_overlays, follow=None, keep=follow_tracks):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -464,8 +550,23 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     tracked component in its track's colour (visualize.overlay_instances with the overlay's alpha, beta and edge) -- those the component
     selection removed from the exported binary mask too; the boxes are still painted on top when asked.  With None nothing of this
     runs and every file is byte for byte what it is without the argument.
+    follow (None: off; needs tracks; not together with a component mode -- the two are alternative answers to the same question):
+    {"rule": "mass" | "area" | "length" | "best_gt" | "all" ("mass"), "min_frames": N (1)}, {} for the defaults.  The exported binary mask
+    becomes that of whole tracks, chosen per sequence once the sequence is known, so a category runs in two passes.  Pass 1 is the loop
+    above up to and including paint: the detections, tracks and instance-map files (and, with instances["overlay"], the overlay) come out
+    of it unchanged; J / F, <stem>.png, result_<k>.mat, foreground_mean and the overlay of the final mask wait, and every batch's labels,
+    detections, track ids and restored soft bytes stay on the device (5 bytes per pixel and frame -- the frames a batch was linked against
+    and its thresholded mask are let go: DESIGN.md 7.11).  choose_tracks then runs once
+    per category -- a track is eligible with rows in at least min_frames frames of its sequence; "all" keeps every eligible track, the
+    other rules one per sequence: the largest sum of score_sum ("mass"), of area ("area"), the most frames ("length") or the largest
+    gt_j_mean ("best_gt": needs instances and annotations) -- and pass 2 takes the held batches in the order load gt, keep(labelled, det,
+    words, gt=...) (follow_tracks: two launches per batch), score, draw (the frames are read again), draw boxes, write.  A frame in which
+    no kept track has a row exports an empty mask.  The json gains "follow": {rule, min_frames} and per sequence "kept_mean" (the mean
+    over its frames of kept / (kept + dropped) foreground pixels, 0 for a frame without foreground), the sequences of
+    tracks/<category>.json "followed": [ids]; new keys come after the existing ones.  With None nothing of this runs and every file is
+    byte for byte what it is without the argument.
     restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes / paint /
-    draw_instances are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    draw_instances / keep are injectable: the host logic runs without a GPU on numpy stand-ins."""
     o = SimpleNamespace(**locals())  # every argument under its own name: the options and the injected callables
     _resolve_options(o)
     cats = {cat: _restore_category(cat, entries, o) for cat, entries in frame_lists.items()}
