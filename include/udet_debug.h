@@ -93,6 +93,35 @@ int udet_debug_upconv_lowres_bwd(const float* dy, int ldy, int y_coff, const flo
  * taps_cap < ntaps: UDET_ERR_ARG with *ntaps set.  udet_debug_max_segs: UDET_MAX_SEGS of the launcher. */
 int udet_debug_upconv_tables(int h, int w, int backward, int* nseg, int* seg, int* seg_tap, int* taps, int taps_cap, int* ntaps);
 int udet_debug_max_segs(void);
+/* ---- The glue launchers of csrc/elementwise.hip that have no entry point in udet.h, one launch each (tests/test_glue_gpu.py) ----------------
+ * udet_debug_<launcher>(...) checks its arguments and calls launch_<launcher> with them; nothing else.  Every check comes before the
+ * first HIP call:  a NULL pointer, a count < 1, ncalls outside 0..3, copies outside 1..3, an unknown act, a workspace that is too small
+ * -> UDET_ERR_ARG;  ld < 1, coff < 0 or a channel window [coff, coff + c) that does not fit in ld -> UDET_ERR_SHAPE;  a pointer that is not
+ * aligned for the vector accesses of its kernel -> UDET_ERR_ALIGN (float2: flow-shaped tensors f; float4: x8, gin, fin, dfin, imgin and, for
+ * share / fold, buf whenever ld, coff and c are all multiples of 4 -- the float4 form; double: the gen_input workspace).
+ * Layouts (NHWC, P = pixels of the B samples):
+ *   resize fwd:  y[n,oh,ow,ldy] channels [y_coff, y_coff + c) = legacy_bilinear(x[n,h,w,ldx] channels [x_coff, x_coff + c)) * mul / div
+ *   resize bwd:  dx[n,h,w,ldx] window (+)= adjoint of the same resize applied to dy[n,oh,ow,ldy] window
+ *   share / fold: buf [copies * P, ld], window [coff, coff + c): share copies rows [0, P) to rows [k P, (k + 1) P), k = 1..copies - 1;
+ *                fold adds those rows onto rows [0, P) in the order (x0 + x1) + x2 and leaves them as they are
+ *   emit_du:     u = d * act'(a) on the window of [P, ld] rows, act' taken from the stored output a
+ *   pack_pwc_input: x8 [2P, 4] = [i1 + 0.5 | 0] then [i2 + 0.5 | 0];  i1, i2 [P, 3]
+ *   gen_input:   gin [B, HW, 8] = [img (3), standardised flow (2), 0, 0, 0];  workspace: udet_debug_gen_input_workspace_bytes(B), 8-byte aligned
+ *   mask_rec_inputs: logits [P, 8] (channels 0, 1 read), f [P, 2] -> mask [P], fin [3P, 4] (rows of the first `ncalls` calls written)
+ *   pack_imgin:  imgin [ncalls * P, 4] = [img | 0] per call;  mask_bwd: dlogits [P, 8], channels 0 and 1 written */
+int udet_debug_launch_resize_bilinear_fwd(const float* x, int ldx, int x_coff, int n, int h, int w, float* y, int ldy, int y_coff, int oh, int ow,
+                                          int c, float mul, float div, void* stream);
+int udet_debug_launch_resize_bilinear_bwd(const float* dy, int ldy, int y_coff, int n, int oh, int ow, float* dx, int ldx, int x_coff, int h, int w,
+                                          int c, int accumulate, void* stream);
+int udet_debug_launch_share_samples(float* buf, long p, int ld, int coff, int c, int copies, void* stream);
+int udet_debug_launch_fold_samples(float* buf, long p, int ld, int coff, int c, int copies, void* stream);
+int udet_debug_launch_emit_du(const float* d, const float* a, float* u, long p, int ld, int coff, int c, int act, float alpha, void* stream);
+int udet_debug_launch_pack_pwc_input(const float* i1, const float* i2, float* x8, long p, void* stream);
+size_t udet_debug_gen_input_workspace_bytes(int b);
+int udet_debug_launch_gen_input(const float* img, const float* f, float* gin, int b, long hw, void* workspace, size_t workspace_bytes, void* stream);
+int udet_debug_launch_mask_rec_inputs(const float* logits, const float* f, float* mask, float* fin, long p, int ncalls, void* stream);
+int udet_debug_launch_pack_imgin(const float* img, float* imgin, long p, int ncalls, void* stream);
+int udet_debug_launch_mask_bwd(const float* dmask, const float* dfin, const float* f, const float* mask, float* dlogits, long p, void* stream);
 /* (The experiment knobs of earlier rounds -- lane choices and the work-skipping ablation mask -- are no longer reachable from any library
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */

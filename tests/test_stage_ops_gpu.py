@@ -114,6 +114,113 @@ def test_clip_or_noise_and_adam_step_equal_the_fused_apply(ops):
     assert torch.equal(a, b) and float(a.min()) >= 0.0 and float(a.max()) <= 0.2 and abs(float(a.mean()) - 0.1) < 2e-3
 
 
+# ---- the same entry points at the shapes, masks and values where the kernels take another path (oracle/oracle_glue.py holds the cases and
+# the measured tolerances G.TOL; tests/test_glue_oracle.py re-measures them on the CPU) ---------------------------------------------------
+from oracle import oracle_glue as G  # noqa: E402
+
+
+@pytest.mark.parametrize("cbn", G.LOSS_CBN)
+@pytest.mark.parametrize("B,H,W", G.LOSS_SHAPES)
+def test_losses_at_small_and_odd_shapes(ops, B, H, W, cbn):
+    """losses_forward, both losses_backward forms and charbonnier_loss at B = 1 and 3, HW = 15 (below one block), 257 (one past a block)
+    and 33 x 40; masks all 0, all 1 and random; epsilon 75 and 1e-3 (small enough for the denominators to matter).  All eight losses at
+    1e-4; coef ITSELF against float64 autograd through the four per-sample sums (G.coef_f64), each derivative relative to its own
+    largest value, at G.TOL['coef'] (measured 3.74e-7, allowed 4 x); the gradients at 1e-4."""
+    for kind in G.LOSS_MASKS:
+        for eps in G.LOSS_EPS:
+            flow, mask, pred3 = G.loss_case(B, H, W, kind, 80 + G.LOSS_SHAPES.index((B, H, W)))
+            L, coef = ops.losses_forward(flow.cuda(), mask.cuda(), pred3.cuda(), cbn, eps)
+            fd, md, pd = flow.double(), mask.double().requires_grad_(True), pred3.double().requires_grad_(True)
+            ref, _ = G.losses(fd, md, pd, cbn, eps)
+            for k, v in zip(ops.LOSS_KEYS, L.cpu().tolist()):
+                assert abs(v - float(ref[k])) < 1e-4 * max(1.0, abs(float(ref[k]))), (kind, eps, k, v, float(ref[k]))
+            c64 = G.coef_f64(flow, mask, pred3, cbn, eps)
+            for j in range(4):
+                assert G.relmax(coef.cpu()[:, j], c64[:, j]) <= G.TOL["coef"], (kind, eps, j, coef.cpu()[:, j], c64[:, j])
+            gp, = torch.autograd.grad(ref["recover"], [pd], retain_graph=True)
+            dpred = ops.losses_backward(flow.cuda(), mask.cuda(), pred3.cuda(), "recover", cbn=cbn).cpu()
+            assert rel(dpred, gp.float()) < 1e-4, (kind, eps)
+            gp, gm = torch.autograd.grad(ref["generator"], [pd, md])
+            dpred, dmask = ops.losses_backward(flow.cuda(), mask.cuda(), pred3.cuda(), "generator", coef, cbn=cbn)
+            assert rel(dpred.cpu(), gp[:2 * B].float()) < 1e-4, (kind, eps)
+            assert rel(dmask.cpu(), gm.float()) < 1e-4, (kind, eps)
+            got = ops.charbonnier_loss(flow.cuda(), pred3[:B].cuda(), mask.cuda(), cbn).cpu()
+            assert rel(got, O.charbonnier_loss(fd, pd[:B].detach(), md.detach(), cbn).float()) < 1e-5, (kind, eps)
+
+
+@pytest.mark.parametrize("cbn", G.LOSS_CBN)
+@pytest.mark.parametrize("B,H,W", G.LOSS_SHAPES)
+def test_losses_where_the_prediction_equals_the_flow(ops, B, H, W, cbn):
+    """pred3[:B] == flow: every pixel's loss term is 2 * 0.001^(2 cbn) * mask, and the Charbonnier derivative is exactly 0"""
+    for kind in G.LOSS_MASKS:
+        flow, mask, pred3 = G.loss_case(B, H, W, kind, 90, equal_pred=True)
+        want = 2.0 * 0.001 ** (2 * cbn) * mask.double().sum(dim=(1, 2, 3))  # (= 2 HW 0.001^(2 cbn) mask for a constant mask)
+        got = ops.charbonnier_loss(flow.cuda(), pred3[:B].cuda(), mask.cuda(), cbn).cpu()
+        assert rel(got, want.float()) < 1e-5, kind
+        L, coef = ops.losses_forward(flow.cuda(), mask.cuda(), pred3.cuda(), cbn, 75.0)
+        assert abs(float(L[4]) - float(want[0])) < 1e-4 * max(1.0, float(want[0])), kind
+        dpred = ops.losses_backward(flow.cuda(), mask.cuda(), pred3.cuda(), "recover", cbn=cbn).cpu()
+        assert float(dpred[:B].abs().max()) == 0.0, kind
+        dpred, _ = ops.losses_backward(flow.cuda(), mask.cuda(), pred3.cuda(), "generator", coef, cbn=cbn)
+        assert float(dpred[:B].abs().max()) == 0.0, kind
+
+
+@pytest.mark.parametrize("t", G.ADAM_T)
+@pytest.mark.parametrize("n", G.ADAM_N)
+def test_clip_and_adam_state_against_tf_adam(ops, n, t):
+    """g after the clip bit for bit, then m and v -- not only w -- against O.TFAdam in float64 after every apply, for gradients that hold
+    exactly +-clip, +-(clip + 1 ulp), 0 and 1e-20, at applies t and t + 1 (lr_t from the float64 closed form, as udet_adam_step computes
+    it) and at n = 1, 255, 257 and one past the 2048-workgroup grid cap.  w at the project's 1e-6; m and v at G.TOL (measured 2.04e-6 /
+    1.63e-7 relative over the two applies, allowed 4 x)."""
+    w0, g0, m0, v0 = G.adam_case(n, 70 + G.ADAM_N.index(n))
+    w, m, v = w0.cuda(), m0.cuda(), v0.cuda()
+    rw, rm, rv = w0.double(), m0.double(), v0.double()
+    for k, gk in enumerate(G.adam_gradients(g0)):
+        tt, g = t + k, gk.cuda()
+        want_g = G.clip_f32(g.cpu(), G.ADAM_CLIP)
+        ops.clip_or_noise_(g, G.ADAM_CLIP, None)
+        assert torch.equal(g.cpu(), want_g)
+        if k == 0 and n >= 7:
+            assert torch.equal(g.cpu()[:4].abs(), torch.full((4,), G.ADAM_CLIP))  # +-clip stay, +-(clip + 1 ulp) land on +-clip
+        ops.adam_step_(w, g, m, v, tt)
+        rw, rm, rv = G.adam_f64(rw, want_g, rm, rv, tt)
+        assert float((w.cpu().double() - rw).abs().max()) < 1e-6
+        assert G.relmax(m.cpu(), rm) <= G.TOL["adam_m"] and G.relmax(v.cpu(), rv) <= G.TOL["adam_v"]
+
+
+@pytest.fixture(scope="module")
+def tail_engine():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from unsupervised_detection_amd import weights as W
+    from unsupervised_detection_amd.engine import Engine, EngineConfig
+    return Engine(EngineConfig(batch_size=2, in_height=128, in_width=192, img_height=64, img_width=128)), W
+
+
+@pytest.mark.parametrize("t", G.ADAM_T)
+@pytest.mark.parametrize("net", ["gen", "rec"])
+def test_fused_apply_equals_clip_then_adam_at_the_edge_values(ops, tail_engine, net, t):
+    """eng.apply (adam_kernel mode 0) == clip (mode 1) followed by Adam (mode 2), bit for bit in w, g, m and v, on a gradient with the
+    edge values at its front and at applies 1, 2, 1000 and 100000; both nets' flat buffers are longer than the grid: the stride loop runs"""
+    eng, W = tail_engine
+    nid = W.NET_GEN if net == "gen" else W.NET_REC
+    n = W.param_total(nid)
+    assert n > 2048 * 256
+    w0, g0, m0, v0 = G.adam_case(n, 75)
+    fused = [x.cuda() for x in (w0, g0, m0, v0)]
+    eng.adam_step = t - 1
+    eng.apply(nid, *fused)
+    assert eng.adam_step == t
+    if nid == W.NET_GEN:
+        assert float(eng.buffer("noise_flag").view(-1)[1]) == 0.0
+    w, g, m, v = (x.cuda() for x in (w0, g0, m0, v0))
+    ops.clip_or_noise_(g, G.ADAM_CLIP, None)
+    ops.adam_step_(w, g, m, v, t)
+    for a, b in zip(fused, (w, g, m, v)):
+        assert torch.equal(a, b)
+    assert torch.equal(g.cpu(), G.clip_f32(g0, G.ADAM_CLIP))
+
+
 @pytest.fixture(scope="module")
 def small_step():
     if not torch.cuda.is_available():

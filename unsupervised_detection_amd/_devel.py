@@ -52,6 +52,31 @@ dbg.udet_debug_upconv_tables.restype = ctypes.c_int
 dbg.udet_debug_upconv_tables.argtypes = [_i, _i, _i] + [_p] * 4 + [_i, _p]
 dbg.udet_debug_max_segs.restype = ctypes.c_int
 dbg.udet_debug_max_segs.argtypes = []
+# the glue launchers of csrc/elementwise.hip, one launch each (include/udet_debug.h; tests/test_glue_gpu.py)
+_l = ctypes.c_long
+for _name, _args in (("resize_bilinear_fwd", [_p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _f, _f, _p]),
+                     ("resize_bilinear_bwd", [_p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+                     ("share_samples", [_p, _l, _i, _i, _i, _i, _p]),
+                     ("fold_samples", [_p, _l, _i, _i, _i, _i, _p]),
+                     ("emit_du", [_p, _p, _p, _l, _i, _i, _i, _i, _f, _p]),
+                     ("pack_pwc_input", [_p, _p, _p, _l, _p]),
+                     ("gen_input", [_p, _p, _p, _i, _l, _p, ctypes.c_size_t, _p]),
+                     ("mask_rec_inputs", [_p, _p, _p, _p, _l, _i, _p]),
+                     ("pack_imgin", [_p, _p, _l, _i, _p]),
+                     ("mask_bwd", [_p, _p, _p, _p, _p, _l, _p])):
+    _fn = getattr(dbg, "udet_debug_launch_" + _name)
+    _fn.restype = ctypes.c_int
+    _fn.argtypes = _args
+dbg.udet_debug_gen_input_workspace_bytes.restype = ctypes.c_size_t
+dbg.udet_debug_gen_input_workspace_bytes.argtypes = [_i]
+
+
+def launch(name: str, *args):
+    """udet_debug_launch_<name>(*args, current stream) with tensors passed as their data pointers; a refusal raises ValueError
+    (_ffi.check) before anything reaches the device."""
+    import torch
+    raw = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+    _check(getattr(dbg, "udet_debug_launch_" + name)(*raw, torch.cuda.current_stream().cuda_stream))
 
 
 def upconv_tables(h: int, w: int, backward: bool):

@@ -7,6 +7,7 @@
 
 #include "../../../include/udet_debug.h"
 #include "../conv_host.h"
+#include "../elementwise.h"
 #include "../plan_run.h"
 
 using namespace udet;
@@ -257,6 +258,128 @@ int udet_debug_upconv_tables(int h, int w, int backward, int* nseg, int* seg, in
   seg_tap[g.nseg] = g.seg_tap[g.nseg];
   for (int t = 0; t < *ntaps; ++t) { taps[3 * t] = g.taps[t].dy; taps[3 * t + 1] = g.taps[t].dx; taps[3 * t + 2] = g.taps[t].widx; }
   return UDET_OK;
+}
+
+}  // extern "C"
+// ---- the glue launchers of elementwise.hip, one launch each (tests/test_glue_gpu.py): argument checks, then the launcher ---------------------
+namespace {
+const long GLUE_MAX_PIXELS = 1L << 31;
+bool glue_misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+// a channel window [coff, coff + c) of a row of ld floats; 0 or the error code (message set)
+int glue_window(const char* who, const char* what, int ld, int coff, int c) {
+  if (c < 1) { set_error("%s: %s needs at least one channel", who, what); return UDET_ERR_ARG; }
+  if (ld < 1 || coff < 0 || (long)coff + c > ld) {
+    set_error("%s: channel window of %s outside the buffer (%d+%d of %d)", who, what, coff, c, ld);
+    return UDET_ERR_SHAPE;
+  }
+  return UDET_OK;
+}
+int glue_pixels(const char* who, long p) {
+  if (p < 1) { set_error("%s: pixel count must be positive", who); return UDET_ERR_ARG; }
+  if (p >= GLUE_MAX_PIXELS) { set_error("%s: pixel count too large", who); return UDET_ERR_SHAPE; }
+  return UDET_OK;
+}
+int glue_align(const char* who, const char* what, const void* p, unsigned bytes) {
+  if (glue_misaligned(p, bytes)) { set_error("%s: %s must be %u-byte aligned", who, what, bytes); return UDET_ERR_ALIGN; }
+  return UDET_OK;
+}
+int glue_resize_check(const char* who, const float* src, int lds, int s_coff, float* dst, int ldd, int d_coff, int n, int h, int w, int oh, int ow,
+                      int c) {
+  if (!src || !dst || n < 1 || h < 1 || w < 1 || oh < 1 || ow < 1) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_window(who, "the source grid's tensor", lds, s_coff, c));
+  UDET_TRY(glue_window(who, "the output grid's tensor", ldd, d_coff, c));
+  UDET_TRY(glue_pixels(who, (long)n * h * w));
+  UDET_TRY(glue_pixels(who, (long)n * oh * ow));
+  UDET_TRY(glue_align(who, "the source tensor", src, 4));
+  return glue_align(who, "the output tensor", dst, 4);
+}
+int glue_share_fold_check(const char* who, const float* buf, long p, int ld, int coff, int c, int copies) {
+  if (!buf || copies < 1 || copies > 3) { set_error("%s: bad argument (copies 1..3)", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_window(who, "buf", ld, coff, c));
+  UDET_TRY(glue_pixels(who, p * copies));
+  const bool v4 = ld % 4 == 0 && coff % 4 == 0 && c % 4 == 0;  // (launch_share_fold takes the float4 form then)
+  return glue_align(who, "buf", buf, v4 ? 16 : 4);
+}
+}  // namespace
+extern "C" {
+int udet_debug_launch_resize_bilinear_fwd(const float* x, int ldx, int x_coff, int n, int h, int w, float* y, int ldy, int y_coff, int oh, int ow,
+                                          int c, float mul, float div, void* stream) {
+  const char* who = "debug_launch_resize_bilinear_fwd";
+  if (!(div != 0.f)) { set_error("%s: div must not be 0", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_resize_check(who, x, ldx, x_coff, y, ldy, y_coff, n, h, w, oh, ow, c));
+  return launch_resize_bilinear_fwd(x, ldx, x_coff, n, h, w, y, ldy, y_coff, oh, ow, c, mul, div, (hipStream_t)stream);
+}
+int udet_debug_launch_resize_bilinear_bwd(const float* dy, int ldy, int y_coff, int n, int oh, int ow, float* dx, int ldx, int x_coff, int h, int w,
+                                          int c, int accumulate, void* stream) {
+  const char* who = "debug_launch_resize_bilinear_bwd";
+  if (accumulate != 0 && accumulate != 1) { set_error("%s: accumulate must be 0 or 1", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_resize_check(who, dy, ldy, y_coff, dx, ldx, x_coff, n, oh, ow, h, w, c));
+  return launch_resize_bilinear_bwd(dy, ldy, y_coff, n, oh, ow, dx, ldx, x_coff, h, w, c, accumulate, (hipStream_t)stream);
+}
+int udet_debug_launch_share_samples(float* buf, long p, int ld, int coff, int c, int copies, void* stream) {
+  UDET_TRY(glue_share_fold_check("debug_launch_share_samples", buf, p, ld, coff, c, copies));
+  return launch_share_samples(buf, p, ld, coff, c, copies, (hipStream_t)stream);
+}
+int udet_debug_launch_fold_samples(float* buf, long p, int ld, int coff, int c, int copies, void* stream) {
+  UDET_TRY(glue_share_fold_check("debug_launch_fold_samples", buf, p, ld, coff, c, copies));
+  return launch_fold_samples(buf, p, ld, coff, c, copies, (hipStream_t)stream);
+}
+int udet_debug_launch_emit_du(const float* d, const float* a, float* u, long p, int ld, int coff, int c, int act, float alpha, void* stream) {
+  const char* who = "debug_launch_emit_du";
+  if (!d || !a || !u || (act != UDET_ACT_NONE && act != UDET_ACT_LEAKY && act != UDET_ACT_ELU)) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_window(who, "d / a / u", ld, coff, c));
+  UDET_TRY(glue_pixels(who, p));
+  if (glue_misaligned(d, 4) || glue_misaligned(a, 4) || glue_misaligned(u, 4)) { set_error("%s: misaligned pointer", who); return UDET_ERR_ALIGN; }
+  return launch_emit_du(d, a, u, p, ld, coff, c, act, alpha, (hipStream_t)stream);
+}
+int udet_debug_launch_pack_pwc_input(const float* i1, const float* i2, float* x8, long p, void* stream) {
+  const char* who = "debug_launch_pack_pwc_input";
+  if (!i1 || !i2 || !x8) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_pixels(who, 2 * p));
+  if (glue_misaligned(i1, 4) || glue_misaligned(i2, 4)) { set_error("%s: misaligned image pointer", who); return UDET_ERR_ALIGN; }
+  UDET_TRY(glue_align(who, "x8", x8, 16));
+  return launch_pack_pwc_input(i1, i2, x8, p, (hipStream_t)stream);
+}
+size_t udet_debug_gen_input_workspace_bytes(int b) { return b < 1 ? 0 : flow_stats_doubles(b) * sizeof(double); }
+int udet_debug_launch_gen_input(const float* img, const float* f, float* gin, int b, long hw, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "debug_launch_gen_input";
+  if (!img || !f || !gin || b < 1 || b > 65535 || !workspace || workspace_bytes < udet_debug_gen_input_workspace_bytes(b)) {
+    set_error("%s: bad argument (workspace: udet_debug_gen_input_workspace_bytes)", who);
+    return UDET_ERR_ARG;
+  }
+  if (hw < 1) { set_error("%s: pixel count must be positive", who); return UDET_ERR_ARG; }
+  if (hw >= GLUE_MAX_PIXELS / b) { set_error("%s: pixel count too large", who); return UDET_ERR_SHAPE; }
+  UDET_TRY(glue_align(who, "img", img, 4));
+  UDET_TRY(glue_align(who, "f", f, 8));
+  UDET_TRY(glue_align(who, "gin", gin, 16));
+  UDET_TRY(glue_align(who, "workspace", workspace, 8));
+  return launch_gen_input(img, f, reinterpret_cast<double*>(workspace), gin, b, hw, (hipStream_t)stream);
+}
+int udet_debug_launch_mask_rec_inputs(const float* logits, const float* f, float* mask, float* fin, long p, int ncalls, void* stream) {
+  const char* who = "debug_launch_mask_rec_inputs";
+  if (!logits || !f || !mask || !fin || ncalls < 0 || ncalls > 3) { set_error("%s: bad argument (ncalls 0..3)", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_pixels(who, 3 * p));
+  if (glue_misaligned(logits, 4) || glue_misaligned(mask, 4)) { set_error("%s: misaligned pointer", who); return UDET_ERR_ALIGN; }
+  UDET_TRY(glue_align(who, "f", f, 8));
+  UDET_TRY(glue_align(who, "fin", fin, 16));
+  return launch_mask_rec_inputs(logits, f, mask, fin, p, ncalls, (hipStream_t)stream);
+}
+int udet_debug_launch_pack_imgin(const float* img, float* imgin, long p, int ncalls, void* stream) {
+  const char* who = "debug_launch_pack_imgin";
+  if (!img || !imgin || ncalls < 0 || ncalls > 3) { set_error("%s: bad argument (ncalls 0..3)", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_pixels(who, 3 * p));
+  UDET_TRY(glue_align(who, "img", img, 4));
+  UDET_TRY(glue_align(who, "imgin", imgin, 16));
+  return launch_pack_imgin(img, imgin, p, ncalls, (hipStream_t)stream);
+}
+int udet_debug_launch_mask_bwd(const float* dmask, const float* dfin, const float* f, const float* mask, float* dlogits, long p, void* stream) {
+  const char* who = "debug_launch_mask_bwd";
+  if (!dmask || !dfin || !f || !mask || !dlogits) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  UDET_TRY(glue_pixels(who, 2 * p));
+  if (glue_misaligned(dmask, 4) || glue_misaligned(mask, 4) || glue_misaligned(dlogits, 4)) { set_error("%s: misaligned pointer", who); return UDET_ERR_ALIGN; }
+  UDET_TRY(glue_align(who, "dfin", dfin, 16));
+  UDET_TRY(glue_align(who, "f", f, 8));
+  return launch_mask_bwd(dmask, dfin, f, mask, dlogits, p, (hipStream_t)stream);
 }
 
 void udet_debug_set_tuning(int on) {

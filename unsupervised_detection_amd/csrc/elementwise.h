@@ -10,7 +10,6 @@ int launch_upb_ring_fold(const float* dxh, int ld, int N, int H, int W, float* d
 int launch_share_samples(float* buf, long P, int ld, int coff, int C, int copies, hipStream_t s);
 int launch_fold_samples(float* buf, long P, int ld, int coff, int C, int copies, hipStream_t s);
 int launch_emit_du(const float* d, const float* a, float* u, long P, int ld, int coff, int C, int act, float alpha, hipStream_t s);
-int launch_pool2x2_sum(const float* du, float* dx, int N, int H, int W, int C, hipStream_t s);
 int launch_pack_pwc_input(const float* i1, const float* i2, float* x8, long P, hipStream_t s);
 int launch_gen_input(const float* img, const float* f, double* part, float* gin, int B, long HW, hipStream_t s);
 size_t flow_stats_doubles(int B);
@@ -80,5 +79,4 @@ int launch_draw_track_boxes_ragged(unsigned char* rgb, int n, const long long* o
                                    const long long* counts, int k, const int* ids, int thickness, const unsigned* palette,
                                    int palette_size, hipStream_t s);
 int launch_fill_uniform(float* x, long n, uint64_t seed, float lo, float hi, hipStream_t s);
-int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s);
 }  // namespace udet

@@ -318,34 +318,8 @@ int launch_resize_bilinear_bwd(const float* dy, int ldy, int y_coff, int N, int 
   return UDET_OK;
 }
 
-// adjoint of resize_nearest_neighbor(x2, align_corners=True) == replicate: 2x2 sum
-__global__ __launch_bounds__(256) void pool2x2_sum_kernel(const float* __restrict__ du, float* __restrict__ dx, int N, int H,
-                                                          int W, int C) {
-  const int c4n = C >> 2;
-  const long total = (long)N * H * W * c4n;
-  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
-    const int c4 = (int)(e % c4n);
-    const long pix = e / c4n;
-    const int x = (int)(pix % W), y = (int)((pix / W) % H), n = (int)(pix / ((long)W * H));
-    const float* b = du + ((((long)n * 2 * H + 2 * y) * 2 * W) + 2 * x) * C + c4 * 4;
-    const float4 a0 = *reinterpret_cast<const float4*>(b), a1 = *reinterpret_cast<const float4*>(b + C);
-    const float4 a2 = *reinterpret_cast<const float4*>(b + (long)2 * W * C), a3 = *reinterpret_cast<const float4*>(b + (long)2 * W * C + C);
-    float4 o;
-    o.x = (a0.x + a1.x) + (a2.x + a3.x);
-    o.y = (a0.y + a1.y) + (a2.y + a3.y);
-    o.z = (a0.z + a1.z) + (a2.z + a3.z);
-    o.w = (a0.w + a1.w) + (a2.w + a3.w);
-    *reinterpret_cast<float4*>(dx + pix * C + c4 * 4) = o;
-  }
-}
-int launch_pool2x2_sum(const float* du, float* dx, int N, int H, int W, int C, hipStream_t s) {
-  hipLaunchKernelGGL(pool2x2_sum_kernel, dim3(grid_for((long)N * H * W * (C / 4))), dim3(256), 0, s, du, dx, N, H, W, C);
-  UDET_HIP(hipGetLastError());
-  return UDET_OK;
-}
-
 // u[p][coff+c] = d[p][coff+c] * act'(a[p][coff+c]), c < C: dU of a region whose gradient was finalised by a
-// non-convolution kernel (resize adjoint, 2x2 pooling)
+// non-convolution kernel (the resize adjoint)
 __global__ __launch_bounds__(256) void emit_du_kernel(const float* __restrict__ d, const float* __restrict__ a,
                                                       float* __restrict__ u, long P, int ld, int coff, int C, int act,
                                                       float alpha) {
@@ -971,17 +945,6 @@ int launch_upb_ring_fold(const float* dxh, int ld, int N, int H, int W, float* d
   if (H < 2 || W < 2) { set_error("upb_ring_fold: source grid must be at least 2x2"); return UDET_ERR_SHAPE; }
   const long total = (long)N * H * W * (ld / 4);
   hipLaunchKernelGGL(upb_ring_fold_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, s, dxh, ld, N, H, W, dx, ld / 4);
-  UDET_HIP(hipGetLastError());
-  return UDET_OK;
-}
-// y = a*x (+ y)   small helper for skip-gradients that need no conv
-__global__ __launch_bounds__(256) void axpy_kernel(const float* __restrict__ x, float* __restrict__ y, long n, float a,
-                                                   int accumulate) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-    y[i] = accumulate ? y[i] + a * x[i] : a * x[i];
-}
-int launch_axpy(const float* x, float* y, long n, float a, int accumulate, hipStream_t s) {
-  hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, n, a, accumulate);
   UDET_HIP(hipGetLastError());
   return UDET_OK;
 }
