@@ -122,6 +122,65 @@ int udet_debug_launch_gen_input(const float* img, const float* f, float* gin, in
 int udet_debug_launch_mask_rec_inputs(const float* logits, const float* f, float* mask, float* fin, long p, int ncalls, void* stream);
 int udet_debug_launch_pack_imgin(const float* img, float* imgin, long p, int ncalls, void* stream);
 int udet_debug_launch_mask_bwd(const float* dmask, const float* dfin, const float* f, const float* mask, float* dlogits, long p, void* stream);
+/* ---- One convolution launch exactly as a step plan builds it (tests/test_conv_epilogue_gpu.py) --------------------------------------------
+ * The single-operator entries of udet.h launch dense operands without epilogue options.  This entry takes what a plan's launches carry:
+ * channel windows on every operand, the gap map of the packed weights, residual / second output / accumulate / dU emission, act' on load
+ * and the two four-class forms of NN x2 + 3x3.  It lays a workspace out, packs the weights with the project's pack code (modes 0 / 1 with
+ * k_split / k_gap through either packer of a plan: launch_pack_weights, or with pack_job = 1 a job of launch_pack_jobs; jobs of modes 5 / 6), fills a ConvParams with the project's setup functions and calls launch_conv:
+ * nothing else.  udet_debug_force_conv / udet_debug_last_conv / udet_debug_conv_fp16(_grad_scale) act on it as on every launch; a forced
+ * Winograd family gets its transformed operand from the packed weights as the single-operator entries do.  The stream is synchronised
+ * before the entry returns, and an error of that synchronisation is the entry's (UDET_ERR_HIP).
+ *   form 0  forward: conv_setup_fwd on the (h << up) x (wd << up) grid; x [n,h,wd,ldx] (up = 1: read through the loader's NN x2), y on the SAME
+ *           output grid; pack mode 0 with the gap map: packed row r < k_split is input channel r, rows [k_split, k_split + k_gap) are zero,
+ *           row r beyond is channel r - k_gap.
+ *   form 1  backward-data of that convolution (up = 0): x = dy on the forward output grid, y = dx [n,h,wd,ldy]; conv_dgrad_classes launches of
+ *           conv_setup_dgrad (stride 2 on an odd grid: one per parity class), pack mode 1, kreal = cout; xa (layout of x) with xact != none:
+ *           x *= act'(xa) on load.  fp16 mode: f16_xscale = udet_debug_conv_fp16_grad_scale's value.
+ *   form 2  NN x2 + 3x3 SAME as four 2x2 convolutions on the low-resolution grid: setup_up_fwd, pack mode 5; x [n,h,wd,ldx], y [n,2h,2wd,ldy].
+ *   form 3  its backward-data pass: setup_up_dgrad, pack mode 6, kreal = cout; x = dU [n,2h,2wd,ldx], y = dx [n,h,wd,ldy].
+ * w: HWIO [k,k,cin,cout] in every form.  The launch reads x at channels [x_coff, x_coff + kc): kc is the K extent as a plan sets it (a
+ * multiple of 4, >= the real channels cin (forms 0 / 2) or cout (1 / 3) plus the gap); channels past the real ones and inside the gap meet zero
+ * weight rows and need only be finite.  With C = cout (forms 0 / 2) or cin (1 / 3) the launch writes y at [y_coff, y_coff + C) and nowhere
+ * else, in conv_epilogue's order:  v = act(conv + bias);  y2 <- v;  v += res;  v += old y (accumulate);  y <- v;
+ * u <- v * act'(ua) for columns [u_c0, u_c1), act' taken from the stored output (a > 0 ? 1 : leaky alpha / ELU a + 1 / none 1).  res, y2, uo
+ * and ua live on y's grid with their own ld / coff (column c of the launch at coff + c).  Backward forms take neither bias nor act.
+ * Every argument is checked before the first HIP call:  NULL x / w / y or args, counts < 1, k*k > 49, stride not 1 / 2, an unknown act or
+ * form, pack_job not 0 / 1, 4 n h wd >= 2^28, up / gap map outside form 0, xa outside form 1, bias or act on a backward form, uo without ua, a workspace that is NULL, not 64-byte aligned or smaller than
+ * udet_debug_conv2d_ex_workspace_bytes(args) -> UDET_ERR_ARG;  ldx, x_coff or kc not multiples of 4, x / xa not 16-byte aligned, any other
+ * pointer not 4-byte aligned -> UDET_ERR_ALIGN (the output side may be unaligned: the kernels then take their scalar store paths);  a
+ * window outside its row (x_coff + kc > ldx, real channels + gap > kc, y / res / y2 window, [u_c0, u_c1) outside [0, C] or the rows of
+ * uo / ua) -> UDET_ERR_SHAPE.
+ * Workspace (floats): zero block [0, 64), ticket counters, one pack job, from 4224 the packed weights, then 8 Mi floats of split-K slabs. */
+typedef struct udet_debug_conv_ex {
+  int form;
+  int n, h, wd, cin, cout, k, stride, dilation, up;
+  int kc, k_split, k_gap;
+  const float* x;
+  int ldx, x_coff;
+  const float* xa;
+  int xact;
+  float xalpha;
+  const float* w;
+  const float* bias;
+  int act;
+  float alpha;
+  float* y;
+  int ldy, y_coff;
+  const float* res;
+  int ldres, res_coff;
+  float* y2;
+  int ldy2, y2_coff;
+  int accumulate;
+  float* uo;
+  int ldu, u_coff;
+  const float* ua;
+  int ldua, ua_coff, uact;
+  float ualpha;
+  int u_c0, u_c1;
+  int pack_job; /* forms 0 / 1: 0 pack with launch_pack_weights, 1 with a pack job of mode 0 / 1 (launch_pack_jobs) */
+} udet_debug_conv_ex;
+size_t udet_debug_conv2d_ex_workspace_bytes(const udet_debug_conv_ex* args);
+int udet_debug_conv2d_ex(const udet_debug_conv_ex* args, void* workspace, size_t workspace_bytes, void* stream);
 /* (The experiment knobs of earlier rounds -- lane choices and the work-skipping ablation mask -- are no longer reachable from any library
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */

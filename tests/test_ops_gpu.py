@@ -351,7 +351,10 @@ WINO_CASES = [
 ]
 
 
-@pytest.mark.parametrize("variant,ks", [(0, 1), (1, 1), (0, 3), (1, 2), (2, 1), (3, 1), (2, 2), (3, 3), (4, 1), (4, 2)])
+WINO_PAIRS = [(0, 1), (1, 1), (0, 3), (1, 2), (2, 1), (3, 1), (2, 2), (3, 3), (4, 1), (4, 2)]  # (variant, K slices asked for)
+
+
+@pytest.mark.parametrize("variant,ks", WINO_PAIRS)
 @pytest.mark.parametrize("case", WINO_CASES)
 def test_conv_winograd_family(ops, force_conv, variant, ks, case):
     """3x3 stride-1 convolutions and their backward-data pass through the fused Winograd kernel (forward: pack mode 7 layout built

@@ -71,6 +71,51 @@ dbg.udet_debug_gen_input_workspace_bytes.restype = ctypes.c_size_t
 dbg.udet_debug_gen_input_workspace_bytes.argtypes = [_i]
 
 
+class ConvEx(ctypes.Structure):
+    """udet_debug_conv_ex (include/udet_debug.h): one convolution launch as a step plan builds it; unset fields are 0 / NULL."""
+    _fields_ = ([("form", _i)] + [(k, _i) for k in ("n", "h", "wd", "cin", "cout", "k", "stride", "dilation", "up", "kc", "k_split", "k_gap")]
+                + [("x", _p), ("ldx", _i), ("x_coff", _i), ("xa", _p), ("xact", _i), ("xalpha", _f), ("w", _p), ("bias", _p), ("act", _i),
+                   ("alpha", _f), ("y", _p), ("ldy", _i), ("y_coff", _i), ("res", _p), ("ldres", _i), ("res_coff", _i), ("y2", _p),
+                   ("ldy2", _i), ("y2_coff", _i), ("accumulate", _i), ("uo", _p), ("ldu", _i), ("u_coff", _i), ("ua", _p), ("ldua", _i),
+                   ("ua_coff", _i), ("uact", _i), ("ualpha", _f), ("u_c0", _i), ("u_c1", _i), ("pack_job", _i)])
+
+
+dbg.udet_debug_conv2d_ex_workspace_bytes.restype = ctypes.c_size_t
+dbg.udet_debug_conv2d_ex_workspace_bytes.argtypes = [ctypes.POINTER(ConvEx)]
+dbg.udet_debug_conv2d_ex.restype = ctypes.c_int
+dbg.udet_debug_conv2d_ex.argtypes = [ctypes.POINTER(ConvEx), _p, ctypes.c_size_t, _p]
+
+
+def conv2d_ex(workspace=None, stream=None, **fields):
+    """udet_debug_conv2d_ex with the struct's fields as keywords (tensors: their data pointers, or (tensor, element offset) for a pointer into
+    one); workspace: a float32 device tensor of conv2d_ex_workspace_bytes(**fields) bytes, or (pointer, bytes).  A refusal raises
+    ValueError (_ffi.check) before anything reaches the device; a pointer given as a plain int is passed as it is."""
+    a = conv_ex_args(**fields)
+    if workspace is None or isinstance(workspace, tuple):
+        ptr, nbytes = workspace or (None, 0)
+    else:
+        ptr, nbytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
+    _check(dbg.udet_debug_conv2d_ex(ctypes.byref(a), ptr, nbytes, stream))
+
+
+def conv_ex_args(**fields) -> ConvEx:
+    a = ConvEx()
+    for k, v in fields.items():
+        if isinstance(v, tuple):
+            v = v[0].data_ptr() + v[1] * v[0].element_size()
+        elif hasattr(v, "data_ptr"):
+            v = v.data_ptr()
+        setattr(a, k, v)
+    return a
+
+
+def conv2d_ex_workspace_bytes(**fields) -> int:
+    return int(dbg.udet_debug_conv2d_ex_workspace_bytes(ctypes.byref(conv_ex_args(**fields))))
+
+
 def launch(name: str, *args):
     """udet_debug_launch_<name>(*args, current stream) with tensors passed as their data pointers; a refusal raises ValueError
     (_ffi.check) before anything reaches the device."""

@@ -50,6 +50,7 @@ int wgrad_last_config();  // split count | variant << 20 of the most recent laun
 enum { WGRAD_RED_FUSED_BN = 1 << 26, WGRAD_RED_SEPARATE_BN = 1 << 27, WGRAD_RED_SWAPPED = 1 << 28, WGRAD_RED_CLASSES = 1 << 29 };
 int wgrad_last_reduce();
 void setup_up_fwd(ConvParams& p, int N, int H, int W);  // plan_exec.hip: NN x2 + 3x3 as four 2x2 convolutions on the low-resolution grid
+void setup_up_dgrad(ConvParams& p, int N, int H, int W);  // plan_exec.hip: its backward-data pass, one stride-2 walk over the full-resolution dU
 void wgrad_force(int nsplit, int dma);  // debug hook: nsplit > 0 pins the split count (clamped to the capacity), dma 0 / 1 / 2 the staging variant, 3 the Winograd-domain family where eligible (-1: as tuned)
 void conv_force_pair(int on);  // test hook: 1 = pair every compatible couple, 0 = never, -1 = as tuned / heuristic
 int conv_last_pair();          // 1: the most recent launch_conv_pair went out as ONE launch

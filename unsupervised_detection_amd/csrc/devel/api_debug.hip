@@ -261,6 +261,146 @@ int udet_debug_upconv_tables(int h, int w, int backward, int* nseg, int* seg, in
 }
 
 }  // extern "C"
+// ---- one convolution launch as a plan builds it (tests/test_conv_epilogue_gpu.py): channel windows on every operand, the gap map of the
+// packed weights, every epilogue option, the four-class up forms.  The parameter block comes from the project's own setup functions
+// (conv_setup_fwd / conv_setup_dgrad / setup_up_fwd / setup_up_dgrad), the weights from its own pack code; this file lays the workspace
+// out and checks arguments -- all of them before the first HIP call.
+namespace {
+enum { CEX_TICKETS = 64, CEX_JOB = CEX_TICKETS + UDET_MAX_TICKETS, CEX_W = CEX_JOB + 64 };
+const size_t CEX_SLAB_FLOATS = (size_t)8 << 20;  // split-K scratch, as the single-operator entry points of api.hip take it
+static_assert(CEX_W % 64 == 0 && sizeof(PackJob) <= 64 * sizeof(float), "workspace layout");
+bool cex_backward(int form) { return form == 1 || form == 3; }
+int cex_taps(const udet_debug_conv_ex& a) { return a.form >= 2 ? 16 : a.k * a.k; }
+size_t cex_weight_floats(const udet_debug_conv_ex& a) {
+  const int nout = cex_backward(a.form) ? a.cin : a.cout;
+  return upc_align64((size_t)cex_taps(a) * a.kc * round_up(nout, 4));
+}
+bool cex_known_act(int act) { return act == UDET_ACT_NONE || act == UDET_ACT_LEAKY || act == UDET_ACT_ELU; }
+// a window [coff, coff + c) of a row of ld floats
+bool cex_outside(int ld, int coff, int c) { return ld < 1 || coff < 0 || (long)coff + c > ld; }
+int cex_check(const udet_debug_conv_ex& a, const void* workspace, size_t workspace_bytes) {
+  const char* who = "debug_conv2d_ex";
+  if (a.form < 0 || a.form > 3) { set_error("%s: unknown form %d", who, a.form); return UDET_ERR_ARG; }
+  if (!a.x || !a.w || !a.y) { set_error("%s: x, w and y must not be NULL", who); return UDET_ERR_ARG; }
+  if (a.n < 1 || a.h < 1 || a.wd < 1 || a.cin < 1 || a.cout < 1 || a.k < 1 || a.k * a.k > UDET_MAX_TAPS || a.dilation < 1 ||
+      (a.stride != 1 && a.stride != 2) || a.kc < 1 || a.k_gap < 0 || a.k_split < 0 || (a.up != 0 && a.up != 1) ||
+      (a.accumulate != 0 && a.accumulate != 1) || (a.pack_job != 0 && a.pack_job != 1)) {
+    set_error("%s: bad count", who);
+    return UDET_ERR_ARG;
+  }
+  if ((long)a.n * (2L * a.h) * (2L * a.wd) >= (1L << 28)) { set_error("%s: grid too large", who); return UDET_ERR_ARG; }
+  if (!cex_known_act(a.act) || !cex_known_act(a.xact) || !cex_known_act(a.uact)) { set_error("%s: unknown act", who); return UDET_ERR_ARG; }
+  if (a.form != 0 && (a.up || a.k_gap || a.k_split != a.kc)) {
+    set_error("%s: the loader's NN x2 and the gap map belong to form 0 (elsewhere up = 0, k_gap = 0, k_split = kc)", who);
+    return UDET_ERR_ARG;
+  }
+  if (a.form >= 2 && (a.k != 3 || a.stride != 1 || a.dilation != 1)) { set_error("%s: forms 2 / 3 are NN x2 + 3x3 stride 1", who); return UDET_ERR_ARG; }
+  if (a.form == 0 && a.up && a.stride != 1) { set_error("%s: the loader's NN x2 goes with stride 1", who); return UDET_ERR_ARG; }
+  if (a.xa && a.form != 1) { set_error("%s: act' on load (xa) belongs to form 1", who); return UDET_ERR_ARG; }
+  if (cex_backward(a.form) ? (a.bias != nullptr || a.act != UDET_ACT_NONE) : false) {
+    set_error("%s: a backward-data launch has neither bias nor activation", who);
+    return UDET_ERR_ARG;
+  }
+  if (a.uo && !a.ua) { set_error("%s: uo needs ua", who); return UDET_ERR_ARG; }
+  // alignment: the A operand is read in float4 groups; every pointer holds floats
+  auto mis = [](const void* q, unsigned b) { return (reinterpret_cast<uintptr_t>(q) & (b - 1)) != 0; };
+  if (a.ldx % 4 || a.x_coff % 4 || a.kc % 4 || mis(a.x, 16) || (a.xa && mis(a.xa, 16))) {
+    set_error("%s: ldx=%d x_coff=%d kc=%d must be multiples of 4 and x / xa 16-byte aligned", who, a.ldx, a.x_coff, a.kc);
+    return UDET_ERR_ALIGN;
+  }
+  if (mis(a.w, 4) || mis(a.bias, 4) || mis(a.y, 4) || mis(a.res, 4) || mis(a.y2, 4) || mis(a.uo, 4) || mis(a.ua, 4)) {
+    set_error("%s: misaligned float pointer", who);
+    return UDET_ERR_ALIGN;
+  }
+  // windows
+  const int kreal = cex_backward(a.form) ? a.cout : a.cin, nout = cex_backward(a.form) ? a.cin : a.cout;
+  if (cex_outside(a.ldx, a.x_coff, a.kc)) { set_error("%s: x window %d+%d outside its row of %d", who, a.x_coff, a.kc, a.ldx); return UDET_ERR_SHAPE; }
+  if (kreal + a.k_gap > a.kc || (a.k_gap > 0 && a.k_split > kreal)) {
+    set_error("%s: %d real channels and a gap of %d at %d do not fit kc=%d", who, kreal, a.k_gap, a.k_split, a.kc);
+    return UDET_ERR_SHAPE;
+  }
+  if (cex_outside(a.ldy, a.y_coff, nout)) { set_error("%s: y window %d+%d outside its row of %d", who, a.y_coff, nout, a.ldy); return UDET_ERR_SHAPE; }
+  if (a.res && cex_outside(a.ldres, a.res_coff, nout)) { set_error("%s: res window outside its row", who); return UDET_ERR_SHAPE; }
+  if (a.y2 && cex_outside(a.ldy2, a.y2_coff, nout)) { set_error("%s: y2 window outside its row", who); return UDET_ERR_SHAPE; }
+  if (a.uo && (a.u_c0 < 0 || a.u_c1 < a.u_c0 || a.u_c1 > nout || a.u_coff < 0 || a.ua_coff < 0 || a.ldu < 1 || a.ldua < 1 ||
+               (long)a.u_coff + a.u_c1 > a.ldu || (long)a.ua_coff + a.u_c1 > a.ldua)) {
+    set_error("%s: emission columns [%d, %d) outside the launch's %d columns or the rows of uo / ua", who, a.u_c0, a.u_c1, nout);
+    return UDET_ERR_SHAPE;
+  }
+  if (!workspace || mis(workspace, 64) || workspace_bytes < udet_debug_conv2d_ex_workspace_bytes(&a)) {
+    set_error("%s: workspace must be 64-byte aligned and hold udet_debug_conv2d_ex_workspace_bytes", who);
+    return UDET_ERR_ARG;
+  }
+  return UDET_OK;
+}
+}  // namespace
+extern "C" {
+size_t udet_debug_conv2d_ex_workspace_bytes(const udet_debug_conv_ex* a) {
+  if (!a || a->form < 0 || a->form > 3 || a->kc < 1 || a->cin < 1 || a->cout < 1 || a->k < 1 || a->k * a->k > UDET_MAX_TAPS) return 0;
+  return (CEX_W + cex_weight_floats(*a) + CEX_SLAB_FLOATS) * sizeof(float);
+}
+int udet_debug_conv2d_ex(const udet_debug_conv_ex* args, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!args) { set_error("debug_conv2d_ex: bad argument"); return UDET_ERR_ARG; }
+  const udet_debug_conv_ex& a = *args;
+  UDET_TRY(cex_check(a, workspace, workspace_bytes));
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* wp = ws + CEX_W;
+  float* part = wp + cex_weight_floats(a);
+  const bool bwd = cex_backward(a.form);
+  const int nout = bwd ? a.cin : a.cout, ldw = round_up(nout, 4);
+  UDET_HIP(hipMemsetAsync(ws, 0, CEX_JOB * sizeof(float), stream));  // zero block + ticket counters
+  // the two packers of a plan: launch_pack_weights (pack_weights_kernel: the PWC-Net layers, packed once) and the per-step job table of the
+  // trainable networks (pack_jobs_kernel), which has its own copy of the gap map and the only form of modes 5 / 6
+  PackJob j;  // (a host temporary: the stream is synchronised below)
+  if (a.form < 2 && !a.pack_job) {
+    UDET_TRY(launch_pack_weights(a.w, wp, a.k * a.k, a.cin, a.cout, a.kc, ldw, a.k_split, a.k_gap, a.form, nullptr, stream));
+  } else {
+    memset(&j, 0, sizeof(j));
+    j.gamma_off = j.beta_off = -1;
+    j.dst_off = CEX_W; j.T = cex_taps(a); j.R = a.cin; j.C = a.cout; j.Kc = a.kc; j.ldw = ldw; j.k_split = a.k_split; j.k_gap = a.k_gap;
+    j.mode = a.form < 2 ? a.form : (a.form == 2 ? 5 : 6); j.total = (long)j.T * a.kc * ldw;
+    UDET_HIP(hipMemcpyAsync(ws + CEX_JOB, &j, sizeof(j), hipMemcpyHostToDevice, stream));
+    UDET_TRY(launch_pack_jobs(reinterpret_cast<const PackJob*>(ws + CEX_JOB), 1, a.w, ws, 1.f, stream));
+  }
+  int st = UDET_OK;
+  const int launches = a.form == 1 ? conv_dgrad_classes(a.stride, a.h, a.wd) : 1;
+  for (int cls = 0; cls < launches && st == UDET_OK; ++cls) {
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    if (a.form == 0) {
+      conv_setup_fwd(p, a.n, a.h << a.up, a.wd << a.up, a.k, a.k, a.stride, a.dilation);
+      p.up_shift = a.up;
+    } else if (a.form == 1) {
+      if (!conv_setup_dgrad(p, cls, a.n, a.h, a.wd, a.k, a.k, a.stride, a.dilation)) continue;
+    } else if (a.form == 2) {
+      setup_up_fwd(p, a.n, a.h, a.wd);
+    } else {
+      setup_up_dgrad(p, a.n, a.h, a.wd);
+    }
+    p.x = a.x; p.ldx = a.ldx; p.x_coff = a.x_coff;
+    if (a.xa && a.xact != UDET_ACT_NONE) { p.xa = a.xa; p.xact = a.xact; p.xalpha = a.xalpha; }
+    p.wp = wp; p.Kc = a.kc; p.ldw = ldw; p.bias = a.bias;
+    if (bwd) { p.kreal = a.cout; p.f16_xscale = conv_debug_f16_grad_scale_now(); }  // (the x operand is a gradient; 0: none)
+    p.y = a.y; p.ldy = a.ldy; p.y_coff = a.y_coff; p.Cout = nout;
+    p.act = a.act; p.alpha = a.alpha;
+    if (a.res) { p.res = a.res; p.ldres = a.ldres; p.res_coff = a.res_coff; }
+    if (a.y2) { p.y2 = a.y2; p.ldy2 = a.ldy2; p.y2_coff = a.y2_coff; }
+    p.accumulate = a.accumulate;
+    if (a.uo) {
+      p.uo = a.uo; p.ldu = a.ldu; p.u_coff = a.u_coff;
+      p.ua = a.ua; p.ldua = a.ldua; p.ua_coff = a.ua_coff;
+      p.uact = a.uact; p.ualpha = a.ualpha; p.u_c0 = a.u_c0; p.u_c1 = a.u_c1;
+    }
+    p.partial = part; p.partial_cap = CEX_SLAB_FLOATS;
+    p.zero16 = ws; p.tickets = reinterpret_cast<int*>(ws + CEX_TICKETS);
+    st = launch_conv(p, stream);
+  }
+  const hipError_t e = hipStreamSynchronize(stream);  // (a fault in the launch is this call's error, not the caller's next one)
+  if (st == UDET_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(stream)");
+  return st;
+}
+}  // extern "C"
 // ---- the glue launchers of elementwise.hip, one launch each (tests/test_glue_gpu.py): argument checks, then the launcher ---------------------
 namespace {
 const long GLUE_MAX_PIXELS = 1L << 31;

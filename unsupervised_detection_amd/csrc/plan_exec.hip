@@ -65,7 +65,7 @@ void setup_up_fwd(ConvParams& p, int N, int H, int W) {
   p.cls_tap[4] = 16;
 }
 // backward-data: dX[q] = sum_{class, tap} dU[2(q - d) + p] Weff[class][tap]^T -- a stride-2 walk over the full-resolution dU
-static void setup_up_dgrad(ConvParams& p, int N, int H, int W) {
+void setup_up_dgrad(ConvParams& p, int N, int H, int W) {
   p.N = N; p.H = 2 * H; p.W = 2 * W;
   p.OH = H; p.OW = W; p.OHq = H; p.OWq = W;
   p.osy = p.osx = 1; p.ooy = p.oox = 0; p.isy = p.isx = 2;
