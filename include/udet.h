@@ -290,6 +290,54 @@ int udet_link_detections_gap_ragged(const int* labels, int n, const long long* o
                                     int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* One packed integer displacement per pixel of a ragged batch from a batch of flow fields of one common size: what the
+ * motion link below reads.  flow: device float32 [n][fh][fw][2], (u, v) in flow-grid pixels, row i from frame i to the frame before it
+ * (the convention of flow_prev in udet_post_propagate_sequences).  offsets / hw / max_h / max_w / total_pixels: the packed layout of the
+ * link entries.  disp: device int32 [total_pixels]; sample i's H x W values at offsets[i]; dx in the low 16 bits, dy in the high 16, both
+ * signed.  For pixel (x, y) of a sample H x W, in float32 with every operation rounded once and nothing fused:
+ *  - rx = fw / W, ry = fh / H, sx = W / fw, sy = H / fh (one division each, of the integers as floats).
+ *  - gx = ((float)x + 0.5f) * rx - 0.5f, clamped to [0, fw - 1]; x0 = (int)floorf(gx), x1 = min(x0 + 1, fw - 1), ax = gx - (float)x0;
+ *    gy, y0, y1 and ay from y, ry and fh in the same way.
+ *  - per channel, with f00 = flow[i][y0][x0], f01 = flow[i][y0][x1], f10 = flow[i][y1][x0], f11 = flow[i][y1][x1]:
+ *    top = f00 + ax * (f01 - f00), bot = f10 + ax * (f11 - f10), val = top + ay * (bot - top).
+ *  - dx = rint(u * sx) and dy = rint(v * sy), ties to even; a NaN gives 0; the result is clamped to -32768 .. 32767.
+ * One launch, one pixel per lane, a wave on 64 consecutive pixels of one sample; no LDS, no atomics, no workspace; disp is written as
+ * aligned 32-bit stores and nothing else is written: identical from run to run and for a sample alone or inside a batch.
+ * UDET_ERR_ARG, nothing enqueued: a NULL pointer, n outside 1..65535, max_h or max_w < 1, total_pixels < 1, fh or fw outside 1..32767,
+ * flow not 8-byte or disp not 4-byte aligned.  The tables are device memory: the host caller validates them
+ * (native_motion.flow_displacements); the taps are clamped to the grid, so nothing indexes outside flow whatever it holds. */
+int udet_flow_displacements_ragged(const float* flow, int n, int fh, int fw, const long long* offsets, const int* hw, int max_h, int max_w,
+                                   size_t total_pixels, int* disp, void* stream);
+
+/* udet_link_detections_ragged and udet_link_detections_gap_ragged with motion compensation: the predecessor's labels are
+ * read where a displacement says each pixel came from.  Every argument is the co-located entry's; disp: device int32 [total_pixels],
+ * packed like labels, dx in the low 16 bits and dy in the high 16, both signed (udet_flow_displacements_ragged writes it; any other source
+ * will do).  Everything the co-located entries define holds, with one change: inter[c][a][b] counts the positions (x, y) of frame c
+ * where labels_c(x, y) = root_b + 1, the source (x + dx, y + dy) with (dx, dy) = disp_c(x, y) lies inside the H x W frame, and
+ * labels_p(x + dx, y + dy) = root_a + 1.  A position whose source lies outside the frame contributes nothing; disp of a frame that is not
+ * linked is not read; for frame 0 the predecessor is the carried frame (the history's newest frame) and the displacement is frame 0's
+ * own, so nothing new is carried between calls.  Areas, the candidate rule, the threshold, the greedy order, the ids and seq_tracks are
+ * unchanged: every pixel of b is counted at most once, so inter <= area_b and the union stays positive, while inter may exceed area_a
+ * where the displacements map many pixels onto one (inter / union may then exceed 1).  In the gap entry only stage 1 is warped:
+ * gap_inter at distances d >= 2 stays co-located.  With disp all zero every output equals the co-located entry's, entry for entry.
+ * The launches are the co-located entries' four and six, the overlap pass of stage 1 in its motion form (one more coalesced 32-bit load
+ * per pixel, a 2-D bounds test, then the predecessor's label gathered at (y + dy) W + x + dx); the workspaces are those of
+ * udet_link_detections_workspace_bytes and udet_link_detections_gap_workspace_bytes.  UDET_ERR_ARG, nothing enqueued: everything the
+ * co-located entry refuses, and a NULL or misaligned disp.  Every index a kernel forms is bounded whatever disp holds. */
+int udet_link_detections_motion_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                       size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                       const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                       const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                       long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, const int* disp,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+int udet_link_detections_gap_motion_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                           size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                           int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                           const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                           int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                           int* next_id, long long* gap_inter, int* back, int* prev, int* open, const int* disp,
+                                           void* workspace, size_t workspace_bytes, void* stream);
+
 /* The boxes of the written detections painted in the colour of their track, in place: the contract of udet_draw_boxes_ragged with two
  * differences.  The colour of row r of sample i is palette[ids[i][r] mod palette_size] (ids: device int32 [n][k], what
  * udet_link_detections_ragged wrote; palette: device uint32 [palette_size], 0xRRGGBB, palette_size in 1..UDET_TRACK_MAX_PALETTE), and a

@@ -87,6 +87,12 @@ sig("udet_link_detections_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p,
 sig("udet_link_detections_gap_workspace_bytes", c_sz, c_sz, c_i, c_i, c_i, c_i, c_i, c_i)
 sig("udet_link_detections_gap_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p,
     c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
+# motion-compensated linking (native_motion.flow_displacements, native_tracks.link_detections(disp=...)): disp before the workspace
+sig("udet_flow_displacements_ragged", c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p)
+sig("udet_link_detections_motion_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i,
+    c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
+sig("udet_link_detections_gap_motion_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p,
+    c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
 sig("udet_draw_track_boxes_ragged", c_i, c_p, c_i, c_p, c_p, c_sz, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p)
 # per-track instance maps and their picture (native_instances.instance_maps, visualize.overlay_instances)
 sig("udet_track_instance_maps_workspace_bytes", c_sz, c_sz, c_i, c_i)

@@ -16,6 +16,7 @@
                                                       [--detections] [--det_min_area 64] [--det_max 16]     (no reference script)
                                                       [--overlay_boxes] [--overlay_box_thickness 2] [--overlay_box_colour 255,255,0]
                                                       [--tracks] [--track_min_iou 0.1] [--track_max_gap 0]
+                                                      [--track_motion] [--track_motion_size 384 640]
                                                       [--instances] [--overlay_instances]
                                                       [--follow none|mass|area|length|best_gt|all] [--track_min_frames 1]
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
@@ -76,7 +77,10 @@ shares the largest IoU, at least --track_min_iou (0.1) -- and numbers the tracks
 (native_results.link_detections, visualize.draw_track_boxes).  --track_max_gap G (needs --tracks; 0..8, default 0: off) lets a box
 without a predecessor in the frame before it continue a track whose component was missing for up to G frames, by the same IoU rule
 against that track's last-seen component: the object keeps its id and its colour, the records gain back, the tracks span / gaps and
-the sequences bridged.  --instances (needs --tracks) hands the tracks to the pixels: <out>/instances/<sequence>/<frame>.png is an indexed
+the sequences bridged.  --track_motion (needs --tracks) links along the optical flow: every pixel of a frame is compared with the pixel
+of the frame before it that the backward PWC flow, computed at --track_motion_size FH FW (multiples of 64, default 384 640), says it
+came from, so an object that moves further than its own extent between two frames keeps its id (native_motion.flow_displacements,
+DESIGN.md 7.12); native_eval.json gains track_motion.  --instances (needs --tracks) hands the tracks to the pixels: <out>/instances/<sequence>/<frame>.png is an indexed
 PNG at the frame's own size in which a pixel's value names its track (0 background, 1 + id mod 252 a tracked component in its track's
 colour, 255 foreground without a track), the tracks of <out>/tracks/<sequence>.json gain gt_j_mean -- the mean J of that one track
 against the annotation over all frames of its sequence -- and the sequences best_track, and native_eval.json reports unassigned_mean,
@@ -195,6 +199,10 @@ def _add_overlay_arguments(ap):
     ap.add_argument("--track_min_iou", type=float, default=0.1, help="the smallest mask IoU that links two boxes")
     ap.add_argument("--track_max_gap", type=int, default=0,
                     help="with --tracks: a box may continue a track whose component was missing for up to this many frames (0..8; 0: none)")
+    ap.add_argument("--track_motion", action="store_true",
+                    help="with --tracks: link along the optical flow between the frames, so that fast small objects keep their id")
+    ap.add_argument("--track_motion_size", type=int, nargs=2, default=(384, 640), metavar=("FH", "FW"),
+                    help="with --track_motion: the size the flow is computed at, two multiples of 64")
     ap.add_argument("--instances", action="store_true",
                     help="with --tracks: write every frame's instance map, <out>/instances/<sequence>/<frame>.png, and score every track")
     ap.add_argument("--overlay_instances", action="store_true",
@@ -244,18 +252,23 @@ def _detections(flags):
 def _tracks(flags):
     """--tracks and its parameter as restore_results_dir takes them: None without --tracks.  --tracks without --detections, or a bad
     value, is a SystemExit."""
-    gap = getattr(flags, "track_max_gap", 0)
+    gap, motion = getattr(flags, "track_max_gap", 0), getattr(flags, "track_motion", False)
+    size = tuple(getattr(flags, "track_motion_size", (384, 640)))
     if not getattr(flags, "tracks", False):
         if gap:
             raise SystemExit("--track_max_gap bridges the frames in which a track's component is missing: it needs --tracks")
+        if motion or size != (384, 640):
+            raise SystemExit("--track_motion links the detections along the optical flow: it needs --tracks")
         return None
     if not getattr(flags, "detections", False):
         raise SystemExit("--tracks links the detections of consecutive frames: it needs --detections")
+    if size != (384, 640) and not motion:
+        raise SystemExit("--track_motion_size is the size the flow of --track_motion is computed at: it needs --track_motion")
     from .native_tracks import track_params
     try:
-        return track_params({"min_iou": flags.track_min_iou, "max_gap": gap})
+        return track_params(dict({"min_iou": flags.track_min_iou, "max_gap": gap}, **({"motion": {"size": size}} if motion else {})))
     except ValueError as e:
-        raise SystemExit("--tracks: {} (--track_min_iou / --track_max_gap)".format(e))
+        raise SystemExit("--tracks: {} (--track_min_iou / --track_max_gap / --track_motion_size)".format(e))
 
 
 def _instances(flags):

@@ -70,6 +70,10 @@ _DEFS = [
     ("track_min_iou", float, 0.1),
     # ... and a box may continue a track whose component was missing for up to track_max_gap frames (0..8, 0: off)
     ("track_max_gap", int, 0),
+    # ... and track_motion links along the optical flow between the frames, computed at track_motion_size (fh fw, multiples of 64;
+    # DESIGN.md 7.12): an object that moves further than its own extent between two frames keeps its id
+    ("track_motion", bool, False),
+    ("track_motion_size", int, (384, 640)),
     # not reference flags: with --tracks, --instances writes every frame's instance map (an indexed PNG, a pixel's value names its track) into
     # D/native/instances/<sequence>/ and scores every track against the annotation; --overlay_instances (with --overlay) draws the maps, every
     # track in its colour, in the place of the single mask (native_results.instance_maps, visualize.overlay_instances)
@@ -91,6 +95,8 @@ def parse_flags(argv=None):
     for k, t, v in _DEFS:
         if t is bool:
             ap.add_argument("--" + k, type=lambda s: s.lower() in ("1", "true", "yes"), default=v, nargs="?", const=True)
+        elif isinstance(v, tuple):  # a fixed number of values: --track_motion_size 384 640
+            ap.add_argument("--" + k, type=t, nargs=len(v), default=v)
         else:
             ap.add_argument("--" + k, type=t, default=v)
     return ap.parse_args(argv)

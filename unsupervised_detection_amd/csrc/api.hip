@@ -219,28 +219,33 @@ size_t udet_link_detections_workspace_bytes(size_t total_pixels, int n, int k, i
   if (carry && (carry_h < 1 || carry_w < 1 || (long)carry_h * carry_w > 0x7fffffffL)) return 0;
   return link_detections_workspace_bytes(total_pixels, carry_h, carry_w);
 }
-int udet_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
-                                size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
-                                const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
-                                const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
-                                long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
-                                size_t workspace_bytes, void* stream) {
-  if (bad_batch("link_detections_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+// udet_link_detections_ragged (disp = nullptr, motion = false) and udet_link_detections_motion_ragged: the same checks under the entry's name
+static int link_detections_checked(const char* fn, bool motion, const int* labels, int n, const long long* offsets, const int* hw, int max_h,
+                                   int max_w, size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                   const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                   const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                   long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, const int* disp,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (bad_batch(fn, n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (motion && (!disp || (reinterpret_cast<uintptr_t>(disp) & 3))) {
+    set_error("%s: disp must be a non-null, 4-byte aligned int32 buffer of total_pixels elements", fn);
+    return UDET_ERR_ARG;
+  }
   if (!labels || !offsets || !hw || !dets || !counts || !link || !inter || !match || !ids || !linked || !seq_tracks || !next_id) {
-    set_error("link_detections_ragged: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)");
+    set_error("%s: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)", fn);
     return UDET_ERR_ARG;
   }
   if (k < 1 || k > UDET_DET_MAX_K || min_iou_permille < 1 || min_iou_permille > 1000) {
-    set_error("link_detections_ragged: k = %d in 1..UDET_DET_MAX_K = %d and min_iou_permille = %d in 1..1000 are required", k,
+    set_error("%s: k = %d in 1..UDET_DET_MAX_K = %d and min_iou_permille = %d in 1..1000 are required", fn, k,
               UDET_DET_MAX_K, min_iou_permille);
     return UDET_ERR_ARG;
   }
   if (!link_carry_ok(carry_labels, carry_h, carry_w, carry_dets, carry_counts, carry_ids, carry_next_id)) {
-    set_error("link_detections_ragged: the carried frame is either absent (no pointer, 0 x 0) or whole (labels, dets, counts, ids and "
-              "next id, %d x %d at least 1 x 1 and below 2^31 pixels)", carry_h, carry_w);
+    set_error("%s: the carried frame is either absent (no pointer, 0 x 0) or whole (labels, dets, counts, ids and "
+              "next id, %d x %d at least 1 x 1 and below 2^31 pixels)", fn, carry_h, carry_w);
     return UDET_ERR_ARG;
   }
-  if (bad_workspace("link_detections_ragged", workspace, workspace_bytes, link_detections_workspace_bytes(total_pixels, carry_h, carry_w), 4))
+  if (bad_workspace(fn, workspace, workspace_bytes, link_detections_workspace_bytes(total_pixels, carry_h, carry_w), 4))
     return UDET_ERR_ARG;
   const uintptr_t a4 = reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(link) | reinterpret_cast<uintptr_t>(carry_labels) |
                        reinterpret_cast<uintptr_t>(carry_ids) | reinterpret_cast<uintptr_t>(carry_next_id) |
@@ -249,12 +254,32 @@ int udet_link_detections_ragged(const int* labels, int n, const long long* offse
   const uintptr_t a8 = reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(carry_dets) |
                        reinterpret_cast<uintptr_t>(carry_counts) | reinterpret_cast<uintptr_t>(inter);
   if ((a4 & 3) || (a8 & 7)) {
-    set_error("link_detections_ragged: the int32 buffers must be 4-byte aligned, dets, counts and inter 8-byte aligned");
+    set_error("%s: the int32 buffers must be 4-byte aligned, dets, counts and inter 8-byte aligned", fn);
     return UDET_ERR_ARG;
   }
   return launch_link_detections_ragged(labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k, link, carry_labels, carry_h,
                                        carry_w, carry_dets, carry_counts, carry_ids, carry_next_id, min_iou_permille, inter, match, ids,
-                                       linked, seq_tracks, next_id, workspace, (hipStream_t)stream);
+                                       linked, seq_tracks, next_id, disp, workspace, (hipStream_t)stream);
+}
+int udet_link_detections_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  return link_detections_checked("link_detections_ragged", false, labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k, link,
+                                 carry_labels, carry_h, carry_w, carry_dets, carry_counts, carry_ids, carry_next_id, min_iou_permille, inter,
+                                 match, ids, linked, seq_tracks, next_id, nullptr, workspace, workspace_bytes, stream);
+}
+int udet_link_detections_motion_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                       size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                       const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
+                                       const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
+                                       long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, const int* disp,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return link_detections_checked("link_detections_motion_ragged", true, labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k,
+                                 link, carry_labels, carry_h, carry_w, carry_dets, carry_counts, carry_ids, carry_next_id, min_iou_permille,
+                                 inter, match, ids, linked, seq_tracks, next_id, disp, workspace, workspace_bytes, stream);
 }
 
 // the history of udet_link_detections_gap_ragged: absent (no pointer, m = 0, 0 x 0) or whole (every pointer, 1..max_gap + 1 frames of at
@@ -271,31 +296,36 @@ size_t udet_link_detections_gap_workspace_bytes(size_t total_pixels, int n, int 
     return 0;
   return link_detections_gap_workspace_bytes(total_pixels, m, hist_h, hist_w);
 }
-int udet_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
-                                    size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
-                                    int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
-                                    const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
-                                    int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
-                                    int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-  if (bad_batch("link_detections_gap_ragged", n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+// udet_link_detections_gap_ragged (disp = nullptr, motion = false) and udet_link_detections_gap_motion_ragged
+static int link_detections_gap_checked(const char* fn, bool motion, const int* labels, int n, const long long* offsets, const int* hw,
+                                       int max_h, int max_w, size_t total_pixels, const long long* dets, const long long* counts, int k,
+                                       const int* link, int max_gap, int m, const int* hist_labels, int hist_h, int hist_w,
+                                       const long long* hist_dets, const long long* hist_counts, const int* hist_ids, int* hist_open,
+                                       const int* hist_next_id, int min_iou_permille, long long* inter, int* match, int* ids, int* linked,
+                                       int* seq_tracks, int* next_id, long long* gap_inter, int* back, int* prev, int* open, const int* disp,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  if (bad_batch(fn, n, max_h, max_w, total_pixels)) return UDET_ERR_ARG;
+  if (motion && (!disp || (reinterpret_cast<uintptr_t>(disp) & 3))) {
+    set_error("%s: disp must be a non-null, 4-byte aligned int32 buffer of total_pixels elements", fn);
+    return UDET_ERR_ARG;
+  }
   if (!labels || !offsets || !hw || !dets || !counts || !link || !inter || !match || !ids || !linked || !seq_tracks || !next_id ||
       !gap_inter || !back || !prev || !open) {
-    set_error("link_detections_gap_ragged: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)");
+    set_error("%s: bad argument (non-null labels, offsets, hw, dets, counts, link and outputs)", fn);
     return UDET_ERR_ARG;
   }
   if (k < 1 || k > UDET_DET_MAX_K || min_iou_permille < 1 || min_iou_permille > 1000 || max_gap < 1 || max_gap > UDET_TRACK_MAX_GAP) {
-    set_error("link_detections_gap_ragged: k = %d in 1..UDET_DET_MAX_K = %d, min_iou_permille = %d in 1..1000 and max_gap = %d in "
-              "1..UDET_TRACK_MAX_GAP = %d are required", k, UDET_DET_MAX_K, min_iou_permille, max_gap, UDET_TRACK_MAX_GAP);
+    set_error("%s: k = %d in 1..UDET_DET_MAX_K = %d, min_iou_permille = %d in 1..1000 and max_gap = %d in "
+              "1..UDET_TRACK_MAX_GAP = %d are required", fn, k, UDET_DET_MAX_K, min_iou_permille, max_gap, UDET_TRACK_MAX_GAP);
     return UDET_ERR_ARG;
   }
   if (!link_history_ok(max_gap, m, hist_labels, hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id)) {
-    set_error("link_detections_gap_ragged: the history is either absent (no pointer, m = 0, 0 x 0) or whole (labels, dets, counts, ids, "
-              "open and next id; m = %d in 1..max_gap + 1 = %d frames of %d x %d, at least 1 x 1 and below 2^31 pixels)", m, max_gap + 1,
+    set_error("%s: the history is either absent (no pointer, m = 0, 0 x 0) or whole (labels, dets, counts, ids, "
+              "open and next id; m = %d in 1..max_gap + 1 = %d frames of %d x %d, at least 1 x 1 and below 2^31 pixels)", fn, m, max_gap + 1,
               hist_h, hist_w);
     return UDET_ERR_ARG;
   }
-  if (bad_workspace("link_detections_gap_ragged", workspace, workspace_bytes,
+  if (bad_workspace(fn, workspace, workspace_bytes,
                     link_detections_gap_workspace_bytes(total_pixels, m, hist_h, hist_w), 4))
     return UDET_ERR_ARG;
   const uintptr_t a4 = reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(link) | reinterpret_cast<uintptr_t>(hist_labels) |
@@ -306,14 +336,39 @@ int udet_link_detections_gap_ragged(const int* labels, int n, const long long* o
   const uintptr_t a8 = reinterpret_cast<uintptr_t>(dets) | reinterpret_cast<uintptr_t>(counts) | reinterpret_cast<uintptr_t>(hist_dets) |
                        reinterpret_cast<uintptr_t>(hist_counts) | reinterpret_cast<uintptr_t>(inter) | reinterpret_cast<uintptr_t>(gap_inter);
   if ((a4 & 3) || (a8 & 7)) {
-    set_error("link_detections_gap_ragged: the int32 buffers must be 4-byte aligned, dets, counts, inter and gap_inter 8-byte aligned");
+    set_error("%s: the int32 buffers must be 4-byte aligned, dets, counts, inter and gap_inter 8-byte aligned", fn);
     return UDET_ERR_ARG;
   }
   return launch_link_detections_gap_ragged(labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k, link, max_gap, m, hist_labels,
                                            hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id, min_iou_permille, inter,
-                                           match, ids, linked, seq_tracks, next_id, gap_inter, back, prev, open, workspace,
+                                           match, ids, linked, seq_tracks, next_id, gap_inter, back, prev, open, disp, workspace,
                                            (hipStream_t)stream);
 }
+int udet_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                    size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                    int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                    const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                    int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                    int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  return link_detections_gap_checked("link_detections_gap_ragged", false, labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts, k,
+                                     link, max_gap, m, hist_labels, hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id,
+                                     min_iou_permille, inter, match, ids, linked, seq_tracks, next_id, gap_inter, back, prev, open, nullptr,
+                                     workspace, workspace_bytes, stream);
+}
+int udet_link_detections_gap_motion_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                           size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
+                                           int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
+                                           const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
+                                           int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
+                                           int* next_id, long long* gap_inter, int* back, int* prev, int* open, const int* disp,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  return link_detections_gap_checked("link_detections_gap_motion_ragged", true, labels, n, offsets, hw, max_h, max_w, total_pixels, dets,
+                                     counts, k, link, max_gap, m, hist_labels, hist_h, hist_w, hist_dets, hist_counts, hist_ids, hist_open,
+                                     hist_next_id, min_iou_permille, inter, match, ids, linked, seq_tracks, next_id, gap_inter, back, prev,
+                                     open, disp, workspace, workspace_bytes, stream);
+}
+
 
 int udet_draw_track_boxes_ragged(unsigned char* image_rgb, int n, const long long* offsets, const int* hw, size_t total_pixels,
                                  const long long* dets, const long long* counts, int k, const int* ids, int thickness,

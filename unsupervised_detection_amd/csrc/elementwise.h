@@ -65,16 +65,16 @@ int launch_link_detections_ragged(const int* labels, int n, const long long* off
                                   size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
                                   const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
                                   const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
-                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
-                                  hipStream_t s);
+                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, const int* disp,
+                                  void* workspace, hipStream_t s);  // disp: nullptr, or the motion link's displacements
 size_t link_detections_gap_workspace_bytes(size_t total_pixels, int m, int hist_h, int hist_w);
 int launch_link_detections_gap_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
                                       size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
                                       int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
                                       const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
                                       int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
-                                      int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
-                                      hipStream_t s);
+                                      int* next_id, long long* gap_inter, int* back, int* prev, int* open, const int* disp,
+                                      void* workspace, hipStream_t s);
 int launch_draw_track_boxes_ragged(unsigned char* rgb, int n, const long long* offsets, const int* hw, const long long* dets,
                                    const long long* counts, int k, const int* ids, int thickness, const unsigned* palette,
                                    int palette_size, hipStream_t s);

@@ -18,6 +18,8 @@
 // sample whatever labels and dets hold; every other index comes from offsets / hw, which the caller validates on the host
 // (native_results.link_detections), and from ranks clamped to k.  udet_link_detections_gap_ragged (below the four
 // kernels) adds the bridge across frames in which a component is missing: six launches, the same properties.
+// udet_link_detections_motion_ragged / udet_link_detections_gap_motion_ragged are the same launches with the overlap pass
+// of stage 1 in its MOTION form: the predecessor's label is read where a per-pixel displacement (csrc/motion.hip) says the pixel came from.
 #include "common.h"
 #include "elementwise.h"
 #include "track_rows.h"  // link_rows, link_enter_roots: shared with instances.hip
@@ -73,7 +75,12 @@ struct LinkSide {
   size_t at;
 };
 
-__device__ __forceinline__ void link_overlap_pass(LinkSide fp, LinkSide fc, int W, long long HW, int k, const int* __restrict__ lookup,
+// MOTION: the predecessor's label is read where disp says the pixel came from -- dx in the low 16 bits, dy in the high
+// 16, both signed; the source is tested in 2-D against the H x W frame before it becomes an address, and a source outside the frame is
+// background.  Without MOTION disp and H are not looked at and the pass is what it was.
+template <bool MOTION>
+__device__ __forceinline__ void link_overlap_pass(LinkSide fp, LinkSide fc, int H, int W, long long HW, int k,
+                                                  const int* __restrict__ lookup, const int* __restrict__ disp,
                                                   unsigned long long* __restrict__ out, int* __restrict__ lds) {
   const int t = threadIdx.x, lane = t & 63;
   int* __restrict__ hist = lds;  // hist [k * k], root_p [k], root_c [k]
@@ -92,7 +99,18 @@ __device__ __forceinline__ void link_overlap_pass(LinkSide fp, LinkSide fc, int 
   for (long long base = (long long)blockIdx.x * 256; base < HW; base += (long long)gridDim.x * 256) {  // block-uniform bounds
     const long long p = base + t;
     const bool valid = p < HW;
-    const int vp = valid ? lab_p[p] : 0, vc = valid ? lab_c[p] : 0;
+    int vp = 0;
+    const int vc = valid ? lab_c[p] : 0;
+    if (MOTION) {
+      if (valid) {
+        const int dv = disp[p];
+        const long long y = p / W;
+        const long long xs = (p - y * W) + (short)(dv & 0xffff), ys = y + (dv >> 16);  // |dx|, |dy| <= 2^15: no overflow
+        if (xs >= 0 && xs < W && ys >= 0 && ys < H) vp = lab_p[ys * W + xs];           // 0 <= ys W + xs < HW
+      }
+    } else {
+      vp = valid ? lab_p[p] : 0;
+    }
     int a = -1, b = -1;
     if (vp >= 1 && vp <= HW && vc >= 1 && vc <= HW) {
       const int ra = lookup[op + vp - 1], rb = lookup[oc + vc - 1];  // never zeroed: only a rank whose row holds this root counts
@@ -108,11 +126,13 @@ __device__ __forceinline__ void link_overlap_pass(LinkSide fp, LinkSide fc, int 
     if (hist[j]) atomicAdd(out + j, (unsigned long long)hist[j]);
 }
 
+// disp: one packed displacement per pixel of the batch, laid out like labels (MOTION only; a frame that is not linked reads none of it).
+template <bool MOTION>
 __global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict__ labels, const long long* __restrict__ offsets,
                                                            const int* __restrict__ hw, size_t total_pixels,
                                                            const long long* __restrict__ dets, const long long* __restrict__ counts, int k,
                                                            LinkCarry carry, const int* __restrict__ linked, const int* __restrict__ lookup,
-                                                           unsigned long long* __restrict__ inter) {
+                                                           const int* __restrict__ disp, unsigned long long* __restrict__ inter) {
   extern __shared__ int link_lds[];
   const int i = blockIdx.y;
   if (!linked[i]) return;  // block-uniform; a linked frame 0 has a carried frame of its size
@@ -123,7 +143,7 @@ __global__ __launch_bounds__(256) void link_overlap_kernel(const int* __restrict
   const LinkSide fp = i ? LinkSide{labels + offsets[i - 1], dets_c - (size_t)k * UDET_DET_FIELDS, link_rows(counts + 3 * i - 3, k),
                                    (size_t)offsets[i - 1]}
                         : LinkSide{carry.labels, carry.dets, link_rows(carry.counts, k), total_pixels};
-  link_overlap_pass(fp, fc, W, HW, k, lookup, inter + (size_t)i * k * k, link_lds);
+  link_overlap_pass<MOTION>(fp, fc, hw[2 * i], W, HW, k, lookup, MOTION ? disp + offsets[i] : nullptr, inter + (size_t)i * k * k, link_lds);
 }
 
 // (inter, union, entry) of the better of two candidates: the larger inter / union by 64-bit cross-multiplication (inter < 2^31, union <
@@ -249,18 +269,19 @@ int launch_link_detections_ragged(const int* labels, int n, const long long* off
                                   size_t total_pixels, const long long* dets, const long long* counts, int k, const int* link,
                                   const int* carry_labels, int carry_h, int carry_w, const long long* carry_dets,
                                   const long long* carry_counts, const int* carry_ids, const int* carry_next_id, int min_iou_permille,
-                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, void* workspace,
-                                  hipStream_t s) {
+                                  long long* inter, int* match, int* ids, int* linked, int* seq_tracks, int* next_id, const int* disp,
+                                  void* workspace, hipStream_t s) {
   const long nb = ((long)max_h * max_w + 256 * LINK_PPT - 1) / (256 * LINK_PPT);
   if (nb > 0x7fffffffL) { set_error("link_detections_ragged: frame too large"); return UDET_ERR_SHAPE; }
   const LinkCarry carry = {carry_labels, carry_dets, carry_counts, carry_ids, carry_next_id, carry_h, carry_w};
   int* lookup = (int*)workspace;
+  const auto overlap = disp ? link_overlap_kernel<true> : link_overlap_kernel<false>;  // disp = nullptr: the co-located link
   const size_t nz = ((size_t)n * k * k + 255) / 256;
   const size_t lds_overlap = ((size_t)k * k + 2 * k) * sizeof(int), lds_match = (2 * (size_t)k * k + 3 * k) * sizeof(int);
   hipLaunchKernelGGL(link_init_kernel, dim3((unsigned)(nz > 65536 ? 65536 : nz)), dim3(256), 0, s, n, offsets, hw, total_pixels, dets,
                      counts, k, link, carry, (unsigned long long*)inter, linked, lookup);
-  hipLaunchKernelGGL(link_overlap_kernel, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts,
-                     k, carry, linked, lookup, (unsigned long long*)inter);
+  hipLaunchKernelGGL(overlap, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts, k, carry,
+                     linked, lookup, disp, (unsigned long long*)inter);
   hipLaunchKernelGGL(link_match_kernel, dim3(n), dim3(256), lds_match, s, dets, counts, k, carry, linked, inter, min_iou_permille, match);
   hipLaunchKernelGGL(link_ids_kernel, dim3(n), dim3(64), 0, s, n, counts, k, carry, linked, match, ids, seq_tracks, next_id);
   UDET_HIP(hipGetLastError());
@@ -329,7 +350,7 @@ __global__ __launch_bounds__(256) void gap_overlap_kernel(const int* __restrict_
                                         (size_t)offsets[f]}
                              : LinkSide{hist.labels + (size_t)j * HW, hist.dets + (size_t)j * k * UDET_DET_FIELDS,
                                         link_rows(hist.counts + 3 * j, k), total_pixels + (size_t)(hist.m - 1 - j) * HW};
-  link_overlap_pass(fp, fc, W, HW, k, lookup, gap_inter + ((size_t)c * max_gap + (d - 2)) * k * k, link_lds);
+  link_overlap_pass<false>(fp, fc, 0, W, HW, k, lookup, nullptr, gap_inter + ((size_t)c * max_gap + (d - 2)) * k * k, link_lds);
 }
 
 // A row of frame f (f < 0: of the history) has found its successor.
@@ -449,8 +470,8 @@ int launch_link_detections_gap_ragged(const int* labels, int n, const long long*
                                       int max_gap, int m, const int* hist_labels, int hist_h, int hist_w, const long long* hist_dets,
                                       const long long* hist_counts, const int* hist_ids, int* hist_open, const int* hist_next_id,
                                       int min_iou_permille, long long* inter, int* match, int* ids, int* linked, int* seq_tracks,
-                                      int* next_id, long long* gap_inter, int* back, int* prev, int* open, void* workspace,
-                                      hipStream_t s) {
+                                      int* next_id, long long* gap_inter, int* back, int* prev, int* open, const int* disp,
+                                      void* workspace, hipStream_t s) {
   const long nb = ((long)max_h * max_w + 256 * LINK_PPT - 1) / (256 * LINK_PPT);
   if (nb > 0x7fffffffL) { set_error("link_detections_gap_ragged: frame too large"); return UDET_ERR_SHAPE; }
   const LinkHistory hist = {hist_labels, hist_dets, hist_counts, hist_ids, hist_open, hist_next_id, m, hist_h, hist_w};
@@ -458,14 +479,15 @@ int launch_link_detections_gap_ragged(const int* labels, int n, const long long*
   const LinkCarry carry = {m ? hist_labels + last * frame : nullptr, m ? hist_dets + last * k * UDET_DET_FIELDS : nullptr,
                            m ? hist_counts + 3 * last : nullptr, m ? hist_ids + last * k : nullptr, hist_next_id, hist_h, hist_w};
   int* lookup = (int*)workspace;
+  const auto overlap = disp ? link_overlap_kernel<true> : link_overlap_kernel<false>;  // disp = nullptr: the co-located link
   const size_t nz = ((size_t)n * k * k + 255) / 256, ngz = nz * max_gap;
   const size_t lds_overlap = ((size_t)k * k + 2 * k) * sizeof(int), lds_match = (2 * (size_t)k * k + 3 * k) * sizeof(int);
   hipLaunchKernelGGL(link_init_kernel, dim3((unsigned)(nz > 65536 ? 65536 : nz)), dim3(256), 0, s, n, offsets, hw, total_pixels, dets,
                      counts, k, link, carry, (unsigned long long*)inter, linked, lookup);
   hipLaunchKernelGGL(gap_init_kernel, dim3((unsigned)(ngz > 65536 ? 65536 : ngz)), dim3(256), 0, s, n, k, max_gap, total_pixels, hist,
                      (unsigned long long*)gap_inter, lookup);
-  hipLaunchKernelGGL(link_overlap_kernel, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts,
-                     k, carry, linked, lookup, (unsigned long long*)inter);
+  hipLaunchKernelGGL(overlap, dim3((unsigned)nb, n), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets, counts, k, carry,
+                     linked, lookup, disp, (unsigned long long*)inter);
   hipLaunchKernelGGL(gap_overlap_kernel, dim3((unsigned)nb, n, max_gap), dim3(256), lds_overlap, s, labels, offsets, hw, total_pixels, dets,
                      counts, k, max_gap, hist, linked, lookup, (unsigned long long*)gap_inter);
   hipLaunchKernelGGL(link_match_kernel, dim3(n), dim3(256), lds_match, s, dets, counts, k, carry, linked, inter, min_iou_permille, match);

@@ -23,7 +23,8 @@ and score -- the detections -- is restore_results_dir(detections={...}) (DESIGN.
 is restore_results_dir(tracks={...}) (DESIGN.md 7.8), across frames in which a component is missing with tracks={"max_gap": G}
 (DESIGN.md 7.9); the tracks as per-frame instance maps, their picture and a track's J against the annotation is
 restore_results_dir(instances={...}); exporting and scoring the masks of whole tracks, chosen without the annotation, is
-restore_results_dir(follow={...}) (native_follow)."""
+restore_results_dir(follow={...}) (native_follow); linking along the optical flow between the frames is
+restore_results_dir(tracks={"motion": {...}}) (native_motion)."""
 import functools
 import os
 from types import SimpleNamespace
@@ -39,6 +40,7 @@ from .native_follow import (FOLLOW_DEFAULTS, FOLLOW_RULES, FollowedMasks, check_
 from .native_instances import (INSTANCE_PALETTE_BYTES, INSTANCE_UNASSIGNED, INSTANCE_WRAP, InstanceMaps, check_instance_arguments,  # noqa: F401
                                instance_maps, instance_params, track_gt_scores)
 from .native_restore import TAB, RestoredMasks, build_restore_tables, check_restore_tables, restore_box, restore_masks  # noqa: F401
+from .native_motion import BackwardFlow, flow_displacements  # noqa: F401
 from .native_tracks import (TRACK_DEFAULTS, TRACK_MAX_GAP, TrackHistory, Tracks, TrackTail, check_link_arguments,  # noqa: F401
                             link_detections, min_iou_permille, summarise_tracks, track_max_gap, track_params, track_records)
 from .post_processing import CRF_MAX_SAMPLES, default_radius, dense_crf_ragged, unary_from_restored
@@ -207,6 +209,8 @@ def _resolve_options(o):
         if o.detections is None:
             raise ValueError("tracks links the detections: it needs detections")
         o.tracks = track_params(o.tracks)
+        if "motion" in o.tracks and o.motion_flow is None:
+            o.motion_flow = BackwardFlow(size=o.tracks["motion"]["size"])
     o.boxes = None
     if o.overlay is not None:
         from .visualize import box_params, overlay_params
@@ -342,6 +346,9 @@ def _restore_category(cat, entries, o):
     j, f, nc, fg = np.empty(len(entries)), np.empty(len(entries)), np.zeros(len(entries)), np.zeros(len(entries))
     records = {}  # frame stem -> its detections, in the list's order
     tail, starts = None, []  # tracks: the previous batch's last frame; per frame, whether it starts a sequence
+    motion = o.tracks is not None and "motion" in o.tracks  # the link follows the flow between the frames
+    if motion and hasattr(o.motion_flow, "reset"):
+        o.motion_flow.reset()  # the category's first frame has no frame before it
     row_gts, gt_area, unassigned = [], [], []  # instances, per frame: row_gt of its records, its annotated pixels, the share of value 255
     held, score_sums = [], []  # follow: per batch what pass 2 reads, held on the device; per frame the score_sum of its rows
     own_overlay = o.overlay is not None and (o.follow is None or (o.instances is not None and o.instances["overlay"]))  # drawn in this loop
@@ -364,7 +371,7 @@ def _restore_category(cat, entries, o):
             raise ValueError("load_sizes must return one (H, W) per path")
         res = o.restore(np.stack(masks), sizes, o.crop, o.threshold)
         pred = res  # what is scored and exported as the binary mask
-        frames = o.load_images(images) if o.crf is not None or own_overlay else None  # read once for both
+        frames = o.load_images(images) if o.crf is not None or own_overlay or motion else None  # read once for all of them
         if o.crf is not None:
             pred = o.refine(res, frames, o.crf)
         if o.component is not None:  # with detections: the batch's labels as well -- what the CRF left, labelled once
@@ -378,8 +385,11 @@ def _restore_category(cat, entries, o):
             det = o.detect(labelled, score=res, min_area=o.detections["min_area"], max_detections=o.detections["max_detections"])
             recs = detection_records(det, res.amax)
             if o.tracks is not None:
+                more = {"max_gap": o.tracks["max_gap"]} if "max_gap" in o.tracks else {}
+                if motion:  # row i: from frame i to the frame before it, the previous batch's last frame for row 0
+                    more["disp"] = o.displace(o.motion_flow(frames), labelled)
                 trk = o.link(labelled, det, link=[0 if s + i == 0 else 1 for i in range(len(rows))], carry=tail, min_iou=o.tracks["min_iou"],
-                             **({"max_gap": o.tracks["max_gap"]} if "max_gap" in o.tracks else {}))
+                             **more)
                 tail = trk.tail()
                 recs = track_records(recs, trk)
                 starts += [not v for v in trk.host()[3]]
@@ -467,7 +477,7 @@ def _summary(cats, o):
         out["detections"] = dict(o.detections, connectivity=int(o.connectivity))
         per_sequence += ["detections_mean"]
     if o.tracks is not None:
-        out["tracks"] = o.tracks
+        out["tracks"] = {k: v for k, v in o.tracks.items() if k != "motion"}
         per_sequence += ["tracks", "track_len_mean"]
     if o.instances is not None:
         out["instances"] = o.instances
@@ -480,6 +490,8 @@ def _summary(cats, o):
         out["follow"] = o.follow
         for c, seq in out["sequences"].items():
             seq["kept_mean"] = cats[c]["kept_mean"]
+    if o.tracks is not None and "motion" in o.tracks:
+        out["track_motion"] = {"size": list(o.tracks["motion"]["size"])}
     return out
 
 
@@ -489,7 +501,8 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                         refine=crf_refine_restored, load_sizes=load_sizes_header, overlay=None, draw=draw_overlays, detections=None,
                         detect=component_boxes, draw_boxes=draw_detection_boxes, tracks=None, link=link_detections,
                         draw_track_boxes=draw_track_detection_boxes, instances=None, paint=instance_maps,
-                        draw_instances=draw_instance_overlays, follow=None, keep=follow_tracks):
+                        draw_instances=draw_instance_overlays, follow=None, keep=follow_tracks, motion_flow=None,
+                        displace=flow_displacements):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -538,6 +551,12 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     tracks["max_gap"] (0; 1..8: DESIGN.md 7.9) lets a row continue a track that ended up to max_gap frames earlier: link is then called
     with max_gap= as well and the tail() it carries is the history of the last max_gap + 1 frames; the records gain "back", the tracks
     "span" and "gaps", the sequences "bridged", and the json's "tracks" carries max_gap.  With 0 or without the key nothing changes.
+    tracks["motion"] (None: off; {} or {"size": (fh, fw)}, both multiples of 64, default 384 x 640: DESIGN.md 7.12) links along the
+    optical flow: the frames are loaded for every batch, motion_flow(frames) (None: a native_motion.BackwardFlow of that size; its
+    reset(), where it has one, is called at every category's start) returns the flow from every frame to the frame before it, float32
+    [n, fh, fw, 2], displace(flow, labelled) (flow_displacements) turns it into one displacement per pixel, and link is called with
+    disp= as well; the "iou" of the records is then clamped to 1 and the json gains "track_motion": {"size": [fh, fw]} after its other
+    keys.  Without the key link receives no disp= and every file is what it was.
     instances (None: off; needs tracks): {} or {"overlay": bool}.  After the link every batch goes through paint(labelled, det, tracks,
     gt=the batch's annotations or None) (instance_maps: two launches per batch) and every frame's map is written to
     <out_dir>/instances/<category>/<frame stem>.png, an indexed PNG (Pillow mode "P", INSTANCE_PALETTE_BYTES) whose bytes are the map's: 0
@@ -566,7 +585,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     tracks/<category>.json "followed": [ids]; new keys come after the existing ones.  With None nothing of this runs and every file is
     byte for byte what it is without the argument.
     restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes / paint /
-    draw_instances / keep are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    draw_instances / keep / motion_flow / displace are injectable: the host logic runs without a GPU on numpy stand-ins."""
     o = SimpleNamespace(**locals())  # every argument under its own name: the options and the injected callables
     _resolve_options(o)
     cats = {cat: _restore_category(cat, entries, o) for cat, entries in frame_lists.items()}

@@ -1,5 +1,6 @@
 """Native-resolution stage, step 4: the detections of consecutive frames linked into tracks by mask overlap (csrc/tracks.hip,
-DESIGN.md 7.8), across frames in which a component is missing with max_gap > 0.
+DESIGN.md 7.8), across frames in which a component is missing with max_gap > 0, along a displacement per pixel with
+disp (native_motion.flow_displacements makes one from the optical flow).
 
   link_detections(selection_or_labels, detections, link, carry, min_iou, max_gap)   one call of udet_link_detections_ragged -> Tracks;
                                                 tail() carries the last frame into the next call (TrackTail).  max_gap > 0: a track also
@@ -34,14 +35,17 @@ def track_params(tracks=None):
     """The `tracks` dict of restore_results_dir ({} or None: the defaults) with the defaults filled in and checked (ValueError)."""
     p = dict(TRACK_DEFAULTS)
     if tracks is not None:
-        if not isinstance(tracks, dict) or not set(tracks) <= set(TRACK_DEFAULTS) | {"max_gap"}:
-            raise ValueError("tracks must be a dict with keys among {}".format(sorted(set(TRACK_DEFAULTS) | {"max_gap"})))
+        if not isinstance(tracks, dict) or not set(tracks) <= set(TRACK_DEFAULTS) | {"max_gap", "motion"}:
+            raise ValueError("tracks must be a dict with keys among {}".format(sorted(set(TRACK_DEFAULTS) | {"max_gap", "motion"})))
         p.update({k: v for k, v in tracks.items() if v is not None})
     min_iou_permille(p["min_iou"])
     p["min_iou"] = float(p["min_iou"])
-    gap = track_max_gap(p.pop("max_gap", 0))
+    gap, motion = track_max_gap(p.pop("max_gap", 0)), p.pop("motion", None)
     if gap:  # the key only when gaps are bridged: without it the dict is what it was
         p["max_gap"] = gap
+    if motion is not None:  # likewise: {"size": (fh, fw)} only when the link follows the flow (DESIGN.md 7.12)
+        from .native_motion import motion_params
+        p["motion"] = motion_params(motion)
     return p
 
 
@@ -87,13 +91,14 @@ class Tracks(object):
     linked (int32 [n]), seq_tracks (int32 [n]) and next_id (int32 [1]) as include/udet.h defines them, on the device; labels: the packed
     labels they were computed from; carry: the TrackTail frame 0 was linked against, or None.  Linked with gap bridging (max_gap > 0):
     gap_inter (int64 [n, max_gap, k, k]), back, prev and open (int32 [n, k]) as well, carry is the TrackHistory or None and hist_open
-    (int32 [m, k]) its open flags after this call."""
+    (int32 [m, k]) its open flags after this call.  motion: whether it was linked through displacements (inter / union may then exceed 1)."""
 
     def __init__(self, inter, match, ids, linked, seq_tracks, next_id, labels, detections, carry=None, back=None, prev=None, gap_inter=None,
-                 open=None, max_gap=0, hist_open=None):
+                 open=None, max_gap=0, hist_open=None, motion=False):
         self.inter, self.match, self.ids, self.linked, self.seq_tracks, self.next_id = inter, match, ids, linked, seq_tracks, next_id
         self.labels, self.detections, self.carry, self.k = labels, detections, carry, int(ids.shape[1])
         self.back, self.prev, self.gap_inter, self.open, self.max_gap, self.hist_open = back, prev, gap_inter, open, int(max_gap), hist_open
+        self.motion = bool(motion)
         self.layout = getattr(detections, "layout", None)  # (a numpy stand-in of the detections has none: it brings its own tail())
         self._host = self._host_gaps = None
 
@@ -143,15 +148,17 @@ class Tracks(object):
         return TrackHistory(lab, (h, w), dets, counts, ids, open, _clone(self.next_id), self.max_gap)
 
 
-def check_link_arguments(layout, detections, link, carry, min_iou, max_gap=0):
+def check_link_arguments(layout, detections, link, carry, min_iou, max_gap=0, disp=None):
     """The host validation of link_detections (ValueError): `layout` (the labels') equals the detections', dets / counts have their shapes, link is None or n values 0 / 1, carry is None or a TrackTail of the same k (max_gap > 0: a TrackHistory of the same k and max_gap), min_iou
-    rounds to a permille in 1..1000.  Returns (link as int32 [n] or None when it is a device tensor, permille)."""
+    rounds to a permille in 1..1000, disp is None or an int32 tensor of one element per element of the labels' buffer.  Returns (link as int32 [n] or None when it is a device tensor, permille)."""
     n, k = detections.layout.n, int(detections.k)
     if not layout.same_as(detections.layout):
         raise ValueError("the labels must be packed like the detections' frames (same offsets and sizes)")
     if tuple(detections.dets.shape) != (n, k, DET_FIELDS) or tuple(detections.counts.shape) != (n, 3) or not 1 <= k <= DET_MAX_K:
         raise ValueError("detections: dets must be [{}, k, {}] and counts [{}, 3] with k in 1..{}".format(n, DET_FIELDS, n, DET_MAX_K))
     permille = min_iou_permille(min_iou)
+    if disp is not None:
+        require_tensor(disp, "disp (one packed displacement per pixel, laid out like the labels)", torch.int32, 1, layout.numel, cuda=False)
     if max_gap and carry is not None:
         if not isinstance(carry, TrackHistory) or carry.k != k or carry.max_gap != max_gap:
             raise ValueError("carry must be the tail() of the previous call's Tracks, linked with the same k = {} and max_gap = {}".format(k, max_gap))
@@ -178,7 +185,7 @@ def check_link_arguments(layout, detections, link, carry, min_iou, max_gap=0):
     return np.ascontiguousarray(host.astype(np.int32)), permille
 
 
-def link_detections(selection_or_labels, detections, link=None, carry=None, min_iou=0.1, max_gap=0) -> Tracks:
+def link_detections(selection_or_labels, detections, link=None, carry=None, min_iou=0.1, max_gap=0, disp=None) -> Tracks:
     """The detections of n consecutive frames linked into tracks by mask overlap, in one call of udet_link_detections_ragged (four
     launches whatever n and the number of sequences and components; nothing comes back to the host).  selection_or_labels: the
     ComponentSelection (with labels) or the 1-D int32 device tensor of labels `detections` (a Detections) was computed from.  link: one
@@ -191,16 +198,23 @@ def link_detections(selection_or_labels, detections, link=None, carry=None, min_
     max_gap (0; 1..8: DESIGN.md 7.9): one call of udet_link_detections_gap_ragged (six launches) in its place -- a row without a
     predecessor in the frame before it may continue a track that ended up to max_gap frames earlier, by the same IoU rule against that
     track's last-seen component; the Tracks carries gap_inter, back, prev and open as well, and carry is the TrackHistory that tail()
-    of a Tracks with the same k and max_gap returns (its tensors stay as they are: the open flags this call closes are in hist_open)."""
+    of a Tracks with the same k and max_gap returns (its tensors stay as they are: the open flags this call closes are in hist_open).
+    disp (None): a device int32 tensor of one packed displacement per element of labels (dx in the low 16 bits, dy in the
+    high 16; native_motion.flow_displacements) -- one call of udet_link_detections_motion_ragged (with max_gap: of
+    udet_link_detections_gap_motion_ragged) in its place: inter counts a pixel of the frame against the predecessor's label at
+    (x + dx, y + dy), a source outside the frame counts nothing, and everything else is as above (only stage 1 of the gap form is warped).
+    The Tracks says so in `motion`.  None is the co-located call, byte for byte."""
     max_gap = track_max_gap(max_gap)
     labels, layout, _ = packed_labels(selection_or_labels, None if isinstance(selection_or_labels, ComponentSelection) else detections.layout)
     total = int(require_tensor(labels, "labels (packed samples)", torch.int32, 1, cuda=False).numel())
     as_layout(layout, None, total, max_samples=65535)
     for t, name, nd in ((detections.dets, "dets", 3), (detections.counts, "counts", 2)):
         require_tensor(t, "detections." + name, torch.int64, nd, cuda=False)
-    host_link, permille = check_link_arguments(layout, detections, link, carry, min_iou, max_gap)
+    host_link, permille = check_link_arguments(layout, detections, link, carry, min_iou, max_gap, disp)
     require_tensor(labels, "labels (packed samples)", torch.int32, 1)
     dev, n, k = labels.device, layout.n, detections.k
+    if disp is not None:
+        require_tensor(disp, "disp (one packed displacement per pixel, laid out like the labels)", torch.int32, 1, total, device=dev)
     require_tensor(detections.dets, "detections.dets", torch.int64, 3, device=dev)
     require_tensor(detections.counts, "detections.counts", torch.int64, 2, device=dev)
     carried = {}  # the carry's tensors by name, in the order they are checked; `open` is the TrackHistory's alone
@@ -226,17 +240,20 @@ def link_detections(selection_or_labels, detections, link=None, carry=None, min_
               detections.counts.data_ptr(), k, d_link.data_ptr())
     results = (inter.data_ptr(), match.data_ptr(), ids.data_ptr(), linked.data_ptr(), seq_tracks.data_ptr(), next_id.data_ptr())
     stream = torch.cuda.current_stream(dev).cuda_stream
+    moved = () if disp is None else (disp.data_ptr(),)  # the motion entries take disp in front of the workspace
     if max_gap:
         m = carry.m if carry is not None else 0
         ws = workspace(lib.udet_link_detections_gap_workspace_bytes(total, n, k, max_gap, m, ch, cw), 4, dev)
-        check(lib.udet_link_detections_gap_ragged(*frames, max_gap, m, c("labels"), ch, cw, c("dets"), c("counts"), c("ids"), c("open"),
-                                                  c("next_id"), permille, *results, gap_inter.data_ptr(), back.data_ptr(), prev.data_ptr(),
-                                                  open.data_ptr(), ws.data_ptr(), ws.numel(), stream))
+        entry = lib.udet_link_detections_gap_ragged if disp is None else lib.udet_link_detections_gap_motion_ragged
+        check(entry(*frames, max_gap, m, c("labels"), ch, cw, c("dets"), c("counts"), c("ids"), c("open"), c("next_id"), permille, *results,
+                    gap_inter.data_ptr(), back.data_ptr(), prev.data_ptr(), open.data_ptr(), *moved, ws.data_ptr(), ws.numel(), stream))
     else:
         ws = workspace(lib.udet_link_detections_workspace_bytes(total, n, k, ch, cw), 4, dev)
-        check(lib.udet_link_detections_ragged(*frames, c("labels"), ch, cw, c("dets"), c("counts"), c("ids"), c("next_id"), permille, *results,
-                                              ws.data_ptr(), ws.numel(), stream))
-    return Tracks(inter, match, ids, linked, seq_tracks, next_id, labels, detections, carry, back, prev, gap_inter, open, max_gap, hist_open)
+        entry = lib.udet_link_detections_ragged if disp is None else lib.udet_link_detections_motion_ragged
+        check(entry(*frames, c("labels"), ch, cw, c("dets"), c("counts"), c("ids"), c("next_id"), permille, *results, *moved, ws.data_ptr(),
+                    ws.numel(), stream))
+    return Tracks(inter, match, ids, linked, seq_tracks, next_id, labels, detections, carry, back, prev, gap_inter, open, max_gap, hist_open,
+                  disp is not None)
 
 
 def track_records(records, tracks):
@@ -245,12 +262,13 @@ def track_records(records, tracks):
     area_b - inter) of that pair in float64, or None).  tracks: a Tracks (or anything with its host(), detections.dets and carry.dets).  Returns
     new lists; the records given stay as they are.  Linked with gap bridging (tracks.max_gap > 0, host_gaps() and a TrackHistory as
     carry), every record gains "back" as well (1: it continues the frame before, d >= 2: a bridge to frame c - d, 0: a new track),
-    "prev" is the rank in frame c - back and the "iou" of a bridged row comes from gap_inter."""
+    "prev" is the rank in frame c - back and the "iou" of a bridged row comes from gap_inter.  Linked with motion (tracks.motion), "iou" is
+    min(1.0, inter / union): displacements may map many pixels onto one, so inter may exceed the predecessor's area."""
     inter, match, ids, _, _ = tracks.host()
     if len(records) != len(ids):
         raise ValueError("one list of records per frame")
     dets = _host(tracks.detections.dets)
-    gaps = getattr(tracks, "max_gap", 0) > 0
+    gaps, motion = getattr(tracks, "max_gap", 0) > 0, bool(getattr(tracks, "motion", False))
     if gaps:
         gap_inter, back, prev_rank, _ = tracks.host_gaps()
         hist = None if tracks.carry is None else _host(tracks.carry.dets)  # [m, k, 9]: frame -1 is its last
@@ -269,6 +287,8 @@ def track_records(records, tracks):
             if a >= 0:
                 it = int(inter[i, a, b] if d == 1 else gap_inter[i, d - 2, a, b])
                 iou = float(np.float64(it) / np.float64(int(prev[a, 1]) + int(dets[i, b, 1]) - it))
+                if motion:
+                    iou = min(1.0, iou)
             new.append(dict(rec, track=int(ids[i, b]), prev=a if a >= 0 else None, iou=iou, **more))
         out.append(new)
     return out
