@@ -12,7 +12,12 @@ extern "C" {
  * second launch, bit 21: split-K summed by the last-arriving workgroup, bit 22 / 23: LDS-DMA kernel with a 3 / 4 stage
  * ring, bit 24: the direct kernels for 2-channel inputs / outputs where the launch is eligible, bit 25: the Winograd F(2x2,3x3) family with
  * bm & 0xffff = variant; ks + 256 r: tail split for r workgroup slots per CU); (0,0,-1) restores.  A forced family a launch is not eligible
- * for, or a tile that is not instantiated, falls back to the built-in choice.  Process-global state: never call it from product code. */
+ * for, or a tile that is not instantiated, falls back to the built-in choice.  Process-global state: never call it from product code.
+ * Pair launches (launch_conv_pair) launch their two problems apart while a configuration is forced, each on that configuration -- unless
+ * udet_debug_force_pair(1) is set: then the pair itself runs the forced configuration as far as a pair has one.  Tile: (bm & 0xffff, bn) if it
+ * is an instantiated GEMM tile, else the pair heuristic's.  Ring: 3 stages if bit 22 is set, else 2.  Split count: ks & 0xff, clamped to the
+ * pair's capacity (both problems' slabs side by side in one scratch region); ks < 0: the heuristic's.  The pair kernels exist only as LDS-DMA
+ * kernels with a 2- / 3-stage ring and a second-launch summation: bits 16 - 21 and 23 - 25 and the tail split (ks + 256 r) are ignored there. */
 void udet_debug_force_conv(int bm, int bn, int ks);
 /* fp16 multiplication (fp32 accumulation) in the single-operator convolution entry points; plans take it from
  * udet_config.conv_fp16.  Process-global state: tests only. */
@@ -49,8 +54,11 @@ int udet_debug_conv2d_backward_filter_ex(const float* x, int ldx, int x_coff, co
 void udet_debug_upb_min_pixels(long v);
 void udet_debug_set_tuning(int on);
 /* pair launches (two convolutions of the same geometry in ONE launch: the recover net's two encoders, csrc/conv_select.hip launch_conv_pair):
- * on = 1 pairs every compatible couple whatever the tuner thinks, 0 never pairs, -1 restores (tuned / heuristic choice);
- * udet_debug_last_pair: 1 when the most recent pair call went out as one launch */
+ * on = 1 pairs every compatible couple whatever the tuner thinks -- on the configuration of udet_debug_force_conv where one is forced (tile,
+ * ring and split count as described there; neither the pair cache nor the tuner is asked then), 0 never pairs, -1 restores (tuned / heuristic
+ * choice; a forced configuration then launches the two apart);
+ * udet_debug_last_pair: 1 when the most recent pair call went out as one launch.  udet_debug_last_conv then carries bit 30, the tile, family 2 / 4
+ * and the split count that ran (after the clamp to the pair's capacity) */
 void udet_debug_force_pair(int on);
 int udet_debug_last_pair(void);
 /* two forward convolutions (same shape parameters; cin a multiple of 8; batches na / nb; HWIO weights) through the pair launcher;
@@ -181,6 +189,19 @@ typedef struct udet_debug_conv_ex {
 } udet_debug_conv_ex;
 size_t udet_debug_conv2d_ex_workspace_bytes(const udet_debug_conv_ex* args);
 int udet_debug_conv2d_ex(const udet_debug_conv_ex* args, void* workspace, size_t workspace_bytes, void* stream);
+/* Two such problems through the pair launcher, as a lane of a step plan hands a couple over (tests/test_conv_pair_epilogue_gpu.py): every
+ * window and option above per problem, separate packed-weight regions, ONE zero block, one set of ticket counters and one split-K scratch
+ * region for both (partial and partial_cap are the same in the two parameter blocks), then one call of launch_conv_pair and a
+ * synchronisation of the stream, whose error is the entry's.  Only what a plan pairs is accepted: forms 0 and 1 with up = 0, form 1 only where
+ * the backward-data pass is ONE launch (stride 2 on an odd grid is one launch per class: UDET_ERR_ARG).  A couple the pair launcher declines
+ * (different kc, columns or taps, xa given, fp16 mode, udet_debug_force_pair(0)) is not refused: it goes out as two launches, a first, and
+ * udet_debug_last_pair reports 0.  Every argument is checked before the first HIP call: each struct as in udet_debug_conv2d_ex (problem a
+ * first); NULL structs, an unaccepted form, a workspace that is NULL, not 64-byte aligned or smaller than
+ * udet_debug_conv2d_pair_ex_workspace_bytes(a, b) -> UDET_ERR_ARG.
+ * Workspace (floats): zero block, ticket counters and one pack job as above, from 4224 the packed weights of a, then those of b (each rounded up
+ * to 64), then 8 Mi floats of split-K slabs. */
+size_t udet_debug_conv2d_pair_ex_workspace_bytes(const udet_debug_conv_ex* a, const udet_debug_conv_ex* b);
+int udet_debug_conv2d_pair_ex(const udet_debug_conv_ex* a, const udet_debug_conv_ex* b, void* workspace, size_t workspace_bytes, void* stream);
 /* (The experiment knobs of earlier rounds -- lane choices and the work-skipping ablation mask -- are no longer reachable from any library
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */

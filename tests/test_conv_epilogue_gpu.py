@@ -55,6 +55,7 @@ class Prob:
     xact: int = ACT_NONE  # act' on load (form 1)
     f16: bool = False
     pack_job: int = 0     # forms 0 / 1: 1 packs through a job of launch_pack_jobs (the per-step packer of the trainable networks)
+    seed: int = 0         # shifts every seed of operands(): the two problems of a pair launch hold different data
 
     @property
     def backward(self):
@@ -103,6 +104,7 @@ class Opt:
     u: tuple = (4, 4)
     ua: tuple = (8, 8)
     ua_shift: int = 0       # the ua pointer offset by this many floats (1: not 16-byte aligned)
+    urange: tuple = None    # the emission's [u_c0, u_c1); (0, 0): all columns; None: emit_range
 
 
 S = Opt("S", bias=True, act=ACT_ELU, y=(8, 8), y2=(4, 4), res=(4, 4))
@@ -121,6 +123,14 @@ def emit_range(cols):
     return 4, c1
 
 
+def emit_of(o, cols):
+    if o.urange is None:
+        return emit_range(cols)
+    c0, c1 = o.urange if o.urange != (0, 0) else (0, cols)
+    assert 0 <= c0 < c1 <= cols, (o.urange, cols)
+    return c0, c1
+
+
 def randn(*shape, seed):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
@@ -129,17 +139,17 @@ def randn(*shape, seed):
 def operands(p: Prob, o: Opt):
     """float32 host tensors of the launch, seeded by the problem alone (every option set of a problem sees the same x / w / bias)"""
     (ih, iw), (oh, ow) = p.grids()
-    rows = p.n * oh * ow
+    rows, sd = p.n * oh * ow, 100 * p.seed
     if p.f16:
-        x = mag(p.n, ih, iw, p.ldx, seed=1)
-        w = mag(p.k, p.k, p.cin, p.cout, seed=2, scale=(2.0 / (p.k * p.k * p.cin)) ** 0.5)
+        x = mag(p.n, ih, iw, p.ldx, seed=sd + 1)
+        w = mag(p.k, p.k, p.cin, p.cout, seed=sd + 2, scale=(2.0 / (p.k * p.k * p.cin)) ** 0.5)
     else:
-        x = randn(p.n, ih, iw, p.ldx, seed=1)
-        w = randn(p.k, p.k, p.cin, p.cout, seed=2) * (2.0 / (p.k * p.k * p.cin)) ** 0.5
-    d = dict(x=x, w=w, bias=randn(p.cout, seed=3) * 0.1 if o.bias else None, rows=rows)
+        x = randn(p.n, ih, iw, p.ldx, seed=sd + 1)
+        w = randn(p.k, p.k, p.cin, p.cout, seed=sd + 2) * (2.0 / (p.k * p.k * p.cin)) ** 0.5
+    d = dict(x=x, w=w, bias=randn(p.cout, seed=sd + 3) * 0.1 if o.bias else None, rows=rows)
     if p.xact != ACT_NONE:
-        xa = randn(p.n, ih, iw, p.ldx, seed=4)
-        xa[randn(p.n, ih, iw, p.ldx, seed=5) > 1.0] = 0.0
+        xa = randn(p.n, ih, iw, p.ldx, seed=sd + 4)
+        xa[randn(p.n, ih, iw, p.ldx, seed=sd + 5) > 1.0] = 0.0
         d["xa"] = xa
 
     def out_buffer(win, old_seed=None):
@@ -149,15 +159,15 @@ def operands(p: Prob, o: Opt):
             b[GUARD:GUARD + rows, win[0]:win[0] + p.cols] = randn(rows, p.cols, seed=old_seed)
         return b
 
-    d["y"] = out_buffer(o.y, 6 if o.accumulate else None)
+    d["y"] = out_buffer(o.y, sd + 6 if o.accumulate else None)
     if o.y2:
         d["y2"] = out_buffer(o.y2)
     if o.res:
-        d["res"] = randn(rows, o.res[0] + p.cols + o.res[1], seed=7)
+        d["res"] = randn(rows, o.res[0] + p.cols + o.res[1], seed=sd + 7)
     if o.uact >= 0:
         d["uo"] = out_buffer(o.u)
-        ua = randn(rows, o.ua[0] + p.cols + o.ua[1], seed=8)
-        ua[randn(rows, ua.shape[1], seed=9) > 1.0] = 0.0   # exact zeros beside negatives and positives
+        ua = randn(rows, o.ua[0] + p.cols + o.ua[1], seed=sd + 8)
+        ua[randn(rows, ua.shape[1], seed=sd + 9) > 1.0] = 0.0   # exact zeros beside negatives and positives
         assert int((ua == 0).sum()) > 0 and int((ua < 0).sum()) > 0 and int((ua > 0).sum()) > 0
         d["ua"] = ua
     return d
@@ -187,7 +197,7 @@ def reference(p: Prob, o: Opt):
     f = lambda k: as_nhwc(d[k].double(), p, k in ("y", "y2", "uo")) if k in d else None  # noqa: E731
     kw = {}
     if o.uact >= 0:
-        c0, c1 = emit_range(p.cols)
+        c0, c1 = emit_of(o, p.cols)
         kw = dict(uo=f("uo"), u_coff=o.u[0], ua=f("ua"), ua_coff=o.ua[0], uact=o.uact, ualpha=float(np.float32(o.ualpha)), u_c0=c0, u_c1=c1)
     # (the linear part -- x window, gap map, act' on load, the convolution -- is linear_part's: one per problem)
     yn, y2n, un = X.conv_ex(p.form, None, p.x_coff, p.K, d["w"].double(), f("y"), o.y[0], bias=None if d["bias"] is None else d["bias"].double(),
@@ -216,8 +226,8 @@ def lib(devel):
 _ws = {}
 
 
-def launch(devel, p: Prob, o: Opt):
-    """one udet_debug_conv2d_ex call; returns the host copies of (y, y2, uo) WITH their guard rows and the configuration word"""
+def device_fields(p: Prob, o: Opt):
+    """(device copies of the launch's tensors, the fields of its udet_debug_conv_ex)"""
     d = operands(p, o)
     g = {k: v.cuda() for k, v in d.items() if isinstance(v, torch.Tensor)}
     f = dict(form=p.form, n=p.n, h=p.h, wd=p.w, cin=p.cin, cout=p.cout, k=p.k, stride=p.stride, dilation=p.dil, up=p.up, kc=p.K,
@@ -232,7 +242,7 @@ def launch(devel, p: Prob, o: Opt):
     if o.y2:
         f.update(y2=(g["y2"], GUARD * g["y2"].shape[1]), ldy2=g["y2"].shape[1], y2_coff=o.y2[0])
     if o.uact >= 0:
-        c0, c1 = emit_range(p.cols)
+        c0, c1 = emit_of(o, p.cols)
         ua = g["ua"]
         if o.ua_shift:  # the same values behind a pointer that is 4 bytes off a 16-byte boundary
             store = torch.zeros(ua.numel() + 4, device="cuda")
@@ -242,6 +252,12 @@ def launch(devel, p: Prob, o: Opt):
             assert (store.data_ptr() + 4 * o.ua_shift) % 16 == 4 * o.ua_shift
         f.update(uo=(g["uo"], GUARD * g["uo"].shape[1]), ldu=g["uo"].shape[1], u_coff=o.u[0], ua=ua, ldua=g["ua"].shape[1], ua_coff=o.ua[0],
                  uact=o.uact, ualpha=o.ualpha, u_c0=c0, u_c1=c1)
+    return g, f
+
+
+def launch(devel, p: Prob, o: Opt):
+    """one udet_debug_conv2d_ex call; returns the host copies of (y, y2, uo) WITH their guard rows and the configuration word"""
+    g, f = device_fields(p, o)
     need = devel.conv2d_ex_workspace_bytes(**f)
     if _ws.get("n", 0) < need:
         _ws["t"], _ws["n"] = torch.empty(need // 4, device="cuda"), need
@@ -265,7 +281,7 @@ def dfo32(a, act, alpha):
 
 def check(p: Prob, o: Opt, got, v0):
     """the launch's outputs against the float64 reference, against the plain run v0 [rows, cols] of the same configuration, and the
-    sentinel everywhere else"""
+    sentinel everywhere else; returns y's deviation from float64 as a fraction of the scale"""
     d = operands(p, o)
     ref_y, ref_y2, ref_u = reference(p, o)
     rows, C = d["rows"], p.cols
@@ -285,7 +301,7 @@ def check(p: Prob, o: Opt, got, v0):
     print("%s %s: y %.2e of the scale (bound %.0e)" % (p, o.name, e, coeff))
     assert torch.isfinite(yw).all() and e < coeff, ("y against float64", e)
     if v0 is None:
-        return
+        return e
     if o.y2:
         untouched("y2", o.y2, C)
         y2w = body(got["y2"])[:, o.y2[0]:o.y2[0] + C]
@@ -307,7 +323,7 @@ def check(p: Prob, o: Opt, got, v0):
         print("   differential: %.2f ulp of the largest operand" % worst)
         assert worst <= 2.0, ("y against (v0 + res) + old beyond the contraction's last bit", worst)
     if o.uact >= 0:
-        c0, c1 = emit_range(C)
+        c0, c1 = emit_of(o, C)
         untouched("uo", (o.u[0] + c0, 0), c1 - c0)
         uw = body(got["uo"])[:, o.u[0] + c0:o.u[0] + c1]
         assert rel(uw, ref_u[:, o.u[0] + c0:o.u[0] + c1]) < 2e-4
@@ -315,6 +331,7 @@ def check(p: Prob, o: Opt, got, v0):
         expu = yw[:, c0:c1] * dfo32(ua, o.uact, o.ualpha)
         assert torch.equal(uw, expu), ("u is not y * act'(ua) in float32", int((uw != expu).sum()))
         assert torch.equal(uw[ua == 0], (yw[:, c0:c1] * (LEAKY if o.uact == ACT_LEAKY else np.float32(1)))[ua == 0])
+    return e
 
 
 def run(devel, p: Prob, opts, force=None, expect=None):

@@ -186,3 +186,65 @@ def test_conv2d_ex_refuses_a_bad_workspace(devel, base):
         with pytest.raises(ValueError, match="libudet error -5:.*workspace"):
             devel.conv2d_ex(workspace=ws, stream=0, **base)
     assert devel.conv2d_ex_workspace_bytes(form=5, kc=8, cin=8, cout=8, k=3) == 0
+
+
+# ---- the refusals of udet_debug_conv2d_pair_ex: the same discipline for two structs ----------------------------------------------------------
+PAIR_FWD = dict(GOOD, k_split=32, k_gap=0, cin=32)                      # a plain forward problem: what fwd_is_plain lets a pair carry
+PAIR_BWD = dict(GOOD_BWD)
+PAIR_BWD_S2 = dict(GOOD_BWD, stride=2, h=8, wd=12)                      # stride 2 on an even grid: four merged classes, ONE launch
+OWN = [  # a struct's own refusals, forwarded: a few of each error class
+    (PAIR_FWD, dict(x=0), ERR_ARG), (PAIR_FWD, dict(stride=3), ERR_ARG), (PAIR_BWD, dict(bias=P16), ERR_ARG), (PAIR_BWD, dict(ua=0), ERR_ARG),
+    (PAIR_FWD, dict(ldx=50), ERR_ALIGN), (PAIR_FWD, dict(x=P16 + 4), ERR_ALIGN), (PAIR_BWD, dict(ua=P16 + 2), ERR_ALIGN),
+    (PAIR_FWD, dict(x_coff=20), ERR_SHAPE), (PAIR_FWD, dict(y_coff=17), ERR_SHAPE), (PAIR_BWD, dict(u_c1=17), ERR_SHAPE),
+    (PAIR_BWD, dict(ldy=16, y_coff=4), ERR_SHAPE),
+]
+PAIR_ONLY = [  # what the single entry takes and a pair does not
+    (GOOD_BWD, dict(form=3, k_split=8), ERR_ARG), (dict(PAIR_FWD, cin=32, cout=8), dict(form=2), ERR_ARG),   # forms 2 / 3
+    (PAIR_FWD, dict(up=1), ERR_ARG),
+    (PAIR_BWD_S2, dict(h=7), ERR_ARG), (PAIR_BWD_S2, dict(wd=11), ERR_ARG), (PAIR_BWD_S2, dict(h=7, wd=11), ERR_ARG),   # one launch per class
+]
+PAIR_REFUSALS = [(which, base, change, code) for base, change, code in OWN + PAIR_ONLY for which in (0, 1)]
+
+
+def _pair_partner(base):
+    return PAIR_BWD if base["form"] in (1, 3) else PAIR_FWD
+
+
+@pytest.mark.parametrize("which,base,change,code", PAIR_REFUSALS)
+def test_conv2d_pair_ex_refuses_before_any_hip_call(devel, which, base, change, code):
+    """problem `which` carries the fault, the other one is sound: either position is checked"""
+    bad, good = dict(base, **change), _pair_partner(base)
+    with pytest.raises(ValueError, match=f"libudet error {code}:.*debug_conv2d_pair_ex"):
+        devel.conv2d_pair_ex(*((good, bad) if which else (bad, good)), workspace=(P16, 1 << 40), stream=0)
+
+
+def test_conv2d_pair_ex_takes_what_the_single_entry_takes_of_those_bases(devel):
+    """the bases of PAIR_ONLY are sound for udet_debug_conv2d_ex with the same change (so the pair's refusal is the pair's own); of these the
+    single entry refuses only a bad workspace here"""
+    for base, change, _ in PAIR_ONLY:
+        f = dict(base, **change)
+        assert devel.conv2d_ex_workspace_bytes(**f) > 0
+        with pytest.raises(ValueError, match="libudet error -5:.*workspace"):
+            devel.conv2d_ex(workspace=(0, 1 << 40), stream=0, **f)
+
+
+@pytest.mark.parametrize("a,b", [(None, PAIR_FWD), (PAIR_FWD, None), (None, None)])
+def test_conv2d_pair_ex_refuses_a_null_struct(devel, a, b):
+    with pytest.raises(ValueError, match="libudet error -5:.*debug_conv2d_pair_ex"):
+        devel.conv2d_pair_ex(a, b, workspace=(P16, 1 << 40), stream=0)
+    assert devel.conv2d_pair_ex_workspace_bytes(a, b) == 0
+
+
+@pytest.mark.parametrize("a,b", [(PAIR_FWD, dict(PAIR_FWD, n=3, cout=12, ldy=28, ldres=16, ldy2=12)),(PAIR_BWD, PAIR_BWD_S2), (PAIR_BWD_S2, PAIR_FWD)])
+def test_conv2d_pair_ex_workspace_formula_and_a_bad_workspace(devel, a, b):
+    """header of 4224 floats, the two packed-weight regions (each rounded up to 64 floats), ONE 8 Mi split-K region"""
+    def wfl(f):
+        nout = f["cin"] if f["form"] == 1 else f["cout"]
+        return (f["k"] ** 2 * f["kc"] * ((nout + 3) // 4 * 4) + 63) // 64 * 64
+    need = devel.conv2d_pair_ex_workspace_bytes(a, b)
+    assert need == 4 * (4224 + wfl(a) + wfl(b) + (8 << 20))
+    assert need == devel.conv2d_ex_workspace_bytes(**a) + 4 * wfl(b)
+    for ws in ((0, need), (P16 + 32, need), (P16, need - 4)):
+        with pytest.raises(ValueError, match="libudet error -5:.*debug_conv2d_pair_ex.*workspace"):
+            devel.conv2d_pair_ex(a, b, workspace=ws, stream=0)
+    assert devel.conv2d_pair_ex_workspace_bytes(a, dict(b, form=5)) == 0

@@ -503,8 +503,12 @@ PAIR_CASES = [
 @pytest.mark.parametrize("case", PAIR_CASES)
 def test_conv_pair_launch(ops, case):
     """Two convolutions of the same geometry (separate inputs / weights / biases / outputs, different batches) in ONE launch
-    (launch_conv_pair, conv_igemm_dma_pair_kernel): each result against the float64 oracle, and bit-identical to the same two problems
-    launched apart on the same kernel family."""
+    (launch_conv_pair, conv_igemm_dma_pair_kernel): each result against the float64 oracle, paired and apart on the built-in choices, and
+    bit-identical to the same two problems launched apart where that can hold: both forced to the same tile and ring
+    (udet_debug_force_conv under udet_debug_force_pair(1) / (0)) with a split count below 4 -- the same kernel body, tile, K-slice
+    boundaries and, in the second pass, the same slab order per element.  On the built-in choices it does not hold: apart, the heuristic
+    picks another family (and tile) than pair_heuristic, and from 4 slices on the single launch's second pass sums the slabs with 4 or 16
+    lanes per element in interleaved order, the pair's always in slab order."""
     import ctypes
     from unsupervised_detection_amd._devel import dbg
     na, nb, h, w, cin, cout, k, s, d = case
@@ -518,18 +522,24 @@ def test_conv_pair_launch(ops, case):
     work = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
     stream = torch.cuda.current_stream().cuda_stream
 
-    def run(force):
+    def run(force, cfg=None):
         ys = [torch.full((n, oh, ow, cout), float("nan"), device="cuda") for n in (na, nb)]
         try:
             dbg.udet_debug_force_pair(force)
+            if cfg:
+                dbg.udet_debug_force_conv(*cfg)
             rc = dbg.udet_debug_conv2d_pair(g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), g[3].data_ptr(), g[4].data_ptr(), g[5].data_ptr(),
                                             ys[0].data_ptr(), ys[1].data_ptr(), na, nb, h, w, cin, cout, k, s, d, 1, ctypes.c_float(0.2),
                                             work.data_ptr(), ws_bytes, stream)
             paired = dbg.udet_debug_last_pair()
+            last = dbg.udet_debug_last_conv()
         finally:
             dbg.udet_debug_force_pair(-1)
+            dbg.udet_debug_force_conv(0, 0, -1)
         assert rc == 0
         torch.cuda.synchronize()
+        if cfg:
+            return [y.cpu() for y in ys], paired, last
         return [y.cpu() for y in ys], paired
 
     got, paired = run(1)
@@ -539,6 +549,19 @@ def test_conv_pair_launch(ops, case):
     for y, y0, ref in zip(got, apart, refs):
         assert float((y - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
         assert float((y0 - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
+    # 128 x 64 on the 2- and the 3-stage ring, second-launch summation (bit 20), 1 and 3 slices asked for (clamped to the capacity)
+    for bit, fam in ((1 << 17, 2), (1 << 22, 4)):
+        for ks in (1, 3):
+            cfg = (128 + bit + (1 << 20), 64, ks)
+            got, paired, last = run(1, cfg)
+            apart, paired0, last0 = run(0, cfg)
+            assert (paired, paired0, (last >> 30) & 1, (last0 >> 30) & 1) == (1, 0, 1, 0), (paired, paired0, hex(last), hex(last0))
+            assert last & 0xfffff == last0 & 0xfffff == fam | (128 << 8), (hex(last), hex(last0))
+            ran = (last >> 20) & 0xff
+            assert 1 <= ran <= ks and ran == (last0 >> 20) & 0xff, (hex(last), hex(last0))
+            for y, y0, ref in zip(got, apart, refs):
+                assert float((y - ref).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
+                assert torch.equal(y, y0), ("pair != apart", cfg, int((y != y0).sum()))
 
 
 def _tune_file_lines(path):

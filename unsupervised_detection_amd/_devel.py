@@ -86,11 +86,13 @@ dbg.udet_debug_conv2d_ex.restype = ctypes.c_int
 dbg.udet_debug_conv2d_ex.argtypes = [ctypes.POINTER(ConvEx), _p, ctypes.c_size_t, _p]
 
 
-def conv2d_ex(workspace=None, stream=None, **fields):
-    """udet_debug_conv2d_ex with the struct's fields as keywords (tensors: their data pointers, or (tensor, element offset) for a pointer into
-    one); workspace: a float32 device tensor of conv2d_ex_workspace_bytes(**fields) bytes, or (pointer, bytes).  A refusal raises
-    ValueError (_ffi.check) before anything reaches the device; a pointer given as a plain int is passed as it is."""
-    a = conv_ex_args(**fields)
+dbg.udet_debug_conv2d_pair_ex_workspace_bytes.restype = ctypes.c_size_t
+dbg.udet_debug_conv2d_pair_ex_workspace_bytes.argtypes = [ctypes.POINTER(ConvEx), ctypes.POINTER(ConvEx)]
+dbg.udet_debug_conv2d_pair_ex.restype = ctypes.c_int
+dbg.udet_debug_conv2d_pair_ex.argtypes = [ctypes.POINTER(ConvEx), ctypes.POINTER(ConvEx), _p, ctypes.c_size_t, _p]
+
+
+def _workspace_and_stream(workspace, stream):
     if workspace is None or isinstance(workspace, tuple):
         ptr, nbytes = workspace or (None, 0)
     else:
@@ -98,7 +100,27 @@ def conv2d_ex(workspace=None, stream=None, **fields):
     if stream is None:
         import torch
         stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
-    _check(dbg.udet_debug_conv2d_ex(ctypes.byref(a), ptr, nbytes, stream))
+    return ptr, nbytes, stream
+
+
+def conv2d_pair_ex(a_fields, b_fields, workspace=None, stream=None):
+    """udet_debug_conv2d_pair_ex: two problems, each a dict of the struct's fields as conv2d_ex takes them (None: a NULL struct), through
+    the pair launcher; workspace: a float32 device tensor of conv2d_pair_ex_workspace_bytes(a_fields, b_fields) bytes, or (pointer, bytes)."""
+    a, b = (None if f is None else ctypes.byref(conv_ex_args(**f)) for f in (a_fields, b_fields))
+    _check(dbg.udet_debug_conv2d_pair_ex(a, b, *_workspace_and_stream(workspace, stream)))
+
+
+def conv2d_pair_ex_workspace_bytes(a_fields, b_fields) -> int:
+    a, b = (None if f is None else ctypes.byref(conv_ex_args(**f)) for f in (a_fields, b_fields))
+    return int(dbg.udet_debug_conv2d_pair_ex_workspace_bytes(a, b))
+
+
+def conv2d_ex(workspace=None, stream=None, **fields):
+    """udet_debug_conv2d_ex with the struct's fields as keywords (tensors: their data pointers, or (tensor, element offset) for a pointer into
+    one); workspace: a float32 device tensor of conv2d_ex_workspace_bytes(**fields) bytes, or (pointer, bytes).  A refusal raises
+    ValueError (_ffi.check) before anything reaches the device; a pointer given as a plain int is passed as it is."""
+    a = conv_ex_args(**fields)
+    _check(dbg.udet_debug_conv2d_ex(ctypes.byref(a), *_workspace_and_stream(workspace, stream)))
 
 
 def conv_ex_args(**fields) -> ConvEx:

@@ -132,6 +132,7 @@ static ConvCfg runnable_cfg(const ConvParams& p, ConvCfg c) {
 // tail_rounds > 0: tail split for this many workgroup slots per CU
 struct ConvForce {
   int bm = 0, bn = 0, ks = -1, family = -1, fold = -1, tail_rounds = 0;
+  bool ring3 = false;  // bit 22 itself, whatever lower family bit won: all a pair launch takes of the family bits
   bool any() const { return bm || family >= 0 || ks >= 0; }
 };
 static ConvForce g_force;
@@ -141,6 +142,7 @@ void conv_force_config(int bm, int bn, int ks) {
   f.ks = ks < 0 ? ks : (ks & 0xff);
   f.tail_rounds = ks < 0 ? 0 : ((ks >> 8) & 0xff);  // ks + 256 r: tail split for r slots per CU (ks & 255 slices; 0: as many as fill a round)
   f.fold = (bm >> 20) & 1 ? 0 : ((bm >> 21) & 1 ? 1 : -1);
+  f.ring3 = ((bm >> 22) & 1) != 0;
   // the family bits of bm, the lowest set one wins (bit 24: the direct kernel the launch is eligible for; bit 25: bm & 0xffff = variant)
   static const int BITS[][2] = {{16, FAM_PLAIN}, {17, FAM_DMA2}, {18, FAM_TILE}, {19, FAM_SELF_STAGING},
                                 {22, FAM_DMA3}, {23, FAM_DMA4}, {24, FAM_THIN_K}, {25, FAM_WINO}};
@@ -295,6 +297,17 @@ static bool pair_compatible(const ConvParams& a, const ConvParams& b) {
     if (a.taps[t].dy != b.taps[t].dy || a.taps[t].dx != b.taps[t].dx) return false;
   return true;
 }
+// the configuration a test pins for a pair (udet_debug_force_conv while udet_debug_force_pair(1) is set): the forced tile where it is
+// instantiated, the ring of bit 22, the forced split count (clamped by the caller); fold, tail split and the other family bits have
+// no pair form and are ignored.  Neither the pair cache nor the tuner is asked.
+static ConvCfg forced_pair_cfg(const ConvParams& a, const ConvParams& b) {
+  const ConvForce& f = g_force;
+  ConvCfg c = pair_heuristic(a, b);
+  if (f.bm && conv_gemm_tile(f.bm, f.bn)) { c.bm = f.bm; c.bn = f.bn; }
+  c.family = f.ring3 ? FAM_DMA3 : FAM_DMA2;
+  if (f.ks >= 0) c.ks = f.ks;
+  return c;
+}
 // Both problems in one launch where that is eligible and (tuned) faster; otherwise the two ordinary launches, a first.
 int launch_conv_pair(ConvParams& a, ConvParams& b, hipStream_t stream) {
   g_last_pair = 0;
@@ -307,7 +320,9 @@ int launch_conv_pair(ConvParams& a, ConvParams& b, hipStream_t stream) {
   }
   ConvCfg c;
   const uint64_t key = pair_key(a, b);
-  if (pair_cache_find(key, &c)) {
+  if (g_force_pair == 1 && g_force.any()) {
+    c = forced_pair_cfg(a, b);
+  } else if (pair_cache_find(key, &c)) {
     if (c.family >= 0) {  // (an entry from a file: instantiated tiles and ring depths only)
       if (!conv_gemm_tile(c.bm, c.bn) || (c.family != FAM_DMA2 && c.family != FAM_DMA3)) c = pair_heuristic(a, b);
       if (c.ks < 1) c.ks = 1;
@@ -321,6 +336,9 @@ int launch_conv_pair(ConvParams& a, ConvParams& b, hipStream_t stream) {
     return launch_conv(b, stream);
   }
   g_last_pair = 1;
+  // (the split count that runs: launch_conv_gemm_pair clamps to the same capacity)
+  const int cap = pair_max_ksplit(a, b);
+  c.ks = c.ks > cap ? cap : (c.ks < 1 ? 1 : c.ks);
   g_last_cfg = config_word(c) | (1 << 30);
   return launch_conv_gemm_pair(a, b, c, stream);
 }

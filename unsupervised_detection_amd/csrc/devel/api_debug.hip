@@ -278,8 +278,9 @@ size_t cex_weight_floats(const udet_debug_conv_ex& a) {
 bool cex_known_act(int act) { return act == UDET_ACT_NONE || act == UDET_ACT_LEAKY || act == UDET_ACT_ELU; }
 // a window [coff, coff + c) of a row of ld floats
 bool cex_outside(int ld, int coff, int c) { return ld < 1 || coff < 0 || (long)coff + c > ld; }
-int cex_check(const udet_debug_conv_ex& a, const void* workspace, size_t workspace_bytes) {
-  const char* who = "debug_conv2d_ex";
+bool cex_misaligned(const void* q, unsigned b) { return (reinterpret_cast<uintptr_t>(q) & (b - 1)) != 0; }
+// everything about one struct but its workspace
+int cex_check_args(const udet_debug_conv_ex& a, const char* who) {
   if (a.form < 0 || a.form > 3) { set_error("%s: unknown form %d", who, a.form); return UDET_ERR_ARG; }
   if (!a.x || !a.w || !a.y) { set_error("%s: x, w and y must not be NULL", who); return UDET_ERR_ARG; }
   if (a.n < 1 || a.h < 1 || a.wd < 1 || a.cin < 1 || a.cout < 1 || a.k < 1 || a.k * a.k > UDET_MAX_TAPS || a.dilation < 1 ||
@@ -303,7 +304,7 @@ int cex_check(const udet_debug_conv_ex& a, const void* workspace, size_t workspa
   }
   if (a.uo && !a.ua) { set_error("%s: uo needs ua", who); return UDET_ERR_ARG; }
   // alignment: the A operand is read in float4 groups; every pointer holds floats
-  auto mis = [](const void* q, unsigned b) { return (reinterpret_cast<uintptr_t>(q) & (b - 1)) != 0; };
+  auto mis = cex_misaligned;
   if (a.ldx % 4 || a.x_coff % 4 || a.kc % 4 || mis(a.x, 16) || (a.xa && mis(a.xa, 16))) {
     set_error("%s: ldx=%d x_coff=%d kc=%d must be multiples of 4 and x / xa 16-byte aligned", who, a.ldx, a.x_coff, a.kc);
     return UDET_ERR_ALIGN;
@@ -327,12 +328,66 @@ int cex_check(const udet_debug_conv_ex& a, const void* workspace, size_t workspa
     set_error("%s: emission columns [%d, %d) outside the launch's %d columns or the rows of uo / ua", who, a.u_c0, a.u_c1, nout);
     return UDET_ERR_SHAPE;
   }
-  if (!workspace || mis(workspace, 64) || workspace_bytes < udet_debug_conv2d_ex_workspace_bytes(&a)) {
+  return UDET_OK;
+}
+int cex_check(const udet_debug_conv_ex& a, const void* workspace, size_t workspace_bytes) {
+  const char* who = "debug_conv2d_ex";
+  UDET_TRY(cex_check_args(a, who));
+  if (!workspace || cex_misaligned(workspace, 64) || workspace_bytes < udet_debug_conv2d_ex_workspace_bytes(&a)) {
     set_error("%s: workspace must be 64-byte aligned and hold udet_debug_conv2d_ex_workspace_bytes", who);
     return UDET_ERR_ARG;
   }
   return UDET_OK;
 }
+// the weights of `a` packed to ws + w_off by one of the two packers of a plan: launch_pack_weights (pack_weights_kernel: the PWC-Net layers,
+// packed once) or the per-step job table of the trainable networks (pack_jobs_kernel), which has its own copy of the gap map and the only
+// form of modes 5 / 6.  j: the caller's host copy of the job, alive until the stream is synchronised.
+int cex_pack(const udet_debug_conv_ex& a, float* ws, size_t w_off, PackJob& j, hipStream_t stream) {
+  const int ldw = round_up(cex_backward(a.form) ? a.cin : a.cout, 4);
+  if (a.form < 2 && !a.pack_job)
+    return launch_pack_weights(a.w, ws + w_off, a.k * a.k, a.cin, a.cout, a.kc, ldw, a.k_split, a.k_gap, a.form, nullptr, stream);
+  memset(&j, 0, sizeof(j));
+  j.gamma_off = j.beta_off = -1;
+  j.dst_off = (long)w_off; j.T = cex_taps(a); j.R = a.cin; j.C = a.cout; j.Kc = a.kc; j.ldw = ldw; j.k_split = a.k_split; j.k_gap = a.k_gap;
+  j.mode = a.form < 2 ? a.form : (a.form == 2 ? 5 : 6); j.total = (long)j.T * a.kc * ldw;
+  UDET_HIP(hipMemcpyAsync(ws + CEX_JOB, &j, sizeof(j), hipMemcpyHostToDevice, stream));
+  return launch_pack_jobs(reinterpret_cast<const PackJob*>(ws + CEX_JOB), 1, a.w, ws, 1.f, stream);
+}
+// launch `cls` of `a` as a parameter block: the project's setup function, then the operands and options; false: a class without a launch
+bool cex_params(const udet_debug_conv_ex& a, int cls, float* ws, const float* wp, float* part, ConvParams& p) {
+  const bool bwd = cex_backward(a.form);
+  const int nout = bwd ? a.cin : a.cout;
+  memset(&p, 0, sizeof(p));
+  if (a.form == 0) {
+    conv_setup_fwd(p, a.n, a.h << a.up, a.wd << a.up, a.k, a.k, a.stride, a.dilation);
+    p.up_shift = a.up;
+  } else if (a.form == 1) {
+    if (!conv_setup_dgrad(p, cls, a.n, a.h, a.wd, a.k, a.k, a.stride, a.dilation)) return false;
+  } else if (a.form == 2) {
+    setup_up_fwd(p, a.n, a.h, a.wd);
+  } else {
+    setup_up_dgrad(p, a.n, a.h, a.wd);
+  }
+  p.x = a.x; p.ldx = a.ldx; p.x_coff = a.x_coff;
+  if (a.xa && a.xact != UDET_ACT_NONE) { p.xa = a.xa; p.xact = a.xact; p.xalpha = a.xalpha; }
+  p.wp = wp; p.Kc = a.kc; p.ldw = round_up(nout, 4); p.bias = a.bias;
+  if (bwd) { p.kreal = a.cout; p.f16_xscale = conv_debug_f16_grad_scale_now(); }  // (the x operand is a gradient; 0: none)
+  p.y = a.y; p.ldy = a.ldy; p.y_coff = a.y_coff; p.Cout = nout;
+  p.act = a.act; p.alpha = a.alpha;
+  if (a.res) { p.res = a.res; p.ldres = a.ldres; p.res_coff = a.res_coff; }
+  if (a.y2) { p.y2 = a.y2; p.ldy2 = a.ldy2; p.y2_coff = a.y2_coff; }
+  p.accumulate = a.accumulate;
+  if (a.uo) {
+    p.uo = a.uo; p.ldu = a.ldu; p.u_coff = a.u_coff;
+    p.ua = a.ua; p.ldua = a.ldua; p.ua_coff = a.ua_coff;
+    p.uact = a.uact; p.ualpha = a.ualpha; p.u_c0 = a.u_c0; p.u_c1 = a.u_c1;
+  }
+  p.partial = part; p.partial_cap = CEX_SLAB_FLOATS;
+  p.zero16 = ws; p.tickets = reinterpret_cast<int*>(ws + CEX_TICKETS);
+  return true;
+}
+// what a pair launch carries (plan_exec.hip fwd_is_plain / dgrad_is_plain): a plain forward launch, or a backward-data pass that is ONE launch
+bool cex_pair_form(const udet_debug_conv_ex& a) { return (a.form == 0 || a.form == 1) && a.up == 0; }
 }  // namespace
 extern "C" {
 size_t udet_debug_conv2d_ex_workspace_bytes(const udet_debug_conv_ex* a) {
@@ -347,55 +402,54 @@ int udet_debug_conv2d_ex(const udet_debug_conv_ex* args, void* workspace, size_t
   float* ws = reinterpret_cast<float*>(workspace);
   float* wp = ws + CEX_W;
   float* part = wp + cex_weight_floats(a);
-  const bool bwd = cex_backward(a.form);
-  const int nout = bwd ? a.cin : a.cout, ldw = round_up(nout, 4);
   UDET_HIP(hipMemsetAsync(ws, 0, CEX_JOB * sizeof(float), stream));  // zero block + ticket counters
-  // the two packers of a plan: launch_pack_weights (pack_weights_kernel: the PWC-Net layers, packed once) and the per-step job table of the
-  // trainable networks (pack_jobs_kernel), which has its own copy of the gap map and the only form of modes 5 / 6
   PackJob j;  // (a host temporary: the stream is synchronised below)
-  if (a.form < 2 && !a.pack_job) {
-    UDET_TRY(launch_pack_weights(a.w, wp, a.k * a.k, a.cin, a.cout, a.kc, ldw, a.k_split, a.k_gap, a.form, nullptr, stream));
-  } else {
-    memset(&j, 0, sizeof(j));
-    j.gamma_off = j.beta_off = -1;
-    j.dst_off = CEX_W; j.T = cex_taps(a); j.R = a.cin; j.C = a.cout; j.Kc = a.kc; j.ldw = ldw; j.k_split = a.k_split; j.k_gap = a.k_gap;
-    j.mode = a.form < 2 ? a.form : (a.form == 2 ? 5 : 6); j.total = (long)j.T * a.kc * ldw;
-    UDET_HIP(hipMemcpyAsync(ws + CEX_JOB, &j, sizeof(j), hipMemcpyHostToDevice, stream));
-    UDET_TRY(launch_pack_jobs(reinterpret_cast<const PackJob*>(ws + CEX_JOB), 1, a.w, ws, 1.f, stream));
-  }
+  UDET_TRY(cex_pack(a, ws, CEX_W, j, stream));
   int st = UDET_OK;
   const int launches = a.form == 1 ? conv_dgrad_classes(a.stride, a.h, a.wd) : 1;
   for (int cls = 0; cls < launches && st == UDET_OK; ++cls) {
     ConvParams p;
-    memset(&p, 0, sizeof(p));
-    if (a.form == 0) {
-      conv_setup_fwd(p, a.n, a.h << a.up, a.wd << a.up, a.k, a.k, a.stride, a.dilation);
-      p.up_shift = a.up;
-    } else if (a.form == 1) {
-      if (!conv_setup_dgrad(p, cls, a.n, a.h, a.wd, a.k, a.k, a.stride, a.dilation)) continue;
-    } else if (a.form == 2) {
-      setup_up_fwd(p, a.n, a.h, a.wd);
-    } else {
-      setup_up_dgrad(p, a.n, a.h, a.wd);
-    }
-    p.x = a.x; p.ldx = a.ldx; p.x_coff = a.x_coff;
-    if (a.xa && a.xact != UDET_ACT_NONE) { p.xa = a.xa; p.xact = a.xact; p.xalpha = a.xalpha; }
-    p.wp = wp; p.Kc = a.kc; p.ldw = ldw; p.bias = a.bias;
-    if (bwd) { p.kreal = a.cout; p.f16_xscale = conv_debug_f16_grad_scale_now(); }  // (the x operand is a gradient; 0: none)
-    p.y = a.y; p.ldy = a.ldy; p.y_coff = a.y_coff; p.Cout = nout;
-    p.act = a.act; p.alpha = a.alpha;
-    if (a.res) { p.res = a.res; p.ldres = a.ldres; p.res_coff = a.res_coff; }
-    if (a.y2) { p.y2 = a.y2; p.ldy2 = a.ldy2; p.y2_coff = a.y2_coff; }
-    p.accumulate = a.accumulate;
-    if (a.uo) {
-      p.uo = a.uo; p.ldu = a.ldu; p.u_coff = a.u_coff;
-      p.ua = a.ua; p.ldua = a.ldua; p.ua_coff = a.ua_coff;
-      p.uact = a.uact; p.ualpha = a.ualpha; p.u_c0 = a.u_c0; p.u_c1 = a.u_c1;
-    }
-    p.partial = part; p.partial_cap = CEX_SLAB_FLOATS;
-    p.zero16 = ws; p.tickets = reinterpret_cast<int*>(ws + CEX_TICKETS);
+    if (!cex_params(a, cls, ws, wp, part, p)) continue;
     st = launch_conv(p, stream);
   }
+  const hipError_t e = hipStreamSynchronize(stream);  // (a fault in the launch is this call's error, not the caller's next one)
+  if (st == UDET_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(stream)");
+  return st;
+}
+// two such launches through launch_conv_pair, handed over as a lane hands its couples over: separate packed weights, ONE zero block, one set of
+// ticket counters and one split-K scratch region (a.partial == b.partial, one partial_cap)
+size_t udet_debug_conv2d_pair_ex_workspace_bytes(const udet_debug_conv_ex* a, const udet_debug_conv_ex* b) {
+  if (!udet_debug_conv2d_ex_workspace_bytes(a) || !udet_debug_conv2d_ex_workspace_bytes(b)) return 0;
+  return (CEX_W + cex_weight_floats(*a) + cex_weight_floats(*b) + CEX_SLAB_FLOATS) * sizeof(float);
+}
+int udet_debug_conv2d_pair_ex(const udet_debug_conv_ex* a_, const udet_debug_conv_ex* b_, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const char* who = "debug_conv2d_pair_ex";
+  if (!a_ || !b_) { set_error("%s: bad argument", who); return UDET_ERR_ARG; }
+  const udet_debug_conv_ex* q[2] = {a_, b_};
+  for (const udet_debug_conv_ex* a : q) {
+    UDET_TRY(cex_check_args(*a, who));
+    if (!cex_pair_form(*a)) { set_error("%s: a pair carries forms 0 / 1 with up = 0 only", who); return UDET_ERR_ARG; }
+    if (a->form == 1 && conv_dgrad_classes(a->stride, a->h, a->wd) != 1) {
+      set_error("%s: backward-data of stride 2 on an odd grid is one launch per class: never a pair", who);
+      return UDET_ERR_ARG;
+    }
+  }
+  if (!workspace || cex_misaligned(workspace, 64) || workspace_bytes < udet_debug_conv2d_pair_ex_workspace_bytes(a_, b_)) {
+    set_error("%s: workspace must be 64-byte aligned and hold udet_debug_conv2d_pair_ex_workspace_bytes", who);
+    return UDET_ERR_ARG;
+  }
+  float* ws = reinterpret_cast<float*>(workspace);
+  const size_t w_off[2] = {CEX_W, CEX_W + cex_weight_floats(*a_)};
+  float* part = ws + w_off[1] + cex_weight_floats(*b_);
+  UDET_HIP(hipMemsetAsync(ws, 0, CEX_JOB * sizeof(float), stream));  // zero block + ticket counters
+  PackJob j[2];  // (host temporaries: the job slot is rewritten in stream order, the stream is synchronised below)
+  ConvParams p[2];
+  for (int i = 0; i < 2; ++i) {
+    UDET_TRY(cex_pack(*q[i], ws, w_off[i], j[i], stream));
+    (void)cex_params(*q[i], 0, ws, ws + w_off[i], part, p[i]);  // (one class: checked above)
+  }
+  const int st = launch_conv_pair(p[0], p[1], stream);
   const hipError_t e = hipStreamSynchronize(stream);  // (a fault in the launch is this call's error, not the caller's next one)
   if (st == UDET_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(stream)");
   return st;
