@@ -867,6 +867,37 @@ int udet_follow_tracks_ragged(const int* labels, int n, const long long* offsets
                               const unsigned long long* keep, const unsigned char* gt, unsigned char* selected, long long* stats,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* Tracks against multi-object annotations (csrc/objects.hip): what the one-to-one matching of annotated objects to
+ * tracks needs from the pixels, counted on the device.  labels, n, offsets, hw, max_h, max_w, total_pixels, dets, counts and k are what
+ * udet_track_instance_maps_ragged takes; objects: device uint8 packed like labels, 0 background, 1..num_objects an annotated object,
+ * anything above num_objects "void"; num_objects (O) in 1..UDET_MAX_OBJECTS.  row_obj: device int64 [n][k][O]; obj_area: device int64
+ * [n][O]; frame_stats: device int64 [n][2].  With rows_i = counts[i][2] clamped to 0..k:
+ *   row_obj[i][r][o]  the pixels whose label is the root of row r (L - 1 == dets[i][r][0], r < rows_i) and whose object byte is o + 1;
+ *                     0 for r >= rows_i;
+ *   obj_area[i][o]    the pixels of sample i with object byte o + 1, whatever their label;
+ *   frame_stats[i]    {pixels with byte in 1..O, pixels with byte > O}.
+ * A label outside 1..H_i*W_i is background, as for the other calls.
+ * Two launches whatever n, k, O and the content are, no host round trip, no workgroup waits for another, integer atomics only: the
+ * outputs are exact, identical from run to run and for a sample alone or inside a batch.  The first launch zeroes the three outputs
+ * and enters every row's rank at its root in the workspace (the lookup of the link: one int32 per pixel, never zeroed, a lookup counts
+ * only when the row it names holds that root); the second takes one pixel per lane, 64 consecutive pixels of one sample per wave, 4096
+ * pixels per workgroup: the object byte is one coalesced byte load per lane, a pair (r, o) is counted by one LDS atomic per horizontal
+ * run of a wave into k x O partials and an object's own pixels by one per run into O partials (dynamic LDS, (k O + O) ints: 8.3 KB at
+ * most), the two frame counts are ballots; then one 64-bit integer atomic per non-zero partial per workgroup.  Nothing is written per
+ * pixel.
+ * workspace: udet_track_object_overlaps_workspace_bytes(total_pixels, n, k) bytes (4 per pixel), 4-byte aligned; 0 for bad arguments.
+ * UDET_ERR_ARG, nothing enqueued: a NULL labels, offsets, hw, dets, counts, objects, row_obj, obj_area or frame_stats, n outside
+ * 1..65535, k outside 1..UDET_DET_MAX_K, num_objects outside 1..UDET_MAX_OBJECTS, max_h or max_w < 1, total_pixels < 1, a short or
+ * misaligned workspace, labels not 4-byte or dets / counts / row_obj / obj_area / frame_stats not 8-byte aligned.  Every index a kernel
+ * forms is bounded, whatever labels, dets, counts, objects and the workspace hold; the tables are device memory: the host caller
+ * validates them (native_objects.object_overlaps). */
+#define UDET_MAX_OBJECTS 32
+size_t udet_track_object_overlaps_workspace_bytes(size_t total_pixels, int n, int k);
+int udet_track_object_overlaps_ragged(const int* labels, int n, const long long* offsets, const int* hw, int max_h, int max_w,
+                                      size_t total_pixels, const long long* dets, const long long* counts, int k,
+                                      const unsigned char* objects, int num_objects, long long* row_obj, long long* obj_area,
+                                      long long* frame_stats, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,9 @@ sig("udet_overlay_instances_ragged", c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_s
 # the masks of whole tracks (native_follow.follow_tracks)
 sig("udet_follow_tracks_workspace_bytes", c_sz, c_sz, c_i, c_i)
 sig("udet_follow_tracks_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, ctypes.c_longlong, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_sz, c_p)
+# tracks against multi-object annotations (native_objects.object_overlaps)
+sig("udet_track_object_overlaps_workspace_bytes", c_sz, c_sz, c_i, c_i)
+sig("udet_track_object_overlaps_ragged", c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_sz, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p)
 sig("udet_histogram_limits", c_i, c_p, c_i)
 sig("udet_grad_histogram_workspace_bytes", c_sz, c_i)
 sig("udet_grad_histogram", c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_sz, c_p)

@@ -19,12 +19,14 @@
                                                       [--track_motion] [--track_motion_size 384 640]
                                                       [--instances] [--overlay_instances]
                                                       [--follow none|mass|area|length|best_gt|all] [--track_min_frames 1]
+                                                      [--objects] [--objects_max 16] [--objects_dir D]
   python -m unsupervised_detection_amd.cli post_process --buffer_dir B --out_dir O [--dprefix davis_shift] [--max_shift 2]
                                                       [--sxy 25] [--srgb 5] [--scomp 5] [--gauss_k 0.1] [--crf_batch 16] [--flow_batch 8]
                                                       [--score_batch 0]
                                                       [--benchmark --dataset ... --root_dir ... [--native_sxy 60] [--component best_gt]
                                                        [--overlay ...] [--detections ...] [--overlay_boxes ...] [--tracks ...]
-                                                       [--instances] [--overlay_instances] [--follow ...] [--track_min_frames N]]
+                                                       [--instances] [--overlay_instances] [--follow ...] [--track_min_frames N]
+                                                       [--objects] [--objects_max O] [--objects_dir D]]
                                                                                                             (post_processing.py)
 
 test_generator --davis_metrics adds the DAVIS-2016 benchmark table (J and F: mean, recall, decay) to the reference's report;
@@ -94,7 +96,14 @@ summed score (mass), the largest summed area, the most frames (length) or -- wit
 against the annotation (best_gt), ties to the longer track, then the smaller id; all keeps every such track.  The stage then runs every
 sequence in two passes, a frame in which the followed track has no box exports an empty mask, the J / F table is that of one consistently
 followed object, native_eval.json gains follow and per sequence kept_mean, and the sequences of <out>/tracks/<sequence>.json gain followed
-(native_results.follow_tracks).
+(native_results.follow_tracks).  --objects (needs --tracks and annotations; the same three commands; with or without --instances,
+--follow, --track_max_gap and --track_motion) scores the tracks against multi-object annotations the way the DAVIS-2017 unsupervised
+protocol judges instance ids: every annotation is read as object ids (an indexed PNG's palette indices, a grey image's values; nothing is
+binarised), ids 1..--objects_max (1..32, default 16) are objects and anything above is void, from the dataset's own annotation files or,
+with --objects_dir D, from D/<sequence>/<frame>.png; every annotated object is matched to at most one track over its sequence,
+one-to-one, so that the summed mean J is largest, <out>/objects/<sequence>.json holds per object its track and J mean / recall / decay,
+the tracks of <out>/tracks/<sequence>.json gain object, and native_eval.json gains objects with the mean over all objects of all
+sequences (native_results.object_overlaps, native_results.match_tracks).
 Like the
 reference, a missing dataset, an unsupported --dataset or a missing
 --flow_ckpt is an IOError; --synthetic opts in to synthetic DAVIS-shaped pairs and seeded random weights (benchmarks, smoke
@@ -212,6 +221,12 @@ def _add_overlay_arguments(ap):
                     help="with --tracks: export and score the masks of whole tracks, one per sequence by its summed score (mass), summed "
                          "area, length or mean J against the annotation (best_gt), or all of them; not together with --component")
     ap.add_argument("--track_min_frames", type=int, default=1, help="with --follow: only tracks with boxes in at least this many frames")
+    ap.add_argument("--objects", action="store_true",
+                    help="with --tracks: match every object of a multi-object annotation to one track and report J per object: "
+                         "<out>/objects/<sequence>.json")
+    ap.add_argument("--objects_max", type=int, default=16, help="with --objects: annotation values 1..this are objects (1..32), above it void")
+    ap.add_argument("--objects_dir", default=None,
+                    help="with --objects: read the object ids from <objects_dir>/<sequence>/<frame>.png, not from the dataset's annotations")
 
 
 def _overlay(flags):
@@ -309,6 +324,25 @@ def _follow(flags):
         raise SystemExit("--follow: {} (--track_min_frames)".format(e))
 
 
+def _objects(flags):
+    """--objects, --objects_max and --objects_dir as restore_results_dir takes them: None without --objects.  --objects without --tracks or
+    on --dataset FRAMES, --objects_max / --objects_dir without --objects, or a bad value, is a SystemExit."""
+    most, folder = getattr(flags, "objects_max", 16), getattr(flags, "objects_dir", None)
+    if not getattr(flags, "objects", False):
+        if most != 16 or folder:
+            raise SystemExit("--objects_max / --objects_dir say how --objects reads the annotations: they need --objects")
+        return None
+    if not getattr(flags, "tracks", False):
+        raise SystemExit("--objects matches the annotated objects to the tracks: it needs --tracks")
+    if getattr(flags, "dataset", None) == "FRAMES":
+        raise SystemExit("--dataset FRAMES has no annotations: --objects needs them")
+    from .native_objects import object_params
+    try:
+        return object_params({"max": most, "dir": folder or None})
+    except ValueError as e:
+        raise SystemExit("--objects: {} (--objects_max / --objects_dir)".format(e))
+
+
 def check_frames_component(flags):
     """A folder of frames has no annotation to pick the best component by."""
     if getattr(flags, "dataset", None) == "FRAMES" and getattr(flags, "component", "none") == "best_gt":
@@ -364,6 +398,7 @@ def parse_restore_results_args(argv):
     _tracks(flags)
     _instances(flags)
     _follow(flags)
+    _objects(flags)
     return flags
 
 
@@ -407,6 +442,7 @@ def parse_post_process_args(argv):
         _tracks(flags)
         _instances(flags)
         _follow(flags)
+        _objects(flags)
     return flags
 
 
@@ -461,6 +497,8 @@ def post_process(a):
             more.update(instances=_instances(a))
         if _follow(a) is not None:
             more.update(follow=_follow(a))
+        if _objects(a) is not None:
+            more.update(objects=_objects(a))
         report["benchmark"] = pp.run_crf_original_resolution(resized, frame_lists_from_reader(a), a.native_sxy, a.srgb, a.scomp, a.gauss_k,
                                                              out_path=original, component=_component(a), gt_rule=a.dataset, **more)
     os.makedirs(a.out_dir, exist_ok=True)
@@ -498,6 +536,7 @@ def check_native_flags(flags):
         _tracks(flags)
         _instances(flags)
         _follow(flags)
+        _objects(flags)
 
 
 def main(argv=None):
@@ -513,7 +552,8 @@ def main(argv=None):
         from .native_results import frame_lists_from_reader, restore_results_dir
         restore_results_dir(a.results_dir, frame_lists_from_reader(a), a.out_dir, mask_key=a.mask_key, crop=a.crop, threshold=a.threshold,
                             batch=a.batch, gt_rule=a.dataset, skip_ends=not a.keep_ends, component=_component(a), connectivity=a.connectivity,
-                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a), instances=_instances(a), follow=_follow(a))
+                            crf=_crf(a), overlay=_overlay(a), detections=_detections(a), tracks=_tracks(a), instances=_instances(a), follow=_follow(a),
+                            objects=_objects(a))
         return 0
     if argv[0] == "davis_eval":
         a = parse_davis_eval_args(argv[1:])
@@ -543,7 +583,7 @@ def main(argv=None):
                                 mask_key="pred_mask", crop=flags.test_crop, gt_rule=flags.dataset, component=_component(flags),
                                 connectivity=flags.connectivity, crf=_crf(flags), overlay=_overlay(flags),
                                 detections=_detections(flags), tracks=_tracks(flags), instances=_instances(flags),
-                                follow=_follow(flags))
+                                follow=_follow(flags), objects=_objects(flags))
         return 0
     _sources(flags, "ensemble")
     learner.setup_inference(flags, aug_test=True)

@@ -83,6 +83,12 @@ _DEFS = [
     # sequence among those with rows in at least track_min_frames frames (native_results.follow_tracks); none: off
     ("follow", str, "none"),
     ("track_min_frames", int, 1),
+    # not reference flags: with --tracks, --objects matches every object of a multi-object annotation (ids 1..objects_max, read from the
+    # dataset's annotations or from objects_dir/<sequence>/<frame>.png) to one track and reports J per object
+    # (native_results.object_overlaps, native_results.match_tracks)
+    ("objects", bool, False),
+    ("objects_max", int, 16),
+    ("objects_dir", str, ""),
 ]
 
 

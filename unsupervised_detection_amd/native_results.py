@@ -1,7 +1,7 @@
 """Output stage at native resolution: restore a batch of masks to each frame's own size, score them there and export them.
 
 The steps live in one module each -- native_restore (restore_masks), native_components (select_components), native_detections
-(component_boxes), native_tracks (link_detections), native_instances (instance_maps) and native_follow (follow_tracks) -- and this module drives them over a folder of results.  Their public names are
+(component_boxes), native_tracks (link_detections), native_instances (instance_maps), native_follow (follow_tracks) and native_objects (object_overlaps, match_tracks) -- and this module drives them over a folder of results.  Their public names are
 importable from here as well.
 
   GtRule / GT_RULES / GtBatch / load_gt_device  a dataset's annotations binarised at native size, in one ragged.PackedLayout per batch
@@ -11,8 +11,8 @@ importable from here as well.
                                                 restored batch: unary from the restored bytes, the frames read at their own size,
                                                 one call of udet_dense_crf_ragged (csrc/crf.hip) -> the labels as the binary masks
   restore_results_dir(results_dir, frame_lists, out_dir, ...)   restore [+ CRF] [+ component selection] [+ detections [+ tracks
-                                                [+ instances]]] + J / F + <sequence>/<frame>.png, result_<k>.mat, native_eval.json
-                                                [, detections/<sequence>.json [, tracks/<sequence>.json [, instances/<sequence>/<frame>.png]]]
+                                                [+ instances] [+ objects]]] + J / F + <sequence>/<frame>.png, result_<k>.mat, native_eval.json
+                                                [, detections/<sequence>.json [, tracks/<sequence>.json [, instances/<sequence>/<frame>.png] [, objects/<sequence>.json]]]
   frame_lists_from_reader(flags)                {category: [(image, annotation), ...]} in the readers' own test order; (image, None) for
                                                 a folder of frames without annotations (--dataset FRAMES), which restore_results_dir
                                                 takes in its annotation-free mode; overlay=... draws the final masks on the frames
@@ -24,7 +24,8 @@ is restore_results_dir(tracks={...}), across frames in which a c
 (DESIGN.md 7.9); the tracks as per-frame instance maps, their picture and a track's J against the annotation is
 restore_results_dir(instances={...}); exporting and scoring the masks of whole tracks, chosen without the annotation, is
 restore_results_dir(follow={...}) (native_follow); linking along the optical flow between the frames is
-restore_results_dir(tracks={"motion": {...}}) (native_motion)."""
+restore_results_dir(tracks={"motion": {...}}) (native_motion); matching the tracks one-to-one to the objects of a
+multi-object annotation, with J per object, is restore_results_dir(objects={...}) (native_objects)."""
 import functools
 import os
 from types import SimpleNamespace
@@ -39,6 +40,8 @@ from .native_follow import (FOLLOW_DEFAULTS, FOLLOW_RULES, FollowedMasks, check_
                             follow_tracks, keep_words)
 from .native_instances import (INSTANCE_PALETTE_BYTES, INSTANCE_UNASSIGNED, INSTANCE_WRAP, InstanceMaps, check_instance_arguments,  # noqa: F401
                                instance_maps, instance_params, track_gt_scores)
+from .native_objects import (MAX_OBJECTS, OBJECT_DEFAULTS, OBJECT_RULES, ObjectOverlaps, ObjectRule, check_object_arguments,  # noqa: F401
+                             load_objects_device, match_tracks, object_overlaps, object_params, objects_summary)
 from .native_restore import TAB, RestoredMasks, build_restore_tables, check_restore_tables, restore_box, restore_masks  # noqa: F401
 from .native_motion import BackwardFlow, flow_displacements  # noqa: F401
 from .native_tracks import (TRACK_DEFAULTS, TRACK_MAX_GAP, TrackHistory, Tracks, TrackTail, check_link_arguments,  # noqa: F401
@@ -240,6 +243,13 @@ def _resolve_options(o):
         if o.follow["rule"] == "best_gt" and (o.instances is None or o.free):
             raise ValueError('follow rule "best_gt" scores the tracks against the annotation: it needs instances and annotations')
     o.rule = None if o.free else (GT_RULES[o.gt_rule] if isinstance(o.gt_rule, str) else o.gt_rule)
+    if o.objects is not None:
+        if o.tracks is None:
+            raise ValueError("objects matches the annotated objects to the tracks: it needs tracks")
+        if o.free:
+            raise ValueError("objects scores the tracks against multi-object annotations: it needs annotations")
+        o.objects = object_params(o.objects)
+        o.object_rule = OBJECT_RULES.get(o.gt_rule, ObjectRule()) if isinstance(o.gt_rule, str) else ObjectRule()
 
 
 def _dump_json(content, *path):
@@ -307,6 +317,38 @@ def _held(obj, drops):
     return c
 
 
+def _object_paths(o, cat, rows):
+    """The object annotations of a batch's frames: the frame list's own annotation paths, or with objects["dir"]
+    <dir>/<category>/<frame stem>.png -- a missing file is an IOError that names it."""
+    if o.objects["dir"] is None:
+        return [a for _, a in rows]
+    paths = [os.path.join(o.objects["dir"], cat, os.path.splitext(os.path.basename(img))[0] + ".png") for img, _ in rows]
+    for p in paths:
+        if not os.path.isfile(p):
+            raise IOError("objects: no object annotation {!r}".format(p))
+    return paths
+
+
+def _match_category(cat, records, obj, starts, o):
+    """The end of a category under `objects`: match_tracks over the held host tables (obj: per frame ids, row_obj, obj_area, void pixels
+    and the largest id seen), every sequence's record with its void_pixels, one warning per sequence with ids above objects["max"], and
+    <out_dir>/objects/<category>.json."""
+    import warnings
+    seqs = match_tracks(list(records.values()), obj["ids"], obj["row_obj"], obj["area"], starts, o.skip_ends)
+    lo, out = 0, []
+    for seq in seqs:
+        hi = lo + seq["frames"]
+        void = sum(obj["void"][lo:hi])
+        if any(m > o.objects["max"] for m in obj["max_id"][lo:hi]):
+            warnings.warn("{}: object ids up to {} in the annotations of frames {}..{}, above objects_max = {}: those pixels count as void; "
+                          "pass a larger --objects_max".format(cat, max(obj["max_id"][lo:hi]), lo + 1, hi, o.objects["max"]))
+        out.append({"frames": seq["frames"], "objects": seq["objects"], "J_mean": seq["J_mean"], "void_pixels": int(void),
+                    "unmatched_tracks": seq["unmatched_tracks"]})
+        lo = hi
+    _dump_json(out, o.out_dir, "objects", cat + ".json")
+    return out
+
+
 def _follow_category(cat, held, words, o, j, f, fg):
     """Pass 2 of a category under `follow`: per held batch, in this order, load gt, keep (the kept rows' masks), score, draw, draw boxes,
     write.  The frames of the overlay are read again, not held.  Returns per frame kept / (kept + dropped), 0 without foreground."""
@@ -350,6 +392,7 @@ def _restore_category(cat, entries, o):
     if motion and hasattr(o.motion_flow, "reset"):
         o.motion_flow.reset()  # the category's first frame has no frame before it
     row_gts, gt_area, unassigned = [], [], []  # instances, per frame: row_gt of its records, its annotated pixels, the share of value 255
+    obj = {"ids": [], "row_obj": [], "area": [], "void": [], "max_id": []}  # objects, per frame: the small host tables match_tracks reads
     held, score_sums = [], []  # follow: per batch what pass 2 reads, held on the device; per frame the score_sum of its rows
     own_overlay = o.overlay is not None and (o.follow is None or (o.instances is not None and o.instances["overlay"]))  # drawn in this loop
     for s in range(0, len(entries), o.batch):
@@ -399,6 +442,17 @@ def _restore_category(cat, entries, o):
                     row_gts += [[int(v) for v in row_gt[i][:len(r)]] for i, r in enumerate(recs)]
                     gt_area += [int(v) for v in stats[:, 2]]
                     unassigned += [int(u) / (int(a) + int(u)) if int(a) + int(u) else 0.0 for a, u in stats[:, :2]]
+                if o.objects is not None:
+                    ann = o.load_objects(_object_paths(o, cat, rows), o.object_rule)
+                    row_obj, obj_area, ostats = o.overlaps(labelled, det, ann, o.objects["max"]).host()
+                    ids = trk.host()[2]
+                    obj["ids"] += [[int(v) for v in ids[i][:len(r)]] for i, r in enumerate(recs)]
+                    obj["row_obj"] += [[[int(v) for v in row] for row in row_obj[i][:len(r)]] for i, r in enumerate(recs)]
+                    obj["area"] += [[int(v) for v in obj_area[i]] for i in range(len(rows))]
+                    obj["void"] += [int(v) for v in ostats[:, 1]]
+                    top = getattr(ann, "max_id", None)
+                    obj["max_id"] += [0] * len(rows) if top is None else [int(v) for v in top]
+                    ann = None  # no per-pixel data is held
             records.update(zip(stems, recs))
         if o.follow is not None:  # pass 1 of 2: what depends on the final binary mask waits until the category's tracks are known
             held.append((s, rows, stems, labelled, det, _held(trk, HELD_TRACK_DROPS), _held(res, HELD_RESTORED_DROPS)))
@@ -439,6 +493,12 @@ def _restore_category(cat, entries, o):
             rec["kept_mean"] = float(np.mean(kept)) if kept else 0.0
             for seq, ids in zip(summary, followed):
                 seq["followed"] = ids
+        if o.objects is not None:
+            rec["objects"] = _match_category(cat, records, obj, starts, o)
+            for seq, m in zip(summary, rec["objects"]):
+                taken = {v["track"]: oid for oid, v in m["objects"].items() if v["track"] is not None}
+                for t in seq["tracks"]:
+                    t["object"] = taken.get(t["id"])
         _dump_json(summary, o.out_dir, "tracks", cat + ".json")
         lengths = [t["frames"] for seq in summary for t in seq["tracks"]]
         rec["tracks"], rec["track_len_mean"] = len(lengths), float(np.mean(lengths)) if lengths else 0.0
@@ -492,6 +552,11 @@ def _summary(cats, o):
             seq["kept_mean"] = cats[c]["kept_mean"]
     if o.tracks is not None and "motion" in o.tracks:
         out["track_motion"] = {"size": list(o.tracks["motion"]["size"])}
+    if o.objects is not None:
+        out["objects"] = objects_summary(o.objects, {c: r["objects"] for c, r in cats.items()})
+        if o.verbose:
+            for c, v in out["objects"]["sequences"].items():
+                print("  {:<24s} {:3d} objects   J mean {:.4f}".format(c, sum(len(q["objects"]) for q in cats[c]["objects"]), v))
     return out
 
 
@@ -502,7 +567,7 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
                         detect=component_boxes, draw_boxes=draw_detection_boxes, tracks=None, link=link_detections,
                         draw_track_boxes=draw_track_detection_boxes, instances=None, paint=instance_maps,
                         draw_instances=draw_instance_overlays, follow=None, keep=follow_tracks, motion_flow=None,
-                        displace=flow_displacements):
+                        displace=flow_displacements, objects=None, load_objects=load_objects_device, overlaps=object_overlaps):
     """Restore, score and export a folder of <category>/result_<k>.mat files (test_generator --generate_visualization,
     post_processing.run_crf, ...) at native resolution.  frame_lists: {category: [(image_path, annotation_path), ...]} in the
     reader's own test order; result_<k>.mat of a category belongs to entry k-1 (the numbering evaluation.evaluate_masks writes; for
@@ -584,8 +649,21 @@ def restore_results_dir(results_dir, frame_lists, out_dir, mask_key="mask", crop
     over its frames of kept / (kept + dropped) foreground pixels, 0 for a frame without foreground), the sequences of
     tracks/<category>.json "followed": [ids]; new keys come after the existing ones.  With None nothing of this runs and every file is
     byte for byte what it is without the argument.
+    objects (None: off; needs tracks and annotations -- each missing one is a ValueError that names it): {"max": O (16; 1..32), "dir": D
+    (None)}, {} for the defaults.  After the link every batch's object annotations are read as ids, not binarised (load_objects(paths,
+    rule): load_objects_device -- a mode-"P" PNG gives its palette indices, a mode-"L" image its grey values) from the frame list's own
+    annotation paths, or with dir from <dir>/<category>/<frame stem>.png (a missing file is an IOError that names it), and go through
+    overlaps(labelled, det, ids, max) (object_overlaps: two launches per batch); only its small host tables and the rows' track ids are
+    kept.  At the category's end match_tracks assigns every annotated object at most one track, one-to-one, maximising the summed
+    sequence-mean J over the frames the DAVIS table counts (skip_ends), and <out_dir>/objects/<category>.json holds per sequence
+    {"frames", "objects": {id: {"track", "J": {mean, recall, decay}, "frames_annotated"}}, "J_mean", "void_pixels", "unmatched_tracks"};
+    every track of tracks/<category>.json gains "object" (id or null) after its other keys and the json gains "objects": {"max", "J":
+    {mean, recall, decay} over all objects of all sequences, "sequences": {name: J_mean}} after its other keys.  Bytes above max count as
+    void_pixels; ids in max + 1..254 give one warning per sequence that suggests a larger --objects_max (255 is the void label and warns
+    nothing).  The binarised annotation and everything computed from it stay as they are; with None nothing of this runs and every file
+    is byte for byte what it is without the argument.
     restore / load_gt / score / select / load_images / refine / load_sizes / draw / detect / draw_boxes / link / draw_track_boxes / paint /
-    draw_instances / keep / motion_flow / displace are injectable: the host logic runs without a GPU on numpy stand-ins."""
+    draw_instances / keep / motion_flow / displace / load_objects / overlaps are injectable: the host logic runs without a GPU on numpy stand-ins."""
     o = SimpleNamespace(**locals())  # every argument under its own name: the options and the injected callables
     _resolve_options(o)
     cats = {cat: _restore_category(cat, entries, o) for cat, entries in frame_lists.items()}
