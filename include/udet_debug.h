@@ -202,6 +202,54 @@ int udet_debug_conv2d_ex(const udet_debug_conv_ex* args, void* workspace, size_t
  * to 64), then 8 Mi floats of split-K slabs. */
 size_t udet_debug_conv2d_pair_ex_workspace_bytes(const udet_debug_conv_ex* a, const udet_debug_conv_ex* b);
 int udet_debug_conv2d_pair_ex(const udet_debug_conv_ex* a, const udet_debug_conv_ex* b, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- A 2-channel head in the GEMM + gather form, exactly as a plan runs it (csrc/plan_exec.hip run_fwd's head branch; tests/test_heads_gpu.py) ----
+ * A plan runs every layer plan_build.hip's mark_heads marks (2 output channels over a deep input, k*k*2 <= 64, stride 1 or the transposed 4x4
+ * stride-2 form) in three steps wherever the direct kernel of conv_thin.hip is not taken -- in fp32 every head with Kc > 64, in fp16 mode every head:
+ *   1. the weights packed with the taps folded into the N axis, wz [kc][ldz], ldz = k*k*2 rounded up to 32, column t*2 + c (pack mode 3; mode 4 for
+ *      the transposed form), with the gap map of form 0 above;  pack_job 0: launch_pack_taps_into_n (pack_job_kernel: the frozen PWC-Net weights),
+ *      1: a job of launch_pack_jobs (pack_jobs_kernel: the per-step table of the trainable networks);
+ *   2. ONE 1x1 convolution (conv_setup_fwd, launch_conv) of x [n,h,wd,ldx] channels [x_coff, x_coff + kc) with wz into z [n,h,wd,ldz];
+ *   3. launch_tap_gather on the tap table of conv_setup_fwd(k, k, 1, 1) / conv_setup_dgrad(2h, 2wd, 4, 4, 2, 1): y = bias + the per-tap shifted
+ *      reads of z, written to y [n,oh,ow,ldy] channels [y_coff, y_coff + 2) and nowhere else (oh x ow = h x wd; transposed: 2h x 2wd).  An even
+ *      ldy and y_coff with an 8-byte aligned y take tap_gather2_kernel (float2 per tap), everything else the generic tap_gather_kernel.
+ * This entry lays a workspace out and runs those three steps with the project's own functions; udet_debug_force_conv / udet_debug_last_conv /
+ * udet_debug_conv_fp16 act on the GEMM of step 2.  The stream is synchronised before the entry returns, and an error of that synchronisation
+ * is the entry's (UDET_ERR_HIP).
+ * w: HWIO [k,k,cin,2], transposed: HWOI [4,4,2,cin].  bias [2] or NULL.  kc, k_split, k_gap as in udet_debug_conv_ex (no gap: k_gap = 0,
+ * k_split = kc); channels past the real ones and inside the gap meet zero weight rows and need only be finite.
+ * Every argument is checked before the first HIP call:  NULL args / x / w / y, counts < 1, k_gap or k_split < 0, transposed or pack_job not
+ * 0 / 1, k*k*2 > 64, transposed with k != 4, 4 n h wd >= 2^28, a workspace that is NULL, not 64-byte aligned or smaller than
+ * udet_debug_conv2d_head_ex_workspace_bytes(args) -> UDET_ERR_ARG;  ldx, x_coff or kc not multiples of 4, x not 16-byte aligned, w / bias / y not
+ * 4-byte aligned -> UDET_ERR_ALIGN;  a window outside its row (x_coff + kc > ldx, y_coff + 2 > ldy) or a gap that does not fit (cin + k_gap > kc,
+ * k_split > cin with a gap) -> UDET_ERR_SHAPE.
+ * Workspace (floats): zero block [0, 64), ticket counters, one pack job, from 4224 wz (rounded up to 64), then z (rounded up to 64), then
+ * 8 Mi floats of split-K slabs. */
+typedef struct udet_debug_head_ex {
+  int n, h, wd, cin, k;
+  int kc, k_split, k_gap;
+  const float* x;
+  int ldx, x_coff;
+  const float* w;
+  const float* bias;
+  float* y;
+  int ldy, y_coff;
+  int transposed; /* 0: k x k stride 1; 1: 4x4 stride-2 transpose, output 2h x 2wd */
+  int pack_job;   /* 0: launch_pack_taps_into_n; 1: a mode 3 / 4 job through launch_pack_jobs */
+} udet_debug_head_ex;
+size_t udet_debug_conv2d_head_ex_workspace_bytes(const udet_debug_head_ex* args);
+int udet_debug_conv2d_head_ex(const udet_debug_head_ex* args, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- launch_warp_cost_volume with the slab arguments of a plan (csrc/plan_step.hip; tests/test_warp_cost_volume_slab_gpu.py) ----------------
+ * udet_warp_cost_volume (udet.h) passes a dense flow and a dense 81-column output without a c1 segment.  A plan calls the launcher IN PLACE on a
+ * level's slab: out[.., corr_coff + d] = the 81 correlations of c1 with warp(c2, flow * flow_scale), out[.., c1_coff + c] = c1 (c1_coff = -1:
+ * no such segment), the flow read at flow[.., f_coff + 0 / 1] of rows ldf wide -- flow == out, ldf == ldo on the slab -- and nothing else of a
+ * row written.  flow = NULL: c2 is not warped (level 6).  One launch, not synchronised.
+ * Checked before the launch:  NULL c1 / c2 / out or a count < 1 -> UDET_ERR_ARG;  the launcher's own conditions (c a multiple of 4; h, w >= 2
+ * with a flow; n h w max(c, ldo) < 2^31 -> UDET_ERR_SHAPE;  c1_coff and ldo multiples of 4 with a c1 segment -> UDET_ERR_ALIGN);  c1 / c2 (out
+ * with a c1 segment) not 16-byte aligned -> UDET_ERR_ALIGN;  a window outside its row (corr_coff + 81 > ldo, c1_coff + c > ldo,
+ * f_coff + 2 > ldf, negative offsets) -> UDET_ERR_SHAPE;  the corr and c1 windows overlapping, or with flow == out a different ldf / a flow
+ * window that overlaps the corr or c1 window -> UDET_ERR_ARG. */
+int udet_debug_warp_cost_volume_ex(const float* c1, const float* c2, const float* flow, int ldf, int f_coff, float flow_scale, float* out, int ldo,
+                                   int corr_coff, int c1_coff, int n, int h, int w, int c, void* stream);
 /* (The experiment knobs of earlier rounds -- lane choices and the work-skipping ablation mask -- are no longer reachable from any library
  * that links against libudet.so: they are compiled out of it.  `make -C unsupervised_detection_amd/csrc exp` builds libudet_exp.so, the same
  * sources with -DUDET_EXPERIMENT, which exports udet_exp_knob(id, value); tools/knob_bench.py is its only user.  csrc/plan.h lists the ids.) */

@@ -43,6 +43,14 @@ def drop_gap(xw, creal, k_split, k_gap):
     return torch.cat([xw[..., :k_split], xw[..., k_split + k_gap:creal + k_gap]], -1)
 
 
+def head(x, x_coff, kc, w, bias=None, k_split=None, k_gap=0, transposed=False):
+    """a 2-channel head as a plan launches it (udet_debug_conv2d_head_ex): the K window [x_coff, x_coff + kc) of x with the gap dropped,
+    through conv2d_same (w HWIO, stride 1) or, transposed, conv2d_transpose_k4s2_same (w HWOI [4, 4, cout, cin]), plus bias"""
+    creal = w.shape[3] if transposed else w.shape[2]
+    xr = drop_gap(x[..., x_coff:x_coff + kc], creal, kc if k_split is None else k_split, k_gap)
+    return O.conv2d_transpose_k4s2_same(xr, w, bias) if transposed else O.conv2d_same(xr, w, bias, 1, 1)
+
+
 def linear(form, xr, w, out_hw, stride=1, dilation=1, up=0):
     """the launch's sum over taps and real channels; xr: the A operand's real channels (forward forms: the layer's input, backward forms:
     the gradient w.r.t. the layer's output); w HWIO [k, k, cin, cout]; out_hw: the grid of the launch's output (backward forms)"""

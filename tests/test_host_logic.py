@@ -228,3 +228,118 @@ def test_debug_filter_gradient_entry_checks_its_arguments_before_any_device_call
     assert call(up=2) == ARG and call(up=2, gamma=fake, outs=(fake,) * 4, k=5) == ARG and call(up=3) == ARG
     assert call(x=None) == ARG and call(outs=(None, fake, None, None)) == ARG
     assert call(ws=None) == ARG and call(ws=fake + 4) == ARG and call(ws_bytes=64) == ARG
+
+
+def test_debug_head_entry_checks_its_arguments_before_any_device_call():
+    """udet_debug_conv2d_head_ex (tests/test_heads_gpu.py drives it on the GPU): every refusal of include/udet_debug.h with its code and
+    message, on fake pointers -- nothing reaches the device."""
+    from unsupervised_detection_amd import _devel
+    from unsupervised_detection_amd._ffi import lib
+    import ctypes
+    SHAPE, ALIGN, ARG = -1, -2, -5
+    fake = 1 << 20  # never dereferenced: every check comes before the first HIP call
+    base = dict(n=1, h=4, wd=5, cin=36, k=3, kc=40, k_split=40, k_gap=0, x=fake, ldx=48, x_coff=4, w=fake, bias=fake, y=fake, ldy=4, y_coff=0,
+                transposed=0, pack_job=0)
+    need = _devel.conv2d_head_ex_workspace_bytes(**base)
+    # zero block, tickets, job slot (4224 floats), wz [40][32], z [20][32] each rounded up to 64 floats, 8 Mi floats of split-K slabs
+    assert need == 4 * (4224 + 40 * 32 + 20 * 32 + (8 << 20))
+
+    def call(ws=fake, ws_bytes=need, **over):
+        a = _devel.head_ex_args(**{**base, **over})
+        return _devel.dbg.udet_debug_conv2d_head_ex(ctypes.byref(a), ws, ws_bytes, None)
+
+    def refused(code, text, **over):
+        assert call(**over) == code, over
+        assert text in lib.udet_last_error(), (over, lib.udet_last_error())
+
+    assert _devel.dbg.udet_debug_conv2d_head_ex(None, fake, need, None) == ARG
+    for name in ("x", "w", "y"):  # a NULL operand
+        refused(ARG, b"must not be NULL", **{name: None})
+    for name in ("n", "h", "wd", "cin", "k", "kc"):
+        refused(ARG, b"bad count", **{name: 0})
+    refused(ARG, b"bad count", k_gap=-1)
+    refused(ARG, b"bad count", k_split=-1)
+    refused(ARG, b"unknown transposed", transposed=2)
+    refused(ARG, b"unknown transposed", transposed=-1)
+    refused(ARG, b"unknown pack_job", pack_job=2)
+    refused(ARG, b"exceed the 64", k=6)       # 6*6*2 = 72 columns
+    refused(ARG, b"exceed the 64", k=200)     # (no overflow of k*k)
+    refused(ARG, b"4x4 stride 2", transposed=1, k=3)
+    refused(ARG, b"grid too large", n=1 << 12, h=1 << 8, wd=1 << 8)
+    # alignment of the A operand's window and of the pointers
+    refused(ALIGN, b"multiples of 4", ldx=50)
+    refused(ALIGN, b"multiples of 4", x_coff=2)
+    refused(ALIGN, b"multiples of 4", kc=42)
+    refused(ALIGN, b"multiples of 4", x=fake + 8)
+    for name in ("w", "bias", "y"):
+        refused(ALIGN, b"misaligned float pointer", **{name: fake + 2})
+    # windows outside their rows, a gap that does not fit
+    refused(SHAPE, b"x window", x_coff=12)             # 12 + 40 > 48
+    refused(SHAPE, b"x window", ldx=36, x_coff=0)
+    refused(SHAPE, b"do not fit", cin=44)              # more real channels than kc
+    refused(SHAPE, b"do not fit", k_split=20, k_gap=8)  # 36 + 8 > 40
+    refused(SHAPE, b"do not fit", cin=30, k_split=32, k_gap=4)  # the gap starts past the real channels
+    refused(SHAPE, b"y window", ldy=4, y_coff=3)
+    refused(SHAPE, b"y window", ldy=1, y_coff=0)
+    refused(SHAPE, b"y window", y_coff=-1)
+    # workspace: NULL, not 64-byte aligned, too small
+    refused(ARG, b"workspace", ws=None)
+    refused(ARG, b"workspace", ws=fake + 32)
+    refused(ARG, b"workspace", ws_bytes=need - 4)
+    # a legal gap map and the transposed form change only the workspace need
+    assert _devel.conv2d_head_ex_workspace_bytes(**{**base, "k": 4, "transposed": 1}) == need
+    assert _devel.conv2d_head_ex_workspace_bytes(**{**base, "k": 5}) == 4 * (4224 + 40 * 64 + 20 * 64 + (8 << 20))
+    assert _devel.conv2d_head_ex_workspace_bytes(**{**base, "k": 6}) == 0
+
+
+def test_debug_warp_cost_volume_entry_checks_its_arguments_before_the_launch():
+    """udet_debug_warp_cost_volume_ex (tests/test_warp_cost_volume_slab_gpu.py): the launcher's own conditions, the three windows and their
+    overlap on a slab, refused on the host with fake pointers."""
+    from unsupervised_detection_amd._devel import dbg
+    from unsupervised_detection_amd._ffi import lib
+    SHAPE, ALIGN, ARG = -1, -2, -5
+    fake, other = 1 << 20, 1 << 24
+    C = 32
+    ld = 568  # a level's slab: corr at 448, c1 at 532, flow at 532 + C
+    base = dict(c1=other, c2=other + 4096, flow=fake, ldf=ld, f_coff=532 + C, scale=2.5, out=fake, ldo=ld, corr_coff=448, c1_coff=532, n=2, h=6,
+                w=7, c=C)
+
+    def refused(code, text, **over):
+        a = {**base, **over}
+        st = dbg.udet_debug_warp_cost_volume_ex(a["c1"], a["c2"], a["flow"], a["ldf"], a["f_coff"], a["scale"], a["out"], a["ldo"], a["corr_coff"],
+                                                a["c1_coff"], a["n"], a["h"], a["w"], a["c"], None)
+        assert st == code, (over, st, lib.udet_last_error())
+        assert text in lib.udet_last_error(), (over, lib.udet_last_error())
+
+    for name in ("c1", "c2", "out"):  # a NULL operand (flow may be NULL: level 6)
+        refused(ARG, b"NULL operand", **{name: None})
+    for name in ("n", "h", "w", "c"):
+        refused(ARG, b"bad count", **{name: 0})
+    # the launcher's own conditions
+    refused(SHAPE, b"multiple of 4", c=30)
+    refused(SHAPE, b"H,W >= 2", h=1)
+    refused(SHAPE, b"H,W >= 2", w=1)
+    refused(SHAPE, b"too large", n=1 << 10, h=1 << 10, w=1 << 10)
+    refused(ALIGN, b"multiples of 4", c1_coff=530)
+    refused(ALIGN, b"multiples of 4", ldo=570, ldf=570)
+    refused(ALIGN, b"16-byte aligned", c1=other + 4)
+    refused(ALIGN, b"16-byte aligned", c2=other + 8)
+    refused(ALIGN, b"16-byte aligned", out=fake + 4, flow=fake + 4)
+    refused(ALIGN, b"16-byte aligned", flow=other + 2, ldf=2, f_coff=0)
+    # windows outside their rows
+    refused(SHAPE, b"corr window", corr_coff=488)          # 488 + 81 > 568
+    refused(SHAPE, b"corr window", corr_coff=-1)
+    refused(SHAPE, b"corr window", ldo=80, flow=None, c1_coff=-1, corr_coff=0)
+    refused(SHAPE, b"c1 window", c1_coff=540)              # 540 + 32 > 568
+    refused(SHAPE, b"c1 window", c1_coff=-2)
+    refused(SHAPE, b"flow window", f_coff=567)
+    refused(SHAPE, b"flow window", f_coff=-1)
+    refused(SHAPE, b"flow window", flow=other + 8192, ldf=1, f_coff=0)
+    # overlapping windows
+    refused(ARG, b"corr and c1 windows overlap", c1_coff=528)      # corr ends at 529
+    refused(ARG, b"corr and c1 windows overlap", c1_coff=420)      # c1 [420, 452) reaches into corr
+    refused(ARG, b"flow window overlaps", f_coff=528)              # inside corr
+    refused(ARG, b"flow window overlaps", f_coff=447)              # its second float is corr's first
+    refused(ARG, b"flow window overlaps", f_coff=563)              # c1's last float
+    refused(ARG, b"flow window overlaps", f_coff=531)              # the gap's last float and c1's first
+    refused(ARG, b"ldf == ldo", ldf=576)

@@ -92,6 +92,21 @@ dbg.udet_debug_conv2d_pair_ex.restype = ctypes.c_int
 dbg.udet_debug_conv2d_pair_ex.argtypes = [ctypes.POINTER(ConvEx), ctypes.POINTER(ConvEx), _p, ctypes.c_size_t, _p]
 
 
+class HeadEx(ctypes.Structure):
+    """udet_debug_head_ex (include/udet_debug.h): a 2-channel head in the GEMM + gather form as a plan runs it; unset fields are 0 / NULL."""
+    _fields_ = ([(k, _i) for k in ("n", "h", "wd", "cin", "k", "kc", "k_split", "k_gap")]
+                + [("x", _p), ("ldx", _i), ("x_coff", _i), ("w", _p), ("bias", _p), ("y", _p), ("ldy", _i), ("y_coff", _i), ("transposed", _i),
+                   ("pack_job", _i)])
+
+
+dbg.udet_debug_conv2d_head_ex_workspace_bytes.restype = ctypes.c_size_t
+dbg.udet_debug_conv2d_head_ex_workspace_bytes.argtypes = [ctypes.POINTER(HeadEx)]
+dbg.udet_debug_conv2d_head_ex.restype = ctypes.c_int
+dbg.udet_debug_conv2d_head_ex.argtypes = [ctypes.POINTER(HeadEx), _p, ctypes.c_size_t, _p]
+dbg.udet_debug_warp_cost_volume_ex.restype = ctypes.c_int
+dbg.udet_debug_warp_cost_volume_ex.argtypes = [_p, _p, _p, _i, _i, _f, _p, _i, _i, _i, _i, _i, _i, _i, _p]
+
+
 def _workspace_and_stream(workspace, stream):
     if workspace is None or isinstance(workspace, tuple):
         ptr, nbytes = workspace or (None, 0)
@@ -136,6 +151,38 @@ def conv_ex_args(**fields) -> ConvEx:
 
 def conv2d_ex_workspace_bytes(**fields) -> int:
     return int(dbg.udet_debug_conv2d_ex_workspace_bytes(ctypes.byref(conv_ex_args(**fields))))
+
+
+def _pointer(v):
+    if isinstance(v, tuple):
+        return v[0].data_ptr() + v[1] * v[0].element_size()
+    return v.data_ptr() if hasattr(v, "data_ptr") else v
+
+
+def head_ex_args(**fields) -> HeadEx:
+    a = HeadEx()
+    for k, v in fields.items():
+        setattr(a, k, _pointer(v))
+    return a
+
+
+def conv2d_head_ex_workspace_bytes(**fields) -> int:
+    return int(dbg.udet_debug_conv2d_head_ex_workspace_bytes(ctypes.byref(head_ex_args(**fields))))
+
+
+def conv2d_head_ex(workspace=None, stream=None, **fields):
+    """udet_debug_conv2d_head_ex with the struct's fields as keywords (tensors, (tensor, element offset) or plain integers for the pointers, as
+    conv2d_ex takes them); workspace: a float32 device tensor of conv2d_head_ex_workspace_bytes(**fields) bytes, or (pointer, bytes)."""
+    a = head_ex_args(**fields)
+    _check(dbg.udet_debug_conv2d_head_ex(ctypes.byref(a), *_workspace_and_stream(workspace, stream)))
+
+
+def warp_cost_volume_ex(c1, c2, flow, ldf, f_coff, flow_scale, out, ldo, corr_coff, c1_coff, n, h, w, c, stream=None):
+    """udet_debug_warp_cost_volume_ex on the current stream: launch_warp_cost_volume with a plan's slab arguments (flow None: level 6; pointers
+    as tensors, (tensor, element offset) or plain integers); a refusal raises ValueError (_ffi.check) before anything reaches the device."""
+    _, _, stream = _workspace_and_stream(None, stream)
+    _check(dbg.udet_debug_warp_cost_volume_ex(_pointer(c1), _pointer(c2), None if flow is None else _pointer(flow), ldf, f_coff, flow_scale,
+                                              _pointer(out), ldo, corr_coff, c1_coff, n, h, w, c, stream))
 
 
 def launch(name: str, *args):

@@ -455,6 +455,126 @@ int udet_debug_conv2d_pair_ex(const udet_debug_conv_ex* a_, const udet_debug_con
   return st;
 }
 }  // extern "C"
+// ---- a 2-channel head in the GEMM + gather form, exactly the sequence of run_fwd's head branch (csrc/plan_exec.hip; tests/test_heads_gpu.py):
+// the weights packed with the taps folded into the N axis (modes 3 / 4, either packer of a plan), ONE 1x1 GEMM over the channel axis into z
+// [n, h, wd, ldz], then launch_tap_gather (bias + the per-tap shifted reads of z) into the output window.  A change to that branch belongs
+// here too.
+namespace {
+int hex_taps(const udet_debug_head_ex& a) { return a.k * a.k; }
+int hex_ldz(const udet_debug_head_ex& a) { return round_up(hex_taps(a) * 2, 32); }
+size_t hex_wz_floats(const udet_debug_head_ex& a) { return upc_align64((size_t)a.kc * hex_ldz(a)); }
+size_t hex_z_floats(const udet_debug_head_ex& a) { return upc_align64((size_t)a.n * a.h * a.wd * hex_ldz(a)); }
+int hex_check(const udet_debug_head_ex& a, const void* workspace, size_t workspace_bytes) {
+  const char* who = "debug_conv2d_head_ex";
+  if (!a.x || !a.w || !a.y) { set_error("%s: x, w and y must not be NULL", who); return UDET_ERR_ARG; }
+  if (a.n < 1 || a.h < 1 || a.wd < 1 || a.cin < 1 || a.k < 1 || a.kc < 1 || a.k_gap < 0 || a.k_split < 0) { set_error("%s: bad count", who); return UDET_ERR_ARG; }
+  if (a.transposed != 0 && a.transposed != 1) { set_error("%s: unknown transposed %d", who, a.transposed); return UDET_ERR_ARG; }
+  if (a.pack_job != 0 && a.pack_job != 1) { set_error("%s: unknown pack_job %d", who, a.pack_job); return UDET_ERR_ARG; }
+  if (a.k > 8 || a.k * a.k * 2 > 64) { set_error("%s: k*k*2 = %d columns exceed the 64 a head's z row holds", who, a.k * a.k * 2); return UDET_ERR_ARG; }
+  if (a.transposed && a.k != 4) { set_error("%s: the transposed form is 4x4 stride 2 (k = %d)", who, a.k); return UDET_ERR_ARG; }
+  if ((long)a.n * (2L * a.h) * (2L * a.wd) >= (1L << 28)) { set_error("%s: grid too large", who); return UDET_ERR_ARG; }
+  if (a.ldx % 4 || a.x_coff % 4 || a.kc % 4 || cex_misaligned(a.x, 16)) {
+    set_error("%s: ldx=%d x_coff=%d kc=%d must be multiples of 4 and x 16-byte aligned", who, a.ldx, a.x_coff, a.kc);
+    return UDET_ERR_ALIGN;
+  }
+  if (cex_misaligned(a.w, 4) || cex_misaligned(a.bias, 4) || cex_misaligned(a.y, 4)) { set_error("%s: misaligned float pointer", who); return UDET_ERR_ALIGN; }
+  if (cex_outside(a.ldx, a.x_coff, a.kc)) { set_error("%s: x window %d+%d outside its row of %d", who, a.x_coff, a.kc, a.ldx); return UDET_ERR_SHAPE; }
+  if ((long)a.cin + a.k_gap > a.kc || (a.k_gap > 0 && a.k_split > a.cin)) {
+    set_error("%s: %d real channels and a gap of %d at %d do not fit kc=%d", who, a.cin, a.k_gap, a.k_split, a.kc);
+    return UDET_ERR_SHAPE;
+  }
+  if (cex_outside(a.ldy, a.y_coff, 2)) { set_error("%s: y window %d+2 outside its row of %d", who, a.y_coff, a.ldy); return UDET_ERR_SHAPE; }
+  if (!workspace || cex_misaligned(workspace, 64) || workspace_bytes < udet_debug_conv2d_head_ex_workspace_bytes(&a)) {
+    set_error("%s: workspace must be 64-byte aligned and hold udet_debug_conv2d_head_ex_workspace_bytes", who);
+    return UDET_ERR_ARG;
+  }
+  return UDET_OK;
+}
+}  // namespace
+extern "C" {
+size_t udet_debug_conv2d_head_ex_workspace_bytes(const udet_debug_head_ex* a) {
+  if (!a || a->n < 1 || a->h < 1 || a->wd < 1 || a->kc < 1 || a->k < 1 || a->k > 8 || a->k * a->k * 2 > 64) return 0;
+  return (CEX_W + hex_wz_floats(*a) + hex_z_floats(*a) + CEX_SLAB_FLOATS) * sizeof(float);
+}
+int udet_debug_conv2d_head_ex(const udet_debug_head_ex* args, void* workspace, size_t workspace_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!args) { set_error("debug_conv2d_head_ex: bad argument"); return UDET_ERR_ARG; }
+  const udet_debug_head_ex& a = *args;
+  UDET_TRY(hex_check(a, workspace, workspace_bytes));
+  float* ws = reinterpret_cast<float*>(workspace);
+  float* wz = ws + CEX_W;
+  float* z = wz + hex_wz_floats(a);
+  float* part = z + hex_z_floats(a);
+  const int T = hex_taps(a), ldz = hex_ldz(a);
+  UDET_HIP(hipMemsetAsync(ws, 0, CEX_JOB * sizeof(float), stream));  // zero block + ticket counters
+  PackJob j;  // (a host temporary: the stream is synchronised below)
+  if (!a.pack_job) {
+    UDET_TRY(launch_pack_taps_into_n(a.w, wz, T, a.cin, 2, a.kc, ldz, a.k_split, a.k_gap, a.transposed, stream));
+  } else {  // the job plan_pack.hip builds for a head of the trainable networks (mode 4: the same job on HWOI weights)
+    memset(&j, 0, sizeof(j));
+    j.gamma_off = j.beta_off = -1;
+    j.dst_off = (long)CEX_W; j.T = T; j.R = a.cin; j.C = 2; j.Kc = a.kc; j.ldw = ldz; j.k_split = a.k_split; j.k_gap = a.k_gap;
+    j.mode = a.transposed ? 4 : 3; j.total = (long)a.kc * ldz;
+    UDET_HIP(hipMemcpyAsync(ws + CEX_JOB, &j, sizeof(j), hipMemcpyHostToDevice, stream));
+    UDET_TRY(launch_pack_jobs(reinterpret_cast<const PackJob*>(ws + CEX_JOB), 1, a.w, ws, 1.f, stream));
+  }
+  int st;
+  {
+    ConvParams p;
+    memset(&p, 0, sizeof(p));
+    conv_setup_fwd(p, a.n, a.h, a.wd, 1, 1, 1, 1);
+    p.x = a.x; p.ldx = a.ldx; p.x_coff = a.x_coff;
+    p.wp = wz; p.Kc = a.kc; p.ldw = ldz;
+    p.y = z; p.ldy = ldz; p.y_coff = 0; p.Cout = T * 2;
+    p.partial = part; p.partial_cap = CEX_SLAB_FLOATS;
+    p.zero16 = ws; p.tickets = reinterpret_cast<int*>(ws + CEX_TICKETS);
+    st = launch_conv(p, stream);
+  }
+  if (st == UDET_OK) {
+    ConvParams g;
+    memset(&g, 0, sizeof(g));
+    if (a.transposed) (void)conv_setup_dgrad(g, 0, a.n, 2 * a.h, 2 * a.wd, a.k, a.k, 2, 1);
+    else conv_setup_fwd(g, a.n, a.h, a.wd, a.k, a.k, 1, 1);
+    g.H = a.h; g.W = a.wd;  // Z lives on the input grid
+    g.bias = a.bias;
+    g.y = a.y; g.ldy = a.ldy; g.y_coff = a.y_coff; g.Cout = 2;
+    st = launch_tap_gather(g, z, ldz, stream);
+  }
+  const hipError_t e = hipStreamSynchronize(stream);  // (a fault in a launch is this call's error, not the caller's next one)
+  if (st == UDET_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(stream)");
+  return st;
+}
+// launch_warp_cost_volume with a plan's slab arguments (csrc/plan_step.hip; tests/test_warp_cost_volume_slab_gpu.py): nothing but checks
+int udet_debug_warp_cost_volume_ex(const float* c1, const float* c2, const float* flow, int ldf, int f_coff, float flow_scale, float* out, int ldo,
+                                   int corr_coff, int c1_coff, int n, int h, int w, int c, void* stream) {
+  const char* who = "debug_warp_cost_volume_ex";
+  if (!c1 || !c2 || !out || n < 1 || h < 1 || w < 1 || c < 1) { set_error("%s: NULL operand or bad count", who); return UDET_ERR_ARG; }
+  // the launcher's own conditions, before anything reaches it
+  if (c % 4 != 0 || (flow && (h < 2 || w < 2))) { set_error("%s: C=%d must be a multiple of 4 and H,W >= 2 with a flow (got %dx%d)", who, c, h, w); return UDET_ERR_SHAPE; }
+  if (ldo < 1 || (long)n * h * w * (c > ldo ? c : ldo) >= (1L << 31)) { set_error("%s: tensor too large for 32-bit element offsets", who); return UDET_ERR_SHAPE; }
+  if (c1_coff >= 0 && ((c1_coff | ldo) & 3)) { set_error("%s: c1 segment offset %d / row stride %d must be multiples of 4", who, c1_coff, ldo); return UDET_ERR_ALIGN; }
+  if (cex_misaligned(c1, 16) || cex_misaligned(c2, 16) || cex_misaligned(flow, 4) || cex_misaligned(out, c1_coff >= 0 ? 16 : 4)) {
+    set_error("%s: c1 / c2 (and out with a c1 segment) must be 16-byte aligned, flow a float pointer", who);
+    return UDET_ERR_ALIGN;
+  }
+  // windows
+  if (corr_coff < 0 || (long)corr_coff + 81 > ldo) { set_error("%s: corr window %d+81 outside its row of %d", who, corr_coff, ldo); return UDET_ERR_SHAPE; }
+  if (c1_coff < -1 || (c1_coff >= 0 && (long)c1_coff + c > ldo)) { set_error("%s: c1 window %d+%d outside its row of %d", who, c1_coff, c, ldo); return UDET_ERR_SHAPE; }
+  if (flow && (ldf < 1 || f_coff < 0 || (long)f_coff + 2 > ldf)) { set_error("%s: flow window %d+2 outside its row of %d", who, f_coff, ldf); return UDET_ERR_SHAPE; }
+  if (flow && (long)n * h * w * ldf >= (1L << 31)) { set_error("%s: flow tensor too large", who); return UDET_ERR_SHAPE; }
+  auto overlap = [](long a0, long a1, long b0, long b1) { return a0 < b1 && b0 < a1; };
+  if (c1_coff >= 0 && overlap(corr_coff, corr_coff + 81L, c1_coff, (long)c1_coff + c)) { set_error("%s: the corr and c1 windows overlap", who); return UDET_ERR_ARG; }
+  if (flow && flow == out) {  // in place on a slab: the flow columns are read while the other windows are written
+    if (ldf != ldo) { set_error("%s: in place needs ldf == ldo", who); return UDET_ERR_ARG; }
+    if (overlap(f_coff, f_coff + 2L, corr_coff, corr_coff + 81L) || (c1_coff >= 0 && overlap(f_coff, f_coff + 2L, c1_coff, (long)c1_coff + c))) {
+      set_error("%s: the flow window overlaps the corr / c1 window of the same slab", who);
+      return UDET_ERR_ARG;
+    }
+  }
+  UDET_TRY(launch_warp_cost_volume(c1, c2, flow, ldf, f_coff, flow_scale, out, ldo, corr_coff, c1_coff, nullptr, n, h, w, c, (hipStream_t)stream));
+  return UDET_OK;
+}
+}  // extern "C"
 // ---- the glue launchers of elementwise.hip, one launch each (tests/test_glue_gpu.py): argument checks, then the launcher ---------------------
 namespace {
 const long GLUE_MAX_PIXELS = 1L << 31;

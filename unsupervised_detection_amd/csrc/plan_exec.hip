@@ -276,6 +276,7 @@ int run_fwd(Plan* P, const Layer& L, int N, float* ws, const Lane& ln) {
   if (L.col2im && !direct_head && fwd_launches(L) == 1) {
     // 2-channel head: the (tap, output channel) pairs become the N axis of ONE 1x1 GEMM over the deep channel axis
     // (every input byte read once, no 16x padding of the MFMA columns per tap), then a gather-sum over the taps
+    // (udet_debug_conv2d_head_ex, csrc/devel/api_debug.hip, repeats this sequence for tests/test_heads_gpu.py: carry a change here over there)
     const Buf& bz = P->buf(L.zbuf);
     ConvParams p;
     memset(&p, 0, sizeof(p));
