@@ -4,6 +4,10 @@ namespace udet {
 void same_pad(int in, int k, int s, int d, int* before, int* out);
 void conv_setup_fwd(ConvParams& p, int N, int H, int W, int kh, int kw, int s, int d);
 int conv_dgrad_classes(int s, int H, int W);
+// the taps are the full 3x3 grid {-d, 0, d}^2: *dil = d, at[a * 3 + b] = index of the tap at offset ((a - 1) d, (b - 1) d)  (conv_host.hip)
+bool conv_taps_3x3(const ConvTap* taps, int ntaps, int* dil, int at[9]);
+// raises a kernel's dynamic-LDS limit on the current device before its first launch there: once per (kernel, device), thread-safe
+int conv_set_dynamic_lds(const void* kernel, int bytes);
 void conv_force_config(int bm, int bn, int ks);  // conv_select.hip; the bit layout of udet_debug_force_conv
 // direct kernels for the 2-channel heads (conv_thin.hip): eligibility of a launch / the launches
 bool conv_thin_n_ok(const ConvParams& p);

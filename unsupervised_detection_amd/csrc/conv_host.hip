@@ -4,6 +4,10 @@
 
 #include <stdint.h>
 
+#include <map>
+#include <mutex>
+#include <utility>
+
 #include "common.h"
 #include "conv_host.h"
 #include "wino_pack.h"
@@ -41,6 +45,47 @@ void conv_setup_fwd(ConvParams& p, int N, int H, int W, int kh, int kw, int s, i
   p.ntaps = 0;
   for (int ky = 0; ky < kh; ++ky)
     for (int kx = 0; kx < kw; ++kx) push_tap(p, ky * d - pt, kx * d - pl, ky * kw + kx);
+}
+
+// the taps are the full 3x3 grid {-d, 0, d}^2 (no culled tap, none twice): *dil = d >= 1, at[a * 3 + b] = the index of the tap at offset
+// ((a - 1) d, (b - 1) d)
+bool conv_taps_3x3(const ConvTap* taps, int ntaps, int* dil, int at[9]) {
+  if (ntaps != 9) return false;
+  int d = 0;
+  for (int t = 0; t < 9; ++t) {
+    const int a = taps[t].dy < 0 ? -taps[t].dy : taps[t].dy;
+    if (a > d) d = a;
+  }
+  if (d < 1) return false;
+  for (int i = 0; i < 9; ++i) at[i] = -1;
+  for (int t = 0; t < 9; ++t) {
+    const int dy = taps[t].dy, dx = taps[t].dx;
+    if (dy % d != 0 || dx % d != 0) return false;
+    const int a = dy / d + 1, b = dx / d + 1;
+    if (a < 0 || a > 2 || b < 0 || b > 2 || at[a * 3 + b] >= 0) return false;
+    at[a * 3 + b] = t;
+  }
+  *dil = d;
+  return true;
+}
+
+// More than 64 KB of dynamic LDS needs the attribute once per kernel and DEVICE (a code object is loaded per device) -- and exactly once
+// under concurrent first launches: the status of the one call is kept per (kernel, device ordinal) behind a mutex.
+int conv_set_dynamic_lds(const void* kernel, int bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, hipError_t> done;
+  int dev = 0;
+  UDET_HIP(hipGetDevice(&dev));
+  hipError_t attr;
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    const auto key = std::make_pair(kernel, dev);
+    auto it = done.find(key);
+    if (it == done.end()) it = done.emplace(key, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)).first;
+    attr = it->second;
+  }
+  UDET_HIP(attr);
+  return UDET_OK;
 }
 
 // Number of launches the backward-data pass of a stride-s SAME conv over an (H,W) input needs: stride 2 on an even

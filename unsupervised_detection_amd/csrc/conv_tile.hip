@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "conv_host.h"
 
 namespace udet {
 
@@ -442,36 +443,20 @@ int launch_conv_tile(const ConvParams& p, int th, int cbmax, hipStream_t stream)
        {conv_tile_kernel<8, 16, TILE_MT_SMALL, TILE_MW_SMALL>, conv_tile_kernel<8, 16, TILE_MT_BIG, TILE_MW_BIG>}},
       {{conv_tile_kernel<4, 32, TILE_MT_SMALL, TILE_MW_SMALL>, conv_tile_kernel<4, 32, TILE_MT_BIG, TILE_MW_BIG>},
        {conv_tile_kernel<4, 16, TILE_MT_SMALL, TILE_MW_SMALL>, conv_tile_kernel<4, 16, TILE_MT_BIG, TILE_MW_BIG>}}};
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (int a = 0; a < 2; ++a)
-      for (int b = 0; b < 2; ++b)
-        for (int c = 0; c < 2; ++c)
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K[a][b][c]), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    attr_set = true;
-  }
+  static const Kern K16[2][2][2] = {
+      {{conv_tile_kernel<8, 32, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<8, 32, TILE_MT_BIG, TILE_MW_BIG, true>},
+       {conv_tile_kernel<8, 16, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<8, 16, TILE_MT_BIG, TILE_MW_BIG, true>}},
+      {{conv_tile_kernel<4, 32, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<4, 32, TILE_MT_BIG, TILE_MW_BIG, true>},
+       {conv_tile_kernel<4, 16, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<4, 16, TILE_MT_BIG, TILE_MW_BIG, true>}}};
+  const Kern (&T)[2][2][2] = p.f16 ? K16 : K;
+  for (int a = 0; a < 2; ++a)  // (the whole table of this precision, eagerly: the first launch of each form is not the one that pays)
+    for (int b = 0; b < 2; ++b)
+      for (int c = 0; c < 2; ++c) UDET_TRY(conv_set_dynamic_lds(reinterpret_cast<const void*>(T[a][b][c]), 96 * 1024));
   const int tiles = ((p.OWq + 31) / 32) * ((p.OHq + th - 1) / th) * p.N;
   const int ncls = p.ncls > 1 ? p.ncls : 1;
   const bool n16 = p.Cout <= 16;
   dim3 grid(tiles, n16 ? 1 : (p.Cout + 31) / 32, ncls);
-  if (p.f16) {
-    static const Kern K16[2][2][2] = {
-        {{conv_tile_kernel<8, 32, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<8, 32, TILE_MT_BIG, TILE_MW_BIG, true>},
-         {conv_tile_kernel<8, 16, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<8, 16, TILE_MT_BIG, TILE_MW_BIG, true>}},
-        {{conv_tile_kernel<4, 32, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<4, 32, TILE_MT_BIG, TILE_MW_BIG, true>},
-         {conv_tile_kernel<4, 16, TILE_MT_SMALL, TILE_MW_SMALL, true>, conv_tile_kernel<4, 16, TILE_MT_BIG, TILE_MW_BIG, true>}}};
-    static bool attr16 = false;
-    if (!attr16) {
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
-          for (int c = 0; c < 2; ++c)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K16[a][b][c]), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-      attr16 = true;
-    }
-    UDET_LAUNCH(K16[th == 4][n16][big], grid, dim3(256), lds, stream, p, g);
-  } else {
-    UDET_LAUNCH(K[th == 4][n16][big], grid, dim3(256), lds, stream, p, g);
-  }
+  UDET_LAUNCH(T[th == 4][n16][big], grid, dim3(256), lds, stream, p, g);
   UDET_HIP(hipGetLastError());
   return UDET_OK;
 }

@@ -23,14 +23,11 @@
 // generator's 64- and 128-channel 3x3 layers (models/nets.py:21-33).
 #include <type_traits>
 
-#include <mutex>
-
 #include "common.h"
 #include "conv_host.h"
+#include "wino_common.h"
 
 namespace udet {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 struct WwgGeom {
   int d;          // dilation
@@ -158,8 +155,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
           for (int c = 0; c < 4; ++c) { ta[c] = d0[c] - d2[c]; tb[c] = d1[c] - d3[c]; }  // rows 0, 3
         }
-        const float Va[4] = {ta[0] - ta[2], ta[1] + ta[2], ta[2] - ta[1], ta[1] - ta[3]};
-        const float Vb[4] = {tb[0] - tb[2], tb[1] + tb[2], tb[2] - tb[1], tb[1] - tb[3]};
+        float Va[4], Vb[4];
+        wino_bt(ta, Va);
+        wino_bt(tb, Vb);
         float fa[2], fb[2];  // the two rows of A e,  A = [1 0; 1 1; 1 -1; 0 -1]
         if (R == 0) { fa[0] = e[0][0] + e[1][0]; fa[1] = e[0][1] + e[1][1]; fb[0] = e[0][0] - e[1][0]; fb[1] = e[0][1] - e[1][1]; }
         else { fa[0] = e[0][0]; fa[1] = e[0][1]; fb[0] = -e[1][0]; fb[1] = -e[1][1]; }
@@ -202,7 +200,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int co = co0 + cob * 32 + li;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ci = ci0 + cib * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int ci = ci0 + cib * 32 + wino_acc_tile(r, lh);
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
       const float m0 = xch[sub][b][r][lane], m3 = xch[sub][3 + b][r][lane];
@@ -220,21 +218,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // the launch's taps are the full 3x3 grid {-d, 0, d}^2 of a stride-1 convolution (no culled tap), channels in whole 64-blocks
 static bool wwg_geometry(const WgradParams& p, WwgGeom* g) {
   if (p.ntaps != 9 || p.isy != 1 || p.isx != 1 || p.up_shift != 0 || p.ycls || p.swapped || p.OH != p.H || p.OW != p.W) return false;
-  int d = 0;
-  for (int t = 0; t < 9; ++t) {
-    const int a = p.taps[t].dy < 0 ? -p.taps[t].dy : p.taps[t].dy;
-    if (a > d) d = a;
-  }
-  if (d < 1) return false;
-  for (int i = 0; i < 9; ++i) g->tap_at[i] = -1;
-  for (int t = 0; t < 9; ++t) {
-    const int dy = p.taps[t].dy, dx = p.taps[t].dx;
-    if (dy % d != 0 || dx % d != 0) return false;
-    const int a = dy / d + 1, b = dx / d + 1;
-    if (a < 0 || a > 2 || b < 0 || b > 2 || g->tap_at[a * 3 + b] >= 0) return false;
-    g->tap_at[a * 3 + b] = t;
-  }
-  g->d = d;
+  if (!conv_taps_3x3(p.taps, p.ntaps, &g->d, g->tap_at)) return false;
+  const int d = g->d;
   const int Hs = (p.H + d - 1) / d, Ws = (p.W + d - 1) / d;  // the largest sub-lattice
   g->rows = (Hs + 1) / 2;
   g->per_row = ((Ws + 1) / 2 + 7) / 8;
@@ -271,20 +256,7 @@ int launch_wgrad_wino(const WgradParams& q, int slices, int ldn, hipStream_t str
   }
   g.slices = slices > g.strips ? g.strips : slices;
   g.ldn = ldn;
-  // 96 KB of dynamic LDS needs the attribute once per DEVICE (a code object is loaded per device) -- and exactly once under concurrent
-  // first launches: one once_flag per device ordinal
-  {
-    constexpr int MAXDEV = 64;
-    static std::once_flag once[MAXDEV];
-    static hipError_t attr[MAXDEV];
-    int dev = 0;
-    UDET_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= MAXDEV) { set_error("wgrad_wino: device ordinal %d out of range", dev); return UDET_ERR_ARG; }
-    std::call_once(once[dev], [&]() {
-      attr[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_wino8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, WWG_LDS);
-    });
-    UDET_HIP(attr[dev]);
-  }
+  UDET_TRY(conv_set_dynamic_lds(reinterpret_cast<const void*>(conv_wgrad_wino8_kernel), WWG_LDS));  // 96 KB
   const int blocks = (q.Cin / 64) * (q.Cout / 64);
   UDET_LAUNCH(conv_wgrad_wino8_kernel, dim3(blocks * g.slices), dim3(512), WWG_LDS, stream, q, g);
   UDET_HIP(hipGetLastError());
